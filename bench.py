@@ -73,6 +73,9 @@ def parse():
                          "(`config4_reference_phase1`; ~15 s of setup)")
     ap.add_argument("--long-window", type=int, default=3000,
                     help="when --steps < 1000: additionally time a window of this many steps (0 off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline workload, write the point its engine holds after its last "
+                         "timed step (x, basis, nonbasic labels, objective; y and d for the dual) as DIR/<name>.npy in float64")
     return ap.parse_args()
 
 
@@ -255,7 +258,7 @@ def rocprof_avg_us(which, dual, accept=None):
     return None, None, None
 
 
-def measure(ctx, args, m, n, seed, solver, steps, warmup, profile_steps, long_window=0, flat_override=None):
+def measure(ctx, args, m, n, seed, solver, steps, warmup, profile_steps, long_window=0, flat_override=None, dump=False):
     """One workload on this process group: W warm-up steps, K timed steps bracketed by barrier +
     synchronize on both sides (max over ranks), an optional longer window, per-kernel event times from
     a second run, and — sharded — the self-check against a single-GPU replay."""
@@ -325,6 +328,15 @@ def measure(ctx, args, m, n, seed, solver, steps, warmup, profile_steps, long_wi
                               "ms_per_step": round(1e3 * ldt / long_window, 6)}
         total_after += long_window
     out["resid"] = eng.inverse_residual() if world == 1 else None
+    if dump:
+        # outside the timed region: what a caller of the engine receives after the last timed step (read_point completes
+        # the iteration the two-launch pipeline left open); copied, since the sharded branch below reads the point again
+        eng.read_point()
+        outputs = {"x": fp.x, "basis": fp.B, "nonbasic": fp.N, "nonbasic_at": fp.Nb, "objective": np.array([fp.obj()]),
+                   "status_iterations": np.array([st, stats.iters])}
+        if dual:
+            outputs["y"], outputs["d"] = fp.y, fp.d
+        out["outputs"] = {k: np.asarray(v, dtype=np.float64).copy() for k, v in outputs.items()}
     if world > 1:
         # outside the timed region: the sharded run must have taken the pivots of a single-GPU run
         # (rank 0 replays them unsharded) and every rank must hold the same basis
@@ -357,7 +369,7 @@ def measure(ctx, args, m, n, seed, solver, steps, warmup, profile_steps, long_wi
                 # the peer-to-peer mailbox passed its self-test and still delivered something wrong: measure
                 # again over RCCL (every rank takes this branch: the verdict above is all-reduced) and say so
                 os.environ["ELLP_DIST_EXCHANGE"] = "rccl"
-                again = measure(ctx, args, m, n, seed, solver, steps, warmup, profile_steps, long_window)
+                again = measure(ctx, args, m, n, seed, solver, steps, warmup, profile_steps, long_window, dump=dump)
                 again["mailbox_failed"] = True
                 return again
             raise SystemExit(3)
@@ -473,7 +485,8 @@ def main():
     want_c5 = args.config5 == 1 or (args.config5 < 0 and is_c3)
     long_window = args.long_window if (args.steps < 1000 and args.long_window > 0) else 0
 
-    head = measure(ctx, args, m, n, args.seed, args.solver, args.steps, args.warmup, args.profile_steps, long_window)
+    head = measure(ctx, args, m, n, args.seed, args.solver, args.steps, args.warmup, args.profile_steps, long_window,
+                   dump=bool(args.dump_outputs))
     c5 = None
     if want_c5:
         c5m = measure(ctx, args, 4000, 40000, 20260305, "primal", args.config5_steps, 100,
@@ -692,6 +705,13 @@ def main():
         out["config3_full_solve_steepest_edge"] = c3se
     if c5 is not None:
         out["config5"] = c5
+    if "outputs" in head:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in head["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": sorted(head["outputs"]),
+                               "after_iterations": int(head["outputs"]["status_iterations"][1])}
     if cpu:
         out["speedup_vs_cpu_baseline"] = round(pivots_per_s / cpu["value"], 1)
     if cpu_same:
