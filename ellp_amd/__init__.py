@@ -126,6 +126,8 @@ def host_lib():
     L.ellp_solve.restype = C.c_int
     L.ellp_solve.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Opts), C.POINTER(_Result)]
     L.ellp_result_free.argtypes = [C.POINTER(_Result)]
+    L.ellp_solve_batch.restype = C.c_int
+    L.ellp_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_void_p]
     L.ellp_debug_phase1.restype = C.c_int
     L.ellp_debug_phase1.argtypes = [C.c_void_p, C.c_int, C.POINTER(_FlatPhase), C.c_char_p, C.c_size_t]
     L.ellp_flat_phase_free.argtypes = [C.POINTER(_FlatPhase)]
@@ -269,24 +271,57 @@ class _Solver:
         host_lib().ellp_solve(prob._h, self._KIND, self.max_iter,
                               C.byref(self._opts) if self._opts is not None else None, C.byref(r))
         try:
-            st, msg = r.status, r.err.decode()
-            iters = (r.iters_phase1, r.iters_phase2)
-            if st == _engine.OPTIMAL:
-                x = np.ctypeslib.as_array(r.x, shape=(r.nx,)).copy() if r.nx else np.zeros(0)
-                return SolverResult(SolverResult.Optimal, Solution(r.obj, x), iters=iters)
-            if st == _engine.INFEASIBLE:
-                return SolverResult(SolverResult.Infeasible, iters=iters)
-            if st == _engine.UNBOUNDED:
-                return SolverResult(SolverResult.Unbounded, iters=iters)
-            if st == _engine.MAXITER:
-                return SolverResult(SolverResult.MaxIter, obj=r.obj, iters=iters)
-            if st in (_engine.ERR_BAD_DIMS, _engine.ERR_SINGULAR):
-                raise EllPError(msg)
-            if st == _engine.ERR_DEVICE:
-                raise _engine.EllpHipError(st, msg)
-            raise RuntimeError(f"panic: {msg}")
+            return _to_result(r)
         finally:
             host_lib().ellp_result_free(C.byref(r))
+
+    def solve_batch(self, problems):
+        """solve() of every problem in `problems`, in lock step: the device loops of each phase of all problems the small
+        kernel takes (1 to 128 rows) run in one batched launch, one workgroup per problem; the others are solved one by
+        one.  Returns a list with one entry per problem: the SolverResult solve(p) returns, or, where solve(p) would
+        raise, the exception instance it would raise (returned, not raised).  Results are those of solve(p) to the bit."""
+        problems = list(problems)
+        n = len(problems)
+        if n == 0:
+            return []
+        handles = (C.c_void_p * n)(*[p._h for p in problems])
+        rs = (_Result * n)()
+        L = host_lib()
+        s = L.ellp_solve_batch(handles, n, self._KIND, self.max_iter,
+                               C.byref(self._opts) if self._opts is not None else None, rs)
+        if s == _engine.ERR_ARG:
+            raise ValueError("solve_batch: invalid arguments")
+        out = []
+        try:
+            for r in rs:
+                try:
+                    out.append(_to_result(r))
+                except Exception as e:  # noqa: BLE001 — the exception solve() would raise, handed back
+                    out.append(e)
+        finally:
+            for r in rs:
+                L.ellp_result_free(C.byref(r))
+        return out
+
+
+def _to_result(r):
+    """SolverResult from a filled ellp_result; raises what solve() raises for it"""
+    st, msg = r.status, r.err.decode()
+    iters = (r.iters_phase1, r.iters_phase2)
+    if st == _engine.OPTIMAL:
+        x = np.ctypeslib.as_array(r.x, shape=(r.nx,)).copy() if r.nx else np.zeros(0)
+        return SolverResult(SolverResult.Optimal, Solution(r.obj, x), iters=iters)
+    if st == _engine.INFEASIBLE:
+        return SolverResult(SolverResult.Infeasible, iters=iters)
+    if st == _engine.UNBOUNDED:
+        return SolverResult(SolverResult.Unbounded, iters=iters)
+    if st == _engine.MAXITER:
+        return SolverResult(SolverResult.MaxIter, obj=r.obj, iters=iters)
+    if st in (_engine.ERR_BAD_DIMS, _engine.ERR_SINGULAR):
+        raise EllPError(msg)
+    if st == _engine.ERR_DEVICE:
+        raise _engine.EllpHipError(st, msg)
+    raise RuntimeError(f"panic: {msg}")
 
 
 class PrimalSimplexSolver(_Solver):

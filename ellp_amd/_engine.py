@@ -82,6 +82,9 @@ def lib():
     L.ellp_primal_solve_with_initial.argtypes = _PROBLEM_ARGS + tail
     L.ellp_dual_solve_with_initial.restype = C.c_int
     L.ellp_dual_solve_with_initial.argtypes = _PROBLEM_ARGS + [C.c_void_p, C.c_void_p] + tail
+    L.ellp_batch_solve_with_initial.restype = C.c_int
+    L.ellp_batch_solve_with_initial.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p,
+                                                C.c_char_p, C.c_size_t]
     L.ellp_engine_create.restype = C.c_int
     L.ellp_engine_create.argtypes = ([C.c_int] + _PROBLEM_ARGS + [C.c_void_p, C.c_void_p] +
                                      [C.POINTER(Opts), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t])
@@ -272,6 +275,38 @@ def dual_solve_with_initial(fp, opts=None):
     s = lib().ellp_dual_solve_with_initial(*fp._args(), _p(fp.y), _p(fp.d), C.byref(o), C.byref(st),
                                            err, 512)
     return s, st, err.value.decode()
+
+
+class BatchItem(C.Structure):
+    """ellp_batch_item (include/ellp_hip.h)"""
+    _fields_ = [("m", C.c_int64), ("n", C.c_int64), ("n_c", C.c_int64), ("A", C.c_void_p), ("c", C.c_void_p),
+                ("b", C.c_void_p), ("bound_kind", C.c_void_p), ("lb", C.c_void_p), ("ub", C.c_void_p), ("x", C.c_void_p),
+                ("B_index", C.c_void_p), ("n_B", C.c_int64), ("N_index", C.c_void_p), ("N_bound", C.c_void_p),
+                ("n_N", C.c_int64), ("y", C.c_void_p), ("d", C.c_void_p), ("err", C.c_char * 256)]
+
+
+def batch_solve_with_initial(kind, flat_problems, opts=None):
+    """solve_with_initial of every FlatProblem in one batched call (ENGINE_PRIMAL or ENGINE_DUAL).  Returns one
+    (status, Stats, errmsg) per problem, as the single-call wrappers do, and mutates the problems in place.  Raises
+    EllpHipError if the call as a whole is refused (options, device)."""
+    fps = list(flat_problems)
+    n = len(fps)
+    items = (BatchItem * max(n, 1))()
+    for it, fp in zip(items, fps):
+        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
+        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
+        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
+        it.B_index, it.n_B = _p(fp.B), fp.nB
+        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(fp.Nb), fp.nN
+        it.y, it.d = _p(fp.y), _p(fp.d)
+    status = (C.c_int * max(n, 1))()
+    stats = (Stats * max(n, 1))()
+    o = opts or default_opts()
+    err = C.create_string_buffer(512)
+    s = lib().ellp_batch_solve_with_initial(kind, n, items, C.byref(o), status, stats, err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    return [(status[k], stats[k], items[k].err.decode()) for k in range(n)]
 
 
 class Engine:

@@ -2659,9 +2659,8 @@ __global__ __launch_bounds__(256) void k_gather_vec(const double *v, const int64
 // c . x for a primal engine (standard_form.rs:48), from the gathered costs: sum_i c_B[i] x[B_i] +
 // sum_j c_N[j] x[N_j]; one block, fixed reduction order.  Only for ellp_stats.obj (the loop never
 // needs it: the reference computes it outside the loop too, primal…:42-45).
-__global__ __launch_bounds__(1024) void k_primal_obj(const double *c_B, const double *c_N, const double *x,
-                                                    const int64_t *B_index, const int64_t *N_index, int64_t m,
-                                                    int64_t nN, DevState *st) {
+__device__ __forceinline__ void primal_obj(const double *c_B, const double *c_N, const double *x, const int64_t *B_index,
+                                           const int64_t *N_index, int64_t m, int64_t nN, DevState *st) {
     __shared__ double s_p[16];
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < m; i += 1024) acc = fma(c_B[i], x[B_index[i]], acc);
@@ -2677,6 +2676,11 @@ __global__ __launch_bounds__(1024) void k_primal_obj(const double *c_B, const do
         for (int w = 0; w < 16; ++w) t += s_p[w];
         st->obj = t;
     }
+}
+__global__ __launch_bounds__(1024) void k_primal_obj(const double *c_B, const double *c_N, const double *x,
+                                                    const int64_t *B_index, const int64_t *N_index, int64_t m,
+                                                    int64_t nN, DevState *st) {
+    primal_obj(c_B, c_N, x, B_index, N_index, m, nN, st);
 }
 
 // ---- DualPhase2::from(phase_1) on the device (dual_problem.rs:258-404), see ellp_engine_dual_rephase
@@ -4032,16 +4036,12 @@ static const void *small_kernel(int kind, int nt) {
 
 // n_explicit: columns of A the caller passes; columns n_explicit .. n-1 (m of them, or none) are the
 // artificial columns of primal phase 1 and are made on the device (build_phase1)
-static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c,
-                               const double *b, const uint8_t *bound_kind, const double *lb, const double *ub,
-                               const double *x, const int64_t *B_index, int64_t n_B, const int64_t *N_index,
-                               const uint8_t *N_bound, int64_t n_N, const double *y, const double *d,
-                               const ellp_opts *opts_in, ellp_engine **out, char *errbuf, size_t errlen,
-                               int64_t n_explicit, bool build_phase1) {
-    if (!out) return ELLP_ERR_ARG;
-    *out = nullptr;
-    if (errbuf && errlen) errbuf[0] = 0;
-    auto t0 = std::chrono::steady_clock::now();
+// The checks ellp_engine_create makes of one LP's arguments, before any HIP call (also those of every item of
+// ellp_batch_solve_with_initial)
+static ellp_status check_problem(int kind, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
+                                 const uint8_t *bound_kind, const double *lb, const double *ub, const double *x,
+                                 const int64_t *B_index, int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N,
+                                 const double *y, const double *d, char *errbuf, size_t errlen) {
     if (kind != ELLP_ENGINE_PRIMAL && kind != ELLP_ENGINE_DUAL) {
         set_err(errbuf, errlen, "unknown engine kind %d", kind);
         return ELLP_ERR_ARG;
@@ -4089,6 +4089,63 @@ static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_
             set_err(errbuf, errlen, "bound_kind[%lld] out of range", (long long)i);
             return ELLP_ERR_ARG;
         }
+    return ELLP_OPTIMAL;
+}
+
+// The device state a fresh engine starts from: running, no pivot yet, the objective of the starting point
+static DevState initial_state(int kind, int64_t m, int64_t n_c, int64_t n_N, const double *c, const double *b,
+                              const uint8_t *bound_kind, const double *lb, const double *ub, const double *x, const double *y,
+                              const double *d) {
+    DevState init;
+    memset(&init, 0, sizeof(init));
+    init.status = ST_RUNNING;
+    init.r = -1;
+    init.lr = -1;
+    init.pp_hi = n_N;
+    init.dp_seq = ~0ull;
+    init.dp_applied = ~0ull;
+    if (kind == ELLP_ENGINE_DUAL) {
+        init.obj = host_dual_obj(m, n_c, b, bound_kind, lb, ub, y, d);  // dual…:184
+    } else {
+        double o = 0.0;  // standard_form.rs:48 `c.dot(x)`
+        for (int64_t i = 0; i < n_c; ++i) o += c[i] * x[i];
+        init.obj = o;
+    }
+    return init;
+}
+
+// dual: the initial dual feasibility assertion (dual…:139-151), on the host
+static bool dual_start_feasible(int64_t n_N, const int64_t *N_index, const uint8_t *N_bound, const double *d, double eps,
+                                char *errbuf, size_t errlen) {
+    for (int64_t j = 0; j < n_N; ++j) {
+        const double di = d[N_index[j]];
+        bool infeasible;
+        if (N_bound[j] == ELLP_NB_LOWER) infeasible = di < -eps;
+        else if (N_bound[j] == ELLP_NB_UPPER) infeasible = di > eps;
+        else infeasible = std::fabs(di) > eps;
+        if (infeasible) {
+            set_err(errbuf, errlen, "initial point of dual phase 2 is dual infeasible");
+            return false;
+        }
+    }
+    return true;
+}
+
+static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c,
+                               const double *b, const uint8_t *bound_kind, const double *lb, const double *ub,
+                               const double *x, const int64_t *B_index, int64_t n_B, const int64_t *N_index,
+                               const uint8_t *N_bound, int64_t n_N, const double *y, const double *d,
+                               const ellp_opts *opts_in, ellp_engine **out, char *errbuf, size_t errlen,
+                               int64_t n_explicit, bool build_phase1) {
+    if (!out) return ELLP_ERR_ARG;
+    *out = nullptr;
+    if (errbuf && errlen) errbuf[0] = 0;
+    auto t0 = std::chrono::steady_clock::now();
+    {
+        const ellp_status cs = check_problem(kind, m, n, n_c, A, c, b, bound_kind, lb, ub, x, B_index, n_B, N_index, N_bound, n_N,
+                                             y, d, errbuf, errlen);
+        if (cs != ELLP_OPTIMAL) return cs;
+    }
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -4301,14 +4358,7 @@ static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_
                                e->N_index, e->c_N, n_N);
         }
         UCHK(hipGetLastError());
-        DevState init;
-        memset(&init, 0, sizeof(init));
-        init.status = ST_RUNNING;
-        init.r = -1;
-        init.lr = -1;
-        init.pp_hi = n_N;
-        init.dp_seq = ~0ull;
-        init.dp_applied = ~0ull;
+        DevState init = initial_state(kind, m, n_c, n_N, c, b, bound_kind, lb, ub, x, y, d);
         if (kind == ELLP_ENGINE_PRIMAL && e->opts.partial_segments > 1 && n_N > 0) {
             // partial pricing (f4): segments of ceil(|N| / P) positions, never more segments than positions
             int P = e->opts.partial_segments;
@@ -4327,11 +4377,6 @@ static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_
             UCHK(hipMemsetAsync(e->y, 0, sizeof(double) * (size_t)ld, e->stream));
             UCHK(hipMemcpyAsync(e->y, y, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, e->stream));
             UCHK(hipMemcpyAsync(e->dd, d, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-            init.obj = host_dual_obj(m, n_c, b, bound_kind, lb, ub, y, d);  // dual…:184
-        } else {
-            double o = 0.0;  // standard_form.rs:48 `c.dot(x)`
-            for (int64_t i = 0; i < n_c; ++i) o += c[i] * x[i];
-            init.obj = o;
         }
         *e->h_st = init;
         UCHK(hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream));
@@ -4357,19 +4402,9 @@ static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_
                            e->nN, e->st);
     }
     // dual: initial dual feasibility assertion (dual…:139-151) — host side, data is in hand
-    if (kind == ELLP_ENGINE_DUAL) {
-        for (int64_t j = 0; j < n_N; ++j) {
-            const double di = d[N_index[j]];
-            bool infeasible;
-            if (N_bound[j] == ELLP_NB_LOWER) infeasible = di < -e->eps;
-            else if (N_bound[j] == ELLP_NB_UPPER) infeasible = di > e->eps;
-            else infeasible = std::fabs(di) > e->eps;
-            if (infeasible) {
-                set_err(errbuf, errlen, "initial point of dual phase 2 is dual infeasible");
-                ellp_engine_destroy(e);
-                return ELLP_ERR_PANIC;
-            }
-        }
+    if (kind == ELLP_ENGINE_DUAL && !dual_start_feasible(n_N, N_index, N_bound, d, e->eps, errbuf, errlen)) {
+        ellp_engine_destroy(e);
+        return ELLP_ERR_PANIC;
     }
     e->dual_maxviol = (kind == ELLP_ENGINE_DUAL && (e->opts.flags & ELLP_FLAG_DUAL_MAX_VIOLATION)) ? 1 : 0;
     e->dual_bflip = (kind == ELLP_ENGINE_DUAL && (e->opts.flags & ELLP_FLAG_DUAL_BOUND_FLIPPING)) ? 1 : 0;
@@ -6619,3 +6654,5 @@ ellp_status ellp_dual_solve_with_initial(int64_t m, int64_t n, int64_t n_c, cons
 }
 
 }  // extern "C"
+
+#include "ellp_batch.inc"

@@ -438,8 +438,10 @@ inline int small_threads(int64_t m, int64_t nN) {
         t_prev = _t;                                        \
     }
 
+// The loop of k_small for the LP of `a`, run by the whole workgroup.  A function of its arguments alone (no blockIdx), so
+// that k_small_batch can run one LP per workgroup with the same code.
 template <int KIND, int NT>
-__global__ __launch_bounds__(NT) void k_small(SmallArgs a) {
+__device__ __forceinline__ void small_loop(const SmallArgs &a) {
     unsigned long long t_prev = a.stamps ? wall_clock64() : 0ull;
     unsigned long long c_prev = a.stamps ? clock64() : 0ull;
     constexpr int NW = NT / 64;
@@ -929,4 +931,25 @@ __global__ __launch_bounds__(NT) void k_small(SmallArgs a) {
         __syncthreads();  // thread 0 clears the flag at the top of the next iteration
         if (stop) return;
     }
+}
+
+template <int KIND, int NT>
+__global__ __launch_bounds__(NT) void k_small(SmallArgs a) {
+    small_loop<KIND, NT>(a);
+}
+
+// Batched solves (ellp_batch_solve_with_initial): workgroup b runs the LP of items[b] — its own arrays, DevState, rbuf / kbuf /
+// flist and its own dynamic LDS — exactly as k_small runs it alone.  An item that ends (or has ended in an earlier launch)
+// retires its workgroup only.  The address of the item is uniform and the items are never written during the launch, so
+// the copy below comes in with scalar loads, once, ahead of the loop.
+template <int KIND, int NT>
+__global__ __launch_bounds__(NT) void k_small_batch(const SmallArgs *__restrict__ items) {
+    const SmallArgs a = items[blockIdx.x];
+    small_loop<KIND, NT>(a);
+}
+
+// c . x of every LP of a batch (k_primal_obj's sum, one workgroup per item): the objective a primal single call reports
+__global__ __launch_bounds__(1024) void k_primal_obj_batch(const SmallArgs *__restrict__ items) {
+    const SmallArgs a = items[blockIdx.x];
+    primal_obj(a.c_B, a.c_N, a.x, a.B_index, a.N_index, a.m, a.nN, a.st);
 }

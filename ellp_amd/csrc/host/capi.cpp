@@ -85,8 +85,10 @@ ellp_problem *ellp_parse_mps(const char *text, char *errbuf, size_t errlen) {
     }
 }
 
-int ellp_solve(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, ellp_result *out) {
-    std::memset(out, 0, sizeof(*out));
+}  // extern "C"
+
+namespace {
+ellp::EngineOptions engine_options(const ellp_opts *opts) {
     ellp::EngineOptions eo;
     if (opts) {
         eo.device = opts->device;
@@ -97,12 +99,14 @@ int ellp_solve(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_
         eo.partial_segments = opts->partial_segments;
         eo.flags = opts->flags;
     }
-    const std::optional<std::uint64_t> mi =
-        max_iter == ELLP_MAX_ITER_NONE ? std::nullopt : std::optional<std::uint64_t>(max_iter);
+    return eo;
+}
+// *out from what `run` returns or throws
+template <class F>
+int fill_result(ellp_result *out, F &&run) {
+    std::memset(out, 0, sizeof(*out));
     try {
-        ellp::SolverResult r = solver == ELLP_SOLVER_PRIMAL
-                                   ? ellp::PrimalSimplexSolver(mi).with_engine(eo).solve(p->prob)
-                                   : ellp::DualSimplexSolver(mi).with_engine(eo).solve(p->prob);
+        ellp::SolverResult r = run();
         out->iters_phase1 = r.iters_phase1;
         out->iters_phase2 = r.iters_phase2;
         switch (r.kind) {
@@ -133,6 +137,47 @@ int ellp_solve(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_
         put(out->err, sizeof(out->err), e.what());
     }
     return out->status;
+}
+}  // namespace
+
+extern "C" {
+
+int ellp_solve(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, ellp_result *out) {
+    const ellp::EngineOptions eo = engine_options(opts);
+    const std::optional<std::uint64_t> mi =
+        max_iter == ELLP_MAX_ITER_NONE ? std::nullopt : std::optional<std::uint64_t>(max_iter);
+    return fill_result(out, [&] {
+        return solver == ELLP_SOLVER_PRIMAL ? ellp::PrimalSimplexSolver(mi).with_engine(eo).solve(p->prob)
+                                            : ellp::DualSimplexSolver(mi).with_engine(eo).solve(p->prob);
+    });
+}
+
+int ellp_solve_batch(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+                     ellp_result *out) {
+    if (count < 0 || (count > 0 && (!probs || !out)) || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL))
+        return ELLP_ERR_ARG;
+    for (int64_t k = 0; k < count; ++k)
+        if (!probs[k]) return ELLP_ERR_ARG;
+    std::vector<ellp::Problem> ps;
+    ps.reserve(static_cast<size_t>(count));
+    for (int64_t k = 0; k < count; ++k) ps.push_back(probs[k]->prob);
+    std::vector<ellp::BatchOutcome> res;
+    try {
+        res = ellp::solve_batch(solver, std::move(ps), max_iter, engine_options(opts));
+    } catch (const std::exception &e) {  // host memory: the batch as a whole
+        for (int64_t k = 0; k < count; ++k) {
+            std::memset(&out[k], 0, sizeof(out[k]));
+            out[k].status = ELLP_ERR_DEVICE;
+            put(out[k].err, sizeof(out[k].err), e.what());
+        }
+        return ELLP_ERR_DEVICE;
+    }
+    for (int64_t k = 0; k < count; ++k)
+        fill_result(&out[k], [&] {
+            if (res[k].error) std::rethrow_exception(res[k].error);
+            return std::move(res[k].result);
+        });
+    return ELLP_OPTIMAL;
 }
 
 static void fill_flat(ellp_flat_phase *o, const ellp::StandardForm &sf, const ellp::Point &pt,

@@ -11,6 +11,7 @@
 #pragma once
 
 #include <cstdint>
+#include <exception>
 #include <limits>
 #include <optional>
 #include <stdexcept>
@@ -222,6 +223,15 @@ private:
     std::uint64_t max_iter_;
     EngineOptions engine_;
 };
+
+// Many problems solved by one solver (solver: ELLP_SOLVER_PRIMAL / ELLP_SOLVER_DUAL) in lock step, the device loops of a
+// phase in one batched call (ellp_batch_solve_with_initial).  Outcome k is what solve(probs[k]) returns, or the
+// exception it throws (error set).
+struct BatchOutcome {
+    SolverResult result;
+    std::exception_ptr error;
+};
+std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng);
 
 // src/parse_mps.rs:11-66.  Variables/rows are taken in file order (the reference iterates
 // HashMaps, so its order is unspecified).

@@ -5,6 +5,8 @@
 //                           one call through the C ABI into the HIP engine.  No CPU loop exists
 //                           here: if the engine cannot run, the error is raised.
 #include <cmath>
+#include <cstring>
+#include <exception>
 
 #include "ellp.h"
 
@@ -350,6 +352,348 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
         return res;
     }
     return res;
+}
+
+}  // namespace ellp
+
+// ---- solve_batch: solve() of many problems in lock step, every device loop of every phase in one batched call
+// (ellp_batch_solve_with_initial) for the problems the small kernel takes.  Each problem takes the steps solve() takes
+// for it — the host set-up, the checks between the phases, the hand-off — and the device loops compute what the single
+// calls compute, so every outcome is solve()'s.  Problems the batch does not take run through solve() itself.
+namespace ellp {
+
+namespace {
+
+// one solve_with_initial of a batch: the arrays of the single call and its outcome
+struct Seam {
+    const StandardForm *sf = nullptr;
+    Point *pt = nullptr;
+    DualFeasiblePoint *dp = nullptr;  // dual
+    Flat f;
+    ellp_status status = ELLP_ERR_ARG;
+    ellp_stats stats{};
+    std::string err;
+};
+
+// false: the call as a whole was refused (options, device) — the caller runs those problems on the single path
+bool run_seams(int kind, std::vector<Seam *> &seams, std::uint64_t max_iter, const EngineOptions &eng) {
+    if (seams.empty()) return true;
+    std::vector<ellp_batch_item> items(seams.size());
+    for (size_t k = 0; k < seams.size(); ++k) {
+        Seam &s = *seams[k];
+        s.f = flatten(*s.sf, *s.pt);
+        ellp_batch_item &it = items[k];
+        std::memset(&it, 0, sizeof(it));
+        it.m = static_cast<std::int64_t>(s.sf->rows());
+        it.n = static_cast<std::int64_t>(s.sf->cols());
+        it.n_c = static_cast<std::int64_t>(s.sf->bounds.size());
+        it.A = s.sf->A.a.data();
+        it.c = s.sf->c.data();
+        it.b = s.sf->b.data();
+        it.bound_kind = s.f.kind.data();
+        it.lb = s.f.lb.data();
+        it.ub = s.f.ub.data();
+        it.x = s.pt->x.data();
+        it.B_index = s.f.B.data();
+        it.n_B = static_cast<std::int64_t>(s.f.B.size());
+        it.N_index = s.f.N.data();
+        it.N_bound = s.f.Nb.data();
+        it.n_N = static_cast<std::int64_t>(s.f.N.size());
+        if (s.dp) {
+            it.y = s.dp->y.data();
+            it.d = s.dp->d.data();
+        }
+    }
+    const ellp_opts o = make_opts(max_iter, eng);
+    std::vector<ellp_status> st(seams.size());
+    std::vector<ellp_stats> stats(seams.size());
+    char err[512] = {0};
+    if (ellp_batch_solve_with_initial(kind, static_cast<std::int64_t>(items.size()), items.data(), &o, st.data(), stats.data(), err,
+                                      sizeof(err)) != ELLP_OPTIMAL)
+        return false;
+    for (size_t k = 0; k < seams.size(); ++k) {
+        Seam &s = *seams[k];
+        s.status = st[k];
+        s.stats = stats[k];
+        s.err = items[k].err;
+        unflatten(s.f, *s.pt);
+    }
+    return true;
+}
+
+// the slots of a batch that have not ended yet
+struct Slot {
+    size_t out;  // index into the outcomes
+    bool done = false;
+};
+
+template <class F>
+void settle(BatchOutcome &o, Slot &slot, F &&f) {
+    try {
+        f();
+    } catch (...) {
+        o.error = std::current_exception();
+        slot.done = true;
+    }
+}
+
+bool batchable(const StandardForm &sf, size_t n_N) { return sf.rows() > 0 && sf.rows() <= 128 && n_N > 0; }
+
+void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which, std::uint64_t max_iter, const EngineOptions &eng,
+                  std::vector<BatchOutcome> &out) {
+    const PrimalSimplexSolver single = PrimalSimplexSolver(max_iter).with_engine(eng);
+    struct Item {
+        Slot slot;
+        std::optional<PrimalPhase1> p1;
+        std::optional<PrimalPhase2> p2;
+        Seam seam;
+    };
+    std::vector<Item> items(which.size());
+    auto fallback = [&](Item &it) {
+        settle(out[it.slot.out], it.slot, [&] { out[it.slot.out].result = single.solve(probs[it.slot.out]); });
+        it.slot.done = true;
+    };
+    // phase 1 on the host
+    std::vector<Seam *> seams;
+    for (size_t k = 0; k < which.size(); ++k) {
+        Item &it = items[k];
+        it.slot.out = which[k];
+        settle(out[it.slot.out], it.slot, [&] {
+            auto p1 = PrimalPhase1::from_problem(probs[which[k]]);
+            if (!p1) {
+                out[it.slot.out].result.kind = SolverResult::Infeasible;
+                it.slot.done = true;
+                return;
+            }
+            it.p1 = std::move(*p1);
+        });
+        if (it.slot.done) continue;
+        if (!batchable(it.p1->std_form, it.p1->point.N.size())) {
+            fallback(it);
+            continue;
+        }
+        it.seam.sf = &it.p1->std_form;
+        it.seam.pt = &it.p1->point;
+        seams.push_back(&it.seam);
+    }
+    if (!run_seams(ELLP_ENGINE_PRIMAL, seams, max_iter, eng)) {
+        for (Item &it : items)
+            if (!it.slot.done) fallback(it);
+        return;
+    }
+    // the checks after phase 1 (solve(), primal…:42-55), phase 2 on the host
+    seams.clear();
+    for (Item &it : items) {
+        if (it.slot.done) continue;
+        if (it.seam.status == ELLP_ERR_ARG) {  // not taken by the batch kernel (LDS)
+            fallback(it);
+            continue;
+        }
+        SolverResult &res = out[it.slot.out].result;
+        settle(out[it.slot.out], it.slot, [&] {
+            const SolutionStatus s1 = to_status(it.seam.status, it.seam.err.c_str());
+            res.iters_phase1 = it.seam.stats.iters;
+            switch (s1) {
+            case SolutionStatus::Optimal: {
+                const double obj = it.p1->obj();
+                if (!(obj > -EPS)) throw EllPPanic("assertion failed: obj > -EPS");
+                if (!(obj < EPS)) {
+                    res.kind = SolverResult::Infeasible;
+                    it.slot.done = true;
+                    return;
+                }
+                break;
+            }
+            case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; it.slot.done = true; return;
+            case SolutionStatus::Unbounded: throw EllPPanic("primal phase 1 should never be unbounded");
+            case SolutionStatus::MaxIter:
+                res.kind = SolverResult::MaxIter;
+                res.max_iter_obj = std::numeric_limits<double>::infinity();
+                it.slot.done = true;
+                return;
+            }
+            it.p2 = PrimalPhase2::from_phase1(std::move(*it.p1));
+            it.p1.reset();
+        });
+        if (it.slot.done) continue;
+        it.seam = Seam{};
+        it.seam.sf = &it.p2->std_form;
+        it.seam.pt = &it.p2->point;
+        seams.push_back(&it.seam);
+    }
+    if (!run_seams(ELLP_ENGINE_PRIMAL, seams, max_iter, eng)) {
+        for (Item &it : items)
+            if (!it.slot.done) fallback(it);
+        return;
+    }
+    for (Item &it : items) {
+        if (it.slot.done) continue;
+        if (it.seam.status == ELLP_ERR_ARG) {
+            fallback(it);
+            continue;
+        }
+        SolverResult &res = out[it.slot.out].result;
+        settle(out[it.slot.out], it.slot, [&] {
+            const SolutionStatus s2 = to_status(it.seam.status, it.seam.err.c_str());
+            res.iters_phase2 = it.seam.stats.iters;
+            switch (s2) {
+            case SolutionStatus::Optimal:
+                res.kind = SolverResult::Optimal;
+                res.solution = Solution{std::move(it.p2->std_form), std::move(it.p2->point)};
+                break;
+            case SolutionStatus::Infeasible: throw EllPPanic("primal phase 2 should never be infeasible");
+            case SolutionStatus::Unbounded: res.kind = SolverResult::Unbounded; break;
+            case SolutionStatus::MaxIter:
+                res.kind = SolverResult::MaxIter;
+                res.max_iter_obj = it.p2->obj();
+                break;
+            }
+        });
+        it.slot.done = true;
+    }
+}
+
+void dual_batch(std::vector<Problem> &probs, std::uint64_t max_iter, const EngineOptions &eng, std::vector<BatchOutcome> &out) {
+    const DualSimplexSolver single = DualSimplexSolver(max_iter).with_engine(eng);
+    const char *hostpt = std::getenv("ELLP_HOST_DUAL_POINT");
+    const bool defer = !(hostpt && hostpt[0] == '1');
+    struct Item {
+        Slot slot;
+        std::optional<DualPhase1> p1;
+        std::optional<DualPhase2> p2;
+        Seam seam;
+    };
+    std::vector<Item> items(probs.size());
+    auto fallback = [&](Item &it) {
+        settle(out[it.slot.out], it.slot, [&] { out[it.slot.out].result = single.solve(probs[it.slot.out]); });
+        it.slot.done = true;
+    };
+    std::vector<Seam *> seams;
+    for (size_t k = 0; k < probs.size(); ++k) {
+        Item &it = items[k];
+        it.slot.out = k;
+        settle(out[k], it.slot, [&] {
+            auto p1 = DualPhase1::from_problem(probs[k], defer);
+            if (!p1) {
+                out[k].result.kind = SolverResult::Infeasible;
+                it.slot.done = true;
+                return;
+            }
+            it.p1 = std::move(*p1);
+        });
+        if (it.slot.done) continue;
+        if (it.p1->point_deferred || !batchable(it.p1->std_form, it.p1->point.point.N.size())) {
+            fallback(it);
+            continue;
+        }
+        it.seam.sf = &it.p1->std_form;
+        it.seam.pt = &it.p1->point.point;
+        it.seam.dp = &it.p1->point;
+        seams.push_back(&it.seam);
+    }
+    if (!run_seams(ELLP_ENGINE_DUAL, seams, max_iter, eng)) {
+        for (Item &it : items)
+            if (!it.slot.done) fallback(it);
+        return;
+    }
+    // the checks after phase 1 (dual…:44-77); the dual-infeasible ones are classified by the primal solver, in one batch
+    std::vector<size_t> classify;
+    seams.clear();
+    for (Item &it : items) {
+        if (it.slot.done) continue;
+        if (it.seam.status == ELLP_ERR_ARG) {
+            fallback(it);
+            continue;
+        }
+        SolverResult &res = out[it.slot.out].result;
+        settle(out[it.slot.out], it.slot, [&] {
+            const SolutionStatus s1 = to_status(it.seam.status, it.seam.err.c_str());
+            res.iters_phase1 = it.seam.stats.iters;
+            switch (s1) {
+            case SolutionStatus::Optimal: {
+                const double obj = it.p1->obj();
+                if (!(obj < EPS)) throw EllPPanic("assertion failed: obj < EPS");
+                if (!(obj > -EPS)) {
+                    classify.push_back(it.slot.out);
+                    it.slot.done = true;
+                    return;
+                }
+                break;
+            }
+            case SolutionStatus::Infeasible: throw EllPPanic("dual phase 1 should never be infeasible");
+            case SolutionStatus::Unbounded: throw EllPPanic("dual phase 1 should never be unbounded");
+            case SolutionStatus::MaxIter:
+                res.kind = SolverResult::MaxIter;
+                res.max_iter_obj = std::numeric_limits<double>::infinity();
+                it.slot.done = true;
+                return;
+            }
+            it.p2 = DualPhase2::from_phase1(std::move(*it.p1));
+            it.p1.reset();
+        });
+        if (it.slot.done) continue;
+        it.seam = Seam{};
+        it.seam.sf = &it.p2->std_form;
+        it.seam.pt = &it.p2->point.point;
+        it.seam.dp = &it.p2->point;
+        seams.push_back(&it.seam);
+    }
+    if (!classify.empty()) {
+        // PrimalSimplexSolver::default() (max_iter 1000) with the same engine options, as solve() does; its result replaces
+        // the dual's
+        for (size_t k : classify) out[k].result = SolverResult{};
+        primal_batch(probs, classify, 1000, eng, out);
+        for (size_t k : classify)
+            if (!out[k].error && out[k].result.kind == SolverResult::Optimal) {
+                out[k].result = SolverResult{};
+                try {
+                    throw EllPPanic("assertion failed: matches!(result, Infeasible | Unbounded | MaxIter)");
+                } catch (...) {
+                    out[k].error = std::current_exception();
+                }
+            }
+    }
+    const bool ran = run_seams(ELLP_ENGINE_DUAL, seams, max_iter, eng);
+    for (Item &it : items) {
+        if (it.slot.done) continue;
+        SolverResult &res = out[it.slot.out].result;
+        settle(out[it.slot.out], it.slot, [&] {
+            SolutionStatus s2;
+            if (!ran || it.seam.status == ELLP_ERR_ARG) {
+                s2 = single.solve_with_initial(it.p2->std_form, it.p2->point, &res.iters_phase2);  // what solve() calls here
+            } else {
+                s2 = to_status(it.seam.status, it.seam.err.c_str());
+                res.iters_phase2 = it.seam.stats.iters;
+            }
+            switch (s2) {
+            case SolutionStatus::Optimal:
+                res.kind = SolverResult::Optimal;
+                res.solution = Solution{std::move(it.p2->std_form), std::move(it.p2->point.point)};
+                break;
+            case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; break;
+            case SolutionStatus::Unbounded: throw EllPPanic("dual phase 2 should never return unbounded");
+            case SolutionStatus::MaxIter:
+                res.kind = SolverResult::MaxIter;
+                res.max_iter_obj = it.p2->obj();
+                break;
+            }
+        });
+        it.slot.done = true;
+    }
+}
+
+}  // namespace
+
+std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng) {
+    std::vector<BatchOutcome> out(probs.size());
+    if (solver == ELLP_ENGINE_PRIMAL) {
+        std::vector<size_t> all(probs.size());
+        for (size_t k = 0; k < all.size(); ++k) all[k] = k;
+        primal_batch(probs, all, max_iter, eng, out);
+    } else {
+        dual_batch(probs, max_iter, eng, out);
+    }
+    return out;
 }
 
 }  // namespace ellp

@@ -188,6 +188,40 @@ ellp_status ellp_dual_solve_with_initial(
     const ellp_opts *opts, ellp_stats *stats, char *errbuf, size_t errbuf_len);
 
 /*
+ * Batched solve_with_initial of many small LPs (kind: ELLP_ENGINE_PRIMAL or ELLP_ENGINE_DUAL), one workgroup per LP in
+ * one launch of the LU-per-iteration kernel of ellp_small.inc.  Every item ends exactly as the single call
+ * (ellp_primal_solve_with_initial / ellp_dual_solve_with_initial with the same opts) ends it: status, iteration counts,
+ * index sets and the bits of x (y and d for the dual).  An item's arrays are the single call's arguments; x, B_index,
+ * N_index, N_bound (y, d) are updated in place.
+ *
+ * Returns the status of the call as a whole: ELLP_ERR_ARG (count < 0, items or status_out NULL, an unknown kind, options the
+ * batch refuses: pipeline other than 0 / 3, partial_segments > 1, ELLP_FLAG_PRIMAL_STEEPEST_EDGE, trace_len > 0, profile,
+ * and the options that make a single call take the explicit-inverse engine instead: refactor_period > 0 or btran_mode != 0
+ * on pipeline 0 without ELLP_FLAG_DUAL_BOUND_FLIPPING), ELLP_ERR_DEVICE, or ELLP_OPTIMAL.  These checks and the
+ * per-item ones run before any HIP call.  Per item: status_out[i], stats_out[i] (iters, pivots, bound_flips, refactors,
+ * obj; may be NULL) and items[i].err.  An item the kernel cannot take (m == 0, m > 128, LDS) gets ELLP_ERR_ARG.
+ * Of opts.flags only ELLP_FLAG_DUAL_MAX_VIOLATION and ELLP_FLAG_DUAL_BOUND_FLIPPING take effect; opts.max_iter holds per item.
+ */
+typedef struct ellp_batch_item {
+    int64_t m, n, n_c;
+    const double *A, *c, *b;
+    const uint8_t *bound_kind;
+    const double *lb, *ub;
+    double *x;
+    int64_t *B_index;
+    int64_t n_B;
+    int64_t *N_index;
+    uint8_t *N_bound;
+    int64_t n_N;
+    double *y, *d;  /* dual only */
+    char err[256];  /* out: the item's message */
+} ellp_batch_item;
+
+ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, ellp_batch_item *items, const ellp_opts *opts,
+                                          ellp_status *status_out, ellp_stats *stats_out, char *errbuf,
+                                          size_t errbuf_len);
+
+/*
  * Resident form of the same path: the tableau stays in HBM between calls, so a caller
  * (bench.py, a phase-1 -> phase-2 hand-off, a windowed parity test) can run the loop in
  * slices without re-uploading.  create = unpack + gather (primal…:99-155); run = the loop for

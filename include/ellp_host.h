@@ -55,6 +55,13 @@ typedef struct ellp_result {
 int ellp_solve(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, ellp_result *out);
 void ellp_result_free(ellp_result *r);
 
+/* solve() of many problems by one solver in lock step: every phase's device loops of the problems the small kernel
+ * takes (1 to 128 rows, with nonbasic columns) run in one batched ellp_batch_solve_with_initial; the rest go through
+ * ellp_solve.  out[k] is exactly what ellp_solve(probs[k], ...) fills in (ellp_result_free each).  Returns ELLP_ERR_ARG
+ * (count < 0, a NULL pointer, an unknown solver), ELLP_ERR_DEVICE (host memory; every out[k] says so) or 0. */
+int ellp_solve_batch(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+                     ellp_result *out);
+
 /* Test/diagnostic tap: the flattened phase-1 problem (exactly the arrays that solve() hands to
  * ellp_*_solve_with_initial) so the host setup can be checked without a GPU.  All arrays are
  * owned by the struct (ellp_flat_phase_free).  Returns 0, 1 if the setup already proves
