@@ -1,16 +1,23 @@
-// ellp_batch.inc — ellp_batch_solve_with_initial: many small LPs (m <= 128), one workgroup of k_small_batch per LP.
+// ellp_batch.inc — ellp_batch_solve_with_initial: many LPs of up to 1,024 rows, one workgroup per LP: k_small_batch for the
+// items a single call runs on k_small (m <= 128), k_mid_batch for those it runs on k_mid for the whole solve.
 //
 // Every item goes through the steps a single call (solve_once on the small path) takes, with the same code where there is
-// code to share: check_problem, initial_state and dual_start_feasible of ellp_engine_create, small_threads for the workgroup
-// size, the loop of k_small (small_loop) for the iterations, k_primal_obj's sum for the objective.  What is batched is the
-// traffic around it: one pinned staging buffer and one device slab hold every item; the host gathers A_B / A_N / c_B / c_N
-// (copies, so exact) into the staging buffer, which goes up in one copy; one launch per workgroup size (64 / 128 / 256) runs
-// every item of that size; the states and outputs come back in one copy.  An item that the cap of a launch (16,384 loop
-// bodies, ELLP_BATCH_LAUNCH_ITERS lowers it) left running is launched again from its device state, as run_small does.
+// code to share: check_problem, exact_loop, initial_state and dual_start_feasible of ellp_engine_create, small_threads /
+// mid_threads for the workgroup size, the loops of k_small (small_loop) and k_mid (mid_loop) for the iterations, k_primal_obj's
+// sum for the objective.  What is batched is the traffic around it: one pinned staging buffer and one device slab hold every
+// item of a chunk; the host gathers A_B / A_N / c_B / c_N (copies, so exact) into the staging buffer, which goes up in one
+// copy; one launch per kernel and workgroup size (64 / 128 / 256 small, 256 / 512 / 1024 mid) runs every item of that size;
+// the states and outputs come back in one copy.  An item that the cap of a launch (16,384 loop bodies on k_small, 4,096 on
+// k_mid, as run_small; ELLP_BATCH_LAUNCH_ITERS lowers both) left running is launched again from its device state.  Before
+// every round one k_mid_transpose_batch launch makes the row-major copy A_Nt of every mid item, as launch_mid does.
+//
+// Chunks: the items are taken in consecutive chunks whose slab stays within a budget (2 GiB; ELLP_BATCH_MAX_BYTES lowers it)
+// and at most 65,535 items; a chunk is a batch of its own, so chunking changes no item's bits.
 //
 // Layout of the slab: [DevState x runnable items][outputs of each item: x, B_index, N_index, Nb (y, d)] | [inputs and
-// scratch of each item: A_B, A_N, c_B, c_N, lb, ub, kind, rbuf, kbuf (flist)][SmallArgs of all items][SmallArgs of the
-// items of the current launch round].  Everything left of '|' is the one read-back.
+// scratch of each item: A_B, A_N, c_B, c_N, lb, ub, kind, rbuf, kbuf (flist)][SmallArgs of all items][MidArgs of the mid
+// items][SmallArgs, MidArgs of the items of the current launch round] | [device-only factors of each mid item: LUa, Ut,
+// A_Nt].  Everything left of the first '|' is the one read-back; everything left of the second is the staging buffer.
 //
 // Included at the end of ellp_engine.hip (outside its anonymous namespace and extern "C" block).
 
@@ -80,14 +87,17 @@ const void *small_batch_kernel(int kind, int nt) {
     return reinterpret_cast<const void *>(&k_small_batch<1, 256>);
 }
 
-// byte offsets of one runnable item's arrays in the slab
+// one runnable item: its kernel, its share of the slab and the byte offsets of its arrays in its chunk's slab
 struct BatchPlan {
     int64_t item;  // index into the caller's items
-    int64_t ld, nNa;
+    int64_t ld, nNa, ldn;
     size_t lds;
     int nt;
+    bool mid;                                                                // k_mid_batch (else k_small_batch)
     size_t o_x, o_B, o_N, o_Nb, o_y, o_d;                                     // outputs
     size_t o_AB, o_AN, o_cB, o_cN, o_lb, o_ub, o_kind, o_rbuf, o_kbuf, o_fl;  // inputs and scratch
+    size_t o_LUa, o_Ut, o_ANt;                                               // device-only factors (mid)
+    size_t bytes;                                                            // the item's share of the slab (batch_layout)
     uint64_t done = 0;                                                       // loop bodies run so far
 };
 
@@ -102,87 +112,45 @@ struct BatchCleanup {
     }
 };
 
-}  // namespace
+size_t batch_round16(size_t b) { return (b + 15) / 16 * 16; }
 
-extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, ellp_batch_item *items, const ellp_opts *opts_in,
-                                                     ellp_status *status_out, ellp_stats *stats_out, char *errbuf,
-                                                     size_t errlen) {
-    if (errbuf && errlen) errbuf[0] = 0;
-    if (count < 0 || (count > 0 && (!items || !status_out))) {
-        set_err(errbuf, errlen, "count < 0, or items / status_out NULL");
-        return ELLP_ERR_ARG;
-    }
-    if (kind != ELLP_ENGINE_PRIMAL && kind != ELLP_ENGINE_DUAL) {
-        set_err(errbuf, errlen, "unknown engine kind %d", kind);
-        return ELLP_ERR_ARG;
-    }
-    ellp_opts opts;
-    ellp_default_opts(&opts);
-    if (opts_in) opts = *opts_in;
-    const bool bflip = kind == ELLP_ENGINE_DUAL && (opts.flags & ELLP_FLAG_DUAL_BOUND_FLIPPING);
-    const bool maxviol = kind == ELLP_ENGINE_DUAL && (opts.flags & ELLP_FLAG_DUAL_MAX_VIOLATION);
-    if (opts.pipeline != 0 && opts.pipeline != 3) {
-        set_err(errbuf, errlen, "batch: pipeline %d; the batch runs the LU-per-iteration kernel (pipeline 0 or 3)", opts.pipeline);
-        return ELLP_ERR_ARG;
-    }
-    if (opts.partial_segments > 1 || (opts.flags & ELLP_FLAG_PRIMAL_STEEPEST_EDGE) || opts.trace_len > 0 || opts.profile) {
-        set_err(errbuf, errlen, "batch: partial pricing, steepest edge, traces and profiling are not available in a batch");
-        return ELLP_ERR_ARG;
-    }
-    if (opts.pipeline == 0 && !bflip && (opts.refactor_period > 0 || opts.btran_mode != 0)) {
-        set_err(errbuf, errlen, "batch: refactor_period / btran_mode select the explicit-inverse engine, which a batch does not run");
-        return ELLP_ERR_ARG;
-    }
-    const double eps = opts.eps > 0.0 ? opts.eps : 1e-10;
-    const uint64_t max_iter = opts.max_iter;
+// Per-chunk rounding of the four argument arrays, at most (the chunk budget allows for it)
+constexpr size_t BATCH_CHUNK_SLACK = 4 * 16;
 
-    // ---- per item: the single call's checks, then what the batch cannot take (all before any HIP call)
-    std::vector<BatchPlan> plan;
-    for (int64_t i = 0; i < count; ++i) {
-        ellp_batch_item &it = items[i];
-        it.err[0] = 0;
-        if (stats_out) memset(&stats_out[i], 0, sizeof(ellp_stats));
-        ellp_status s = check_problem(kind, it.m, it.n, it.n_c, it.A, it.c, it.b, it.bound_kind, it.lb, it.ub, it.x, it.B_index,
-                                      it.n_B, it.N_index, it.N_bound, it.n_N, it.y, it.d, it.err, sizeof(it.err));
-        if (s == ELLP_OPTIMAL && small_lds_bytes(it.m, it.n_N) == 0) {
-            set_err(it.err, sizeof(it.err), "batch: the LU-per-iteration kernel of a batch takes up to %d rows within 150 KB of LDS "
-                                            "(this LP: m = %lld, |N| = %lld)", SMALL_MAX_M, (long long)it.m, (long long)it.n_N);
-            s = ELLP_ERR_ARG;
-        }
-        if (s == ELLP_OPTIMAL && kind == ELLP_ENGINE_DUAL && !dual_start_feasible(it.n_N, it.N_index, it.N_bound, it.d, eps, it.err, sizeof(it.err)))
-            s = ELLP_ERR_PANIC;
-        status_out[i] = s;
-        if (s != ELLP_OPTIMAL) continue;
-        BatchPlan p;
-        p.item = i;
-        p.ld = round_up(it.m, 16);
-        p.nNa = it.n_N > 0 ? it.n_N : 1;
-        p.lds = small_lds_bytes(it.m, it.n_N);
-        p.nt = small_threads(it.m, it.n_N);
-        plan.push_back(p);
-    }
-    if (plan.empty()) return ELLP_OPTIMAL;
-
-    // ---- layout
-    const size_t R = plan.size();
+// The slab of the items plan[0 .. R): offsets into each BatchPlan, and each item's share of the slab in BatchPlan::bytes
+// (its own arrays plus its entries of the shared arrays; a chunk's total is their sum plus at most BATCH_CHUNK_SLACK)
+struct BatchLayout {
+    size_t out_bytes, o_sargs_all, o_margs_all, o_sargs_run, o_margs_run, stage_bytes, total;
+};
+BatchLayout batch_layout(int kind, const ellp_batch_item *items, BatchPlan *plan, size_t R, bool bflip) {
+    BatchLayout L{};
     size_t off = sizeof(DevState) * R;
+    BatchPlan *owner = nullptr;  // the item the next takes belong to
     auto take = [&](size_t bytes) {
         const size_t o = off;
-        off += (bytes + 15) / 16 * 16;
+        off += batch_round16(bytes);
+        if (owner) owner->bytes += batch_round16(bytes);
         return o;
     };
-    for (BatchPlan &p : plan) {
+    size_t nmid = 0;
+    for (size_t k = 0; k < R; ++k) {
+        BatchPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
+        owner = &p;
+        p.bytes = sizeof(DevState) + 2 * sizeof(SmallArgs) + (p.mid ? 2 * sizeof(MidArgs) : 0);
         p.o_x = take(sizeof(double) * (size_t)it.n_c);
         p.o_B = take(sizeof(int64_t) * (size_t)it.m);
         p.o_N = take(sizeof(int64_t) * (size_t)p.nNa);
         p.o_Nb = take((size_t)p.nNa);
         p.o_y = kind == ELLP_ENGINE_DUAL ? take(sizeof(double) * (size_t)p.ld) : 0;
         p.o_d = kind == ELLP_ENGINE_DUAL ? take(sizeof(double) * (size_t)it.n_c) : 0;
+        nmid += p.mid ? 1 : 0;
     }
-    const size_t out_bytes = off;
-    for (BatchPlan &p : plan) {
+    L.out_bytes = off;
+    for (size_t k = 0; k < R; ++k) {
+        BatchPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
+        owner = &p;
         p.o_AB = take(sizeof(double) * (size_t)(p.ld * it.m));
         p.o_AN = take(sizeof(double) * (size_t)(p.ld * p.nNa));
         p.o_cB = take(sizeof(double) * (size_t)it.m);
@@ -190,34 +158,51 @@ extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, el
         p.o_lb = take(sizeof(double) * (size_t)it.n_c);
         p.o_ub = take(sizeof(double) * (size_t)it.n_c);
         p.o_kind = take((size_t)it.n_c);
+        // k_mid, like k_small, touches rbuf / kbuf at nonbasic positions j < |N| only, and flist up to |N| entries
         p.o_rbuf = take(sizeof(double) * (size_t)p.nNa);
         p.o_kbuf = take(sizeof(double) * (size_t)p.nNa);
         p.o_fl = bflip ? take(sizeof(long long) * (size_t)(p.nNa + 1)) : 0;
     }
-    const size_t o_args_all = take(sizeof(SmallArgs) * R);
-    const size_t o_args_run = take(sizeof(SmallArgs) * R);
-    const size_t total = off;
-
-    // ---- device
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_err(errbuf, errlen, "no HIP device available (this library has no CPU path)");
-        return ELLP_ERR_DEVICE;
+    owner = nullptr;  // the argument arrays: shared, counted in the items' bytes above
+    L.o_sargs_all = take(sizeof(SmallArgs) * R);
+    L.o_margs_all = take(sizeof(MidArgs) * nmid);
+    L.o_sargs_run = take(sizeof(SmallArgs) * R);  // the round's argument lists are written per round
+    L.o_margs_run = take(sizeof(MidArgs) * nmid);
+    L.stage_bytes = off;
+    for (size_t k = 0; k < R; ++k) {
+        BatchPlan &p = plan[k];
+        if (!p.mid) continue;
+        owner = &p;
+        p.o_LUa = take(sizeof(double) * (size_t)(p.ld * p.ld));
+        p.o_Ut = take(sizeof(double) * (size_t)(p.ld * p.ld));
+        p.o_ANt = take(sizeof(double) * (size_t)(p.ld * p.ldn));
     }
-    int dev = opts.device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    HIPCHK(hipSetDevice(dev));
-    BatchCleanup cl;
-    HIPCHK(host_set_acquire(dev, &cl.hs));
-    HIPCHK(batch_buf_acquire(dev, true, total, &cl.stage));
-    HIPCHK(batch_buf_acquire(dev, false, total, &cl.slab));
+    L.total = off;
+    return L;
+}
+
+struct BatchRun {
+    int kind;
+    bool bflip, maxviol;
+    double eps;
+    uint64_t max_iter, cap_small, cap_mid;
+};
+
+// One chunk of runnable items, start to end: staging, upload, launch rounds, objective, read-back, per-item results
+ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPlan *plan, size_t R, BatchCleanup &cl,
+                            ellp_status *status_out, ellp_stats *stats_out, char *errbuf, size_t errlen) {
+    const int kind = cfg.kind;
+    const BatchLayout L = batch_layout(kind, items, plan, R, cfg.bflip);
     hipStream_t stream = cl.hs.stream;
     unsigned char *h = static_cast<unsigned char *>(cl.stage.p);
     unsigned char *dv = static_cast<unsigned char *>(cl.slab.p);
 
     // ---- staging: the engine's starting arrays, gathered as ellp_engine_create gathers them on the device
     DevState *h_states = reinterpret_cast<DevState *>(h);
-    SmallArgs *h_all = reinterpret_cast<SmallArgs *>(h + o_args_all);
+    SmallArgs *h_all = reinterpret_cast<SmallArgs *>(h + L.o_sargs_all);
+    MidArgs *h_mall = reinterpret_cast<MidArgs *>(h + L.o_margs_all);
+    std::vector<size_t> mid_at(R, 0);  // position of a mid item in the MidArgs lists
+    size_t nmid = 0;
     for (size_t k = 0; k < R; ++k) {
         const BatchPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
@@ -272,53 +257,103 @@ extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, el
         a.nN = nN;
         a.max_iters = 0;
         a.nch = (int)((nN + 63) / 64);
-        a.eps = eps;
+        a.eps = cfg.eps;
         a.trace = Trace{nullptr, nullptr, 0};
         a.stamps = nullptr;
-        a.maxviol = maxviol ? 1 : 0;
-        a.bflip = bflip ? 1 : 0;
-        a.flist = bflip ? reinterpret_cast<long long *>(dv + p.o_fl) : nullptr;
-        h_all[k] = a;
+        a.maxviol = cfg.maxviol ? 1 : 0;
+        a.bflip = cfg.bflip ? 1 : 0;
+        a.flist = cfg.bflip ? reinterpret_cast<long long *>(dv + p.o_fl) : nullptr;
+        h_all[k] = a;  // k_primal_obj_batch reads every item's, mid items' included
+        if (p.mid) {
+            // launch_mid's arguments, from the same arrays
+            MidArgs ma{};
+            ma.A_B = a.A_B; ma.A_N = a.A_N; ma.c_B = a.c_B; ma.c_N = a.c_N; ma.x = a.x; ma.y = a.y; ma.dd = a.dd;
+            ma.lb = a.lb; ma.ub = a.ub; ma.kind = a.kind; ma.B_index = a.B_index; ma.N_index = a.N_index; ma.Nb = a.Nb;
+            ma.rbuf = a.rbuf;
+            ma.kbuf = a.kbuf;
+            ma.A_Nt = reinterpret_cast<double *>(dv + p.o_ANt);
+            ma.LUa = reinterpret_cast<double *>(dv + p.o_LUa);
+            ma.Ut = reinterpret_cast<double *>(dv + p.o_Ut);
+            ma.st = a.st; ma.m = m; ma.ld = ld; ma.nN = nN; ma.ldn = p.ldn;
+            ma.max_iters = 0;
+            ma.nch = a.nch;
+            ma.eps = cfg.eps;
+            ma.trace = Trace{nullptr, nullptr, 0};
+            ma.stamps = nullptr;
+            ma.maxviol = a.maxviol;
+            ma.resync = 0;
+            ma.b = nullptr;
+            ma.bflip = a.bflip;
+            ma.flist = a.flist;
+            mid_at[k] = nmid;
+            h_mall[nmid++] = ma;
+        }
     }
-    const size_t up_bytes = o_args_run;  // the round's argument list is written per round
-    HIPCHK(hipMemcpyAsync(dv, h, up_bytes, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(dv, h, L.o_sargs_run, hipMemcpyHostToDevice, stream));
 
-    // ---- launch rounds: every item still running, at most `cap` loop bodies each, grouped by workgroup size
-    uint64_t cap = 16384;
-    if (const char *v = getenv("ELLP_BATCH_LAUNCH_ITERS"); v && v[0] && atoll(v) > 0 && (uint64_t)atoll(v) < cap) cap = (uint64_t)atoll(v);
-    SmallArgs *h_run = reinterpret_cast<SmallArgs *>(h + o_args_run);
-    SmallArgs *d_run = reinterpret_cast<SmallArgs *>(dv + o_args_run);
+    // ---- launch rounds: every item still running, at most a cap of loop bodies each, grouped by kernel and workgroup size
+    SmallArgs *h_run = reinterpret_cast<SmallArgs *>(h + L.o_sargs_run);
+    SmallArgs *d_run = reinterpret_cast<SmallArgs *>(dv + L.o_sargs_run);
+    MidArgs *h_mrun = reinterpret_cast<MidArgs *>(h + L.o_margs_run);
+    MidArgs *d_mrun = reinterpret_cast<MidArgs *>(dv + L.o_margs_run);
+    const uint64_t max_iter = cfg.max_iter;
     std::vector<size_t> live;  // plan positions that a launch may still advance
     for (size_t k = 0; k < R; ++k)
         if (items[plan[k].item].n_N > 0 && max_iter > 0) live.push_back(k);
-    static const int nts[3] = {64, 128, 256};
+    static const int nts[6] = {64, 128, 256, 256, 512, 1024};  // k_small_batch x 3, k_mid_batch x 3
     while (!live.empty()) {
-        size_t nrun = 0;
-        bool more = false;  // some item got less than what its budget still allows
+        size_t nrun = 0, nmrun = 0;
+        int64_t tiles_i = 0, tiles_j = 0;  // the grid of the round's transposes
+        bool more = false;                 // some item got less than what its budget still allows
         struct Group { size_t first, cnt, lds; };
-        Group grp[3];
-        for (int g = 0; g < 3; ++g) {
-            grp[g] = Group{nrun, 0, 0};
+        Group grp[6];
+        for (int g = 0; g < 6; ++g) {
+            const bool gmid = g >= 3;
+            grp[g] = Group{gmid ? nmrun : nrun, 0, 0};
             for (size_t k : live) {
                 const BatchPlan &p = plan[k];
-                if (p.nt != nts[g]) continue;
+                if (p.mid != gmid || p.nt != nts[g]) continue;
                 const uint64_t remaining = max_iter - p.done;
-                SmallArgs a = h_all[k];
-                a.max_iters = remaining < cap ? remaining : cap;
-                more = more || a.max_iters < remaining;
-                h_run[nrun++] = a;
+                const uint64_t cap = gmid ? cfg.cap_mid : cfg.cap_small;
+                const uint64_t n = remaining < cap ? remaining : cap;
+                more = more || n < remaining;
+                if (gmid) {
+                    MidArgs a = h_mall[mid_at[k]];
+                    a.max_iters = n;
+                    h_mrun[nmrun++] = a;
+                    const int64_t ti = (a.m + 31) / 32, tj = (a.nN + 31) / 32;
+                    tiles_i = ti > tiles_i ? ti : tiles_i;
+                    tiles_j = tj > tiles_j ? tj : tiles_j;
+                } else {
+                    SmallArgs a = h_all[k];
+                    a.max_iters = n;
+                    h_run[nrun++] = a;
+                }
                 grp[g].cnt += 1;
                 if (p.lds > grp[g].lds) grp[g].lds = p.lds;
             }
         }
-        HIPCHK(hipMemcpyAsync(d_run, h_run, sizeof(SmallArgs) * nrun, hipMemcpyHostToDevice, stream));
-        for (int g = 0; g < 3; ++g) {
+        if (nrun) HIPCHK(hipMemcpyAsync(d_run, h_run, sizeof(SmallArgs) * nrun, hipMemcpyHostToDevice, stream));
+        if (nmrun) {
+            HIPCHK(hipMemcpyAsync(d_mrun, h_mrun, sizeof(MidArgs) * nmrun, hipMemcpyHostToDevice, stream));
+            // the row-major copy of A_N each k_mid launch reads, made afresh as launch_mid makes it
+            hipLaunchKernelGGL(k_mid_transpose_batch, dim3((unsigned)tiles_i, (unsigned)tiles_j, (unsigned)nmrun), dim3(256), 0,
+                               stream, static_cast<const MidArgs *>(d_mrun));
+        }
+        for (int g = 0; g < 6; ++g) {
             if (grp[g].cnt == 0) continue;
-            const void *fn = small_batch_kernel(kind, nts[g]);
+            const bool gmid = g >= 3;
+            const void *fn = gmid ? mid_batch_kernel(kind, nts[g]) : small_batch_kernel(kind, nts[g]);
             HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)grp[g].lds));
-            const SmallArgs *arg = d_run + grp[g].first;
-            void *kargs[] = {&arg};
-            HIPCHK(hipLaunchKernel(fn, dim3((unsigned)grp[g].cnt), dim3((unsigned)nts[g]), kargs, grp[g].lds, stream));
+            if (gmid) {
+                const MidArgs *arg = d_mrun + grp[g].first;
+                void *kargs[] = {&arg};
+                HIPCHK(hipLaunchKernel(fn, dim3((unsigned)grp[g].cnt), dim3((unsigned)nts[g]), kargs, grp[g].lds, stream));
+            } else {
+                const SmallArgs *arg = d_run + grp[g].first;
+                void *kargs[] = {&arg};
+                HIPCHK(hipLaunchKernel(fn, dim3((unsigned)grp[g].cnt), dim3((unsigned)nts[g]), kargs, grp[g].lds, stream));
+            }
         }
         HIPCHK(hipGetLastError());
         if (!more) break;  // every item has run to its end or to its budget
@@ -332,9 +367,9 @@ extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, el
         live.swap(next);
     }
     if (kind == ELLP_ENGINE_PRIMAL)
-        hipLaunchKernelGGL(k_primal_obj_batch, dim3((unsigned)R), dim3(1024), 0, stream, reinterpret_cast<const SmallArgs *>(dv + o_args_all));
+        hipLaunchKernelGGL(k_primal_obj_batch, dim3((unsigned)R), dim3(1024), 0, stream, reinterpret_cast<const SmallArgs *>(dv + L.o_sargs_all));
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h, dv, out_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(h, dv, L.out_bytes, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
 
     // ---- per item: status (run_small), statistics (fill_stats), point (ellp_engine_read_point)
@@ -364,6 +399,149 @@ extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, el
         if (kind == ELLP_ENGINE_DUAL) {
             memcpy(it.y, h + p.o_y, sizeof(double) * (size_t)it.m);
             memcpy(it.d, h + p.o_d, sizeof(double) * (size_t)it.n_c);
+        }
+    }
+    return ELLP_OPTIMAL;
+}
+
+}  // namespace
+
+extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, ellp_batch_item *items, const ellp_opts *opts_in,
+                                                     ellp_status *status_out, ellp_stats *stats_out, char *errbuf,
+                                                     size_t errlen) {
+    if (errbuf && errlen) errbuf[0] = 0;
+    if (count < 0 || (count > 0 && (!items || !status_out))) {
+        set_err(errbuf, errlen, "count < 0, or items / status_out NULL");
+        return ELLP_ERR_ARG;
+    }
+    if (kind != ELLP_ENGINE_PRIMAL && kind != ELLP_ENGINE_DUAL) {
+        set_err(errbuf, errlen, "unknown engine kind %d", kind);
+        return ELLP_ERR_ARG;
+    }
+    ellp_opts opts;
+    ellp_default_opts(&opts);
+    if (opts_in) opts = *opts_in;
+    const bool bflip = kind == ELLP_ENGINE_DUAL && (opts.flags & ELLP_FLAG_DUAL_BOUND_FLIPPING);
+    const bool maxviol = kind == ELLP_ENGINE_DUAL && (opts.flags & ELLP_FLAG_DUAL_MAX_VIOLATION);
+    if (opts.pipeline != 0 && opts.pipeline != 3) {
+        set_err(errbuf, errlen, "batch: pipeline %d; the batch runs the LU-per-iteration kernel (pipeline 0 or 3)", opts.pipeline);
+        return ELLP_ERR_ARG;
+    }
+    if (opts.partial_segments > 1 || (opts.flags & ELLP_FLAG_PRIMAL_STEEPEST_EDGE) || opts.trace_len > 0 || opts.profile) {
+        set_err(errbuf, errlen, "batch: partial pricing, steepest edge, traces and profiling are not available in a batch");
+        return ELLP_ERR_ARG;
+    }
+    if (opts.pipeline == 0 && !bflip && (opts.refactor_period > 0 || opts.btran_mode != 0)) {
+        set_err(errbuf, errlen, "batch: refactor_period / btran_mode select the explicit-inverse engine, which a batch does not run");
+        return ELLP_ERR_ARG;
+    }
+    BatchRun cfg{};
+    cfg.kind = kind;
+    cfg.bflip = bflip;
+    cfg.maxviol = maxviol;
+    cfg.eps = opts.eps > 0.0 ? opts.eps : 1e-10;
+    cfg.max_iter = opts.max_iter;
+    cfg.cap_small = 16384;
+    cfg.cap_mid = 4096;  // run_small's caps
+    if (const char *v = getenv("ELLP_BATCH_LAUNCH_ITERS"); v && v[0] && atoll(v) > 0) {
+        const uint64_t c = (uint64_t)atoll(v);
+        if (c < cfg.cap_small) cfg.cap_small = c;
+        if (c < cfg.cap_mid) cfg.cap_mid = c;
+    }
+    size_t budget = (size_t)2 << 30;  // slab bytes per chunk (the staging buffer is a part of it)
+    if (const char *v = getenv("ELLP_BATCH_MAX_BYTES"); v && v[0] && atoll(v) > 0 && (size_t)atoll(v) < budget) budget = (size_t)atoll(v);
+
+    // ---- per item: the single call's checks, then what the batch cannot take (all before any HIP call)
+    std::vector<BatchPlan> plan;
+    for (int64_t i = 0; i < count; ++i) {
+        ellp_batch_item &it = items[i];
+        it.err[0] = 0;
+        if (stats_out) memset(&stats_out[i], 0, sizeof(ellp_stats));
+        ellp_status s = check_problem(kind, it.m, it.n, it.n_c, it.A, it.c, it.b, it.bound_kind, it.lb, it.ub, it.x, it.B_index,
+                                      it.n_B, it.N_index, it.N_bound, it.n_N, it.y, it.d, it.err, sizeof(it.err));
+        ExactLoop loop = EXACT_NONE;
+        size_t slds = 0, mlds = 0;
+        if (s == ELLP_OPTIMAL) {
+            // the kernel the single call with these options runs for the whole solve; an item it would run on the
+            // explicit-inverse engine or the certified hybrid is not run at all
+            slds = small_lds_bytes(it.m, it.n_N);
+            mlds = mid_lds_bytes(it.m, it.n_N);
+            loop = exact_loop(opts, bflip, false, opts.partial_segments, it.m, slds, mlds);
+            if (loop == EXACT_NONE) {
+                if (it.m > MID_MAX_M)
+                    set_err(it.err, sizeof(it.err), "batch: the LU-per-iteration kernels of a batch take up to %d rows (this LP: m = %lld)",
+                            MID_MAX_M, (long long)it.m);
+                else if (it.m > SMALL_MAX_M && mlds == 0)
+                    set_err(it.err, sizeof(it.err), "batch: the LU-per-iteration kernel k_mid takes up to %d rows and %d nonbasic columns "
+                                                    "within 150 KB of LDS (this LP: m = %lld, |N| = %lld)",
+                            MID_MAX_M, 4096 * 64, (long long)it.m, (long long)it.n_N);
+                else if (it.m > SMALL_MAX_M)
+                    set_err(it.err, sizeof(it.err), "batch: this LP (m = %lld, |N| = %lld) is over %d rows, where a batch runs only what a "
+                                                    "single call runs on k_mid (pipeline 3, dual bound flipping, pipeline 0 with m <= "
+                                                    "ELLP_MID_AUTO_MAX); these options select an explicit-inverse engine",
+                            (long long)it.m, (long long)it.n_N, SMALL_MAX_M);
+                else
+                    set_err(it.err, sizeof(it.err), "batch: the LU-per-iteration kernel of a batch takes up to %d rows within 150 KB of LDS "
+                                                    "(this LP: m = %lld, |N| = %lld)", SMALL_MAX_M, (long long)it.m, (long long)it.n_N);
+                s = ELLP_ERR_ARG;
+            }
+        }
+        if (s == ELLP_OPTIMAL && kind == ELLP_ENGINE_DUAL && !dual_start_feasible(it.n_N, it.N_index, it.N_bound, it.d, cfg.eps, it.err, sizeof(it.err)))
+            s = ELLP_ERR_PANIC;
+        status_out[i] = s;
+        if (s != ELLP_OPTIMAL) continue;
+        BatchPlan p;
+        p.item = i;
+        p.ld = round_up(it.m, 16);
+        p.nNa = it.n_N > 0 ? it.n_N : 1;
+        p.mid = loop == EXACT_MID;
+        p.ldn = p.mid ? (it.n_N + 15) / 16 * 16 : 0;
+        p.lds = p.mid ? mlds : slds;
+        p.nt = p.mid ? mid_threads(it.m) : small_threads(it.m, it.n_N);
+        plan.push_back(p);
+    }
+    if (plan.empty()) return ELLP_OPTIMAL;
+
+    // ---- chunks: consecutive items within the budget (an item alone over it is a chunk of its own)
+    std::vector<size_t> cut{0};
+    size_t max_stage = 0, max_total = 0;
+    {
+        (void)batch_layout(kind, items, plan.data(), plan.size(), bflip);  // every item's share of a slab
+        size_t acc = BATCH_CHUNK_SLACK;
+        for (size_t k = 0; k < plan.size(); ++k) {
+            if (k > cut.back() && (acc + plan[k].bytes > budget || k - cut.back() >= 65535)) {
+                cut.push_back(k);
+                acc = BATCH_CHUNK_SLACK;
+            }
+            acc += plan[k].bytes;
+        }
+        cut.push_back(plan.size());
+        for (size_t c = 0; c + 1 < cut.size(); ++c) {
+            const BatchLayout L = batch_layout(kind, items, plan.data() + cut[c], cut[c + 1] - cut[c], bflip);
+            max_stage = L.stage_bytes > max_stage ? L.stage_bytes : max_stage;
+            max_total = L.total > max_total ? L.total : max_total;
+        }
+    }
+
+    // ---- device
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_err(errbuf, errlen, "no HIP device available (this library has no CPU path)");
+        return ELLP_ERR_DEVICE;
+    }
+    int dev = opts.device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+    HIPCHK(hipSetDevice(dev));
+    BatchCleanup cl;
+    HIPCHK(host_set_acquire(dev, &cl.hs));
+    HIPCHK(batch_buf_acquire(dev, true, max_stage, &cl.stage));
+    HIPCHK(batch_buf_acquire(dev, false, max_total, &cl.slab));
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        const ellp_status rc = batch_run_chunk(cfg, items, plan.data() + cut[c], cut[c + 1] - cut[c], cl, status_out, stats_out,
+                                               errbuf, errlen);
+        if (rc != ELLP_OPTIMAL) {  // the items that did not run say so; the call's result is unspecified (ellp_hip.h)
+            for (size_t k = cut[c]; k < plan.size(); ++k) status_out[plan[k].item] = rc;
+            return rc;
         }
     }
     return ELLP_OPTIMAL;

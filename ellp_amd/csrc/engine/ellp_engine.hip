@@ -4022,6 +4022,18 @@ static const void *mid_kernel(int kind, int nt) {
     return reinterpret_cast<const void *>(&k_mid<1, 1024>);
 }
 
+// the instantiation of k_mid_batch for an engine kind and a workgroup size
+static const void *mid_batch_kernel(int kind, int nt) {
+    if (kind == ELLP_ENGINE_PRIMAL) {
+        if (nt == 256) return reinterpret_cast<const void *>(&k_mid_batch<0, 256>);
+        if (nt == 512) return reinterpret_cast<const void *>(&k_mid_batch<0, 512>);
+        return reinterpret_cast<const void *>(&k_mid_batch<0, 1024>);
+    }
+    if (nt == 256) return reinterpret_cast<const void *>(&k_mid_batch<1, 256>);
+    if (nt == 512) return reinterpret_cast<const void *>(&k_mid_batch<1, 512>);
+    return reinterpret_cast<const void *>(&k_mid_batch<1, 1024>);
+}
+
 // the instantiation of k_small for an engine kind and a workgroup size
 static const void *small_kernel(int kind, int nt) {
     if (kind == ELLP_ENGINE_PRIMAL) {
@@ -4090,6 +4102,23 @@ static ellp_status check_problem(int kind, int64_t m, int64_t n, int64_t n_c, co
             return ELLP_ERR_ARG;
         }
     return ELLP_OPTIMAL;
+}
+
+// Which LU-per-iteration loop a single call runs for the whole solve: EXACT_SMALL (k_small), EXACT_MID (k_mid) or
+// EXACT_NONE (the explicit-inverse engine, alone or as the certified hybrid).  The exact loop ALONE is the default up to
+// m <= 128 (k_small, factors in LDS, 1-5 x slower per iteration than the explicit-inverse engine).  Above that the default
+// is the certified hybrid; pipeline = 3, the dual's bound flipping or ELLP_MID_AUTO_MAX still select k_mid for whole
+// solves up to 1024 rows (15-40 x slower).  ellp_engine_create and ellp_batch_solve_with_initial ask this alone.
+enum ExactLoop { EXACT_NONE = 0, EXACT_SMALL = 1, EXACT_MID = 2 };
+static ExactLoop exact_loop(const ellp_opts &o, bool dual_bflip, bool se, int pp_P, int64_t m, size_t small_lds, size_t mid_lds) {
+    const int pl = o.pipeline;
+    int64_t mid_auto = SMALL_MAX_M;
+    if (const char *ev = getenv("ELLP_MID_AUTO_MAX")) mid_auto = atoll(ev);
+    const bool fits = small_lds > 0 || mid_lds > 0;
+    const bool wanted = pp_P <= 1 && !se && (pl == 3 || dual_bflip || (pl == 0 && o.refactor_period <= 0 && o.btran_mode == 0 &&
+                                                                          o.profile == 0 && (m <= SMALL_MAX_M || m <= mid_auto)));
+    if (!wanted || !fits) return EXACT_NONE;
+    return small_lds > 0 ? EXACT_SMALL : EXACT_MID;
 }
 
 // The device state a fresh engine starts from: running, no pivot yet, the objective of the starting point
@@ -4452,16 +4481,9 @@ static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_
         const int pl = e->opts.pipeline;
         e->small_lds = small_lds_bytes(m, n_N);
         e->mid_lds = mid_lds_bytes(m, n_N);
-        // up to which size the exact loop ALONE is the default: m <= 128 (k_small, factors in LDS, 1-5 x slower per iteration
-        // than the explicit-inverse engine).  Above that the default is the certified hybrid (below); pipeline = 3 or
-        // ELLP_MID_AUTO_MAX still select the LU-per-iteration kernel k_mid for whole solves up to 1024 rows (15-40 x slower).
-        int64_t mid_auto = SMALL_MAX_M;
-        if (const char *ev = getenv("ELLP_MID_AUTO_MAX")) mid_auto = atoll(ev);
-        const bool fits = e->small_lds > 0 || e->mid_lds > 0;
-        const bool wanted = e->pp_P <= 1 && !e->se && (pl == 3 || e->dual_bflip || (pl == 0 && e->opts.refactor_period <= 0 && e->opts.btran_mode == 0 &&
-                                                         e->opts.profile == 0 && (m <= SMALL_MAX_M || m <= mid_auto)));
-        e->small = wanted && fits;
-        e->mid = e->small && e->small_lds == 0;
+        const ExactLoop loop = exact_loop(e->opts, e->dual_bflip, e->se, e->pp_P, m, e->small_lds, e->mid_lds);
+        e->small = loop != EXACT_NONE;
+        e->mid = loop == EXACT_MID;
         if (e->small && getenv("ELLP_SMALL_STAMPS") && !e->small_stamps) {
             if (dmalloc(e, &e->small_stamps, 32) == hipSuccess) (void)hipMemsetAsync(e->small_stamps, 0, 256, e->stream);
             else e->small_stamps = nullptr;

@@ -138,11 +138,11 @@ inline size_t mid_lds_bytes(int64_t m, int64_t nN) {
     return o.bytes <= 150 * 1024 ? (size_t)o.bytes : 0;
 }
 
-// A_Nt[i * ldn + j] = A_N[j * ld + i]
-__global__ __launch_bounds__(256) void k_mid_transpose(const double *A_N, double *A_Nt, int64_t m, int64_t ld, int64_t nN, int64_t ldn) {
-    __shared__ double tile[32][33];
+// A_Nt[i * ldn + j] = A_N[j * ld + i], the 32 x 32 tile at rows 32 bx, columns 32 by
+__device__ __forceinline__ void mid_transpose_tile(double (*tile)[33], const double *A_N, double *A_Nt, int64_t m, int64_t ld,
+                                                   int64_t nN, int64_t ldn, unsigned bx, unsigned by) {
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-    const int64_t i0 = (int64_t)blockIdx.x * 32, j0 = (int64_t)blockIdx.y * 32;
+    const int64_t i0 = (int64_t)bx * 32, j0 = (int64_t)by * 32;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int64_t j = j0 + ty + 8 * k, i = i0 + tx;
@@ -154,6 +154,18 @@ __global__ __launch_bounds__(256) void k_mid_transpose(const double *A_N, double
         const int64_t i = i0 + ty + 8 * k, j = j0 + tx;
         if (i < m && j < nN) A_Nt[i * ldn + j] = tile[tx][ty + 8 * k];
     }
+}
+__global__ __launch_bounds__(256) void k_mid_transpose(const double *A_N, double *A_Nt, int64_t m, int64_t ld, int64_t nN, int64_t ldn) {
+    __shared__ double tile[32][33];
+    mid_transpose_tile(tile, A_N, A_Nt, m, ld, nN, ldn, blockIdx.x, blockIdx.y);
+}
+// the same for every item of a batch launch (k_mid_batch): item blockIdx.z; the grid covers the largest item, the tiles
+// beyond an item's own m x nN leave
+__global__ __launch_bounds__(256) void k_mid_transpose_batch(const MidArgs *__restrict__ items) {
+    __shared__ double tile[32][33];
+    const MidArgs &a = items[blockIdx.z];
+    if ((int64_t)blockIdx.x * 32 >= a.m || (int64_t)blockIdx.y * 32 >= a.nN) return;
+    mid_transpose_tile(tile, a.A_N, a.A_Nt, a.m, a.ld, a.nN, a.ldn, blockIdx.x, blockIdx.y);
 }
 
 #define MID_STAMP(slot)                                     \
@@ -775,8 +787,10 @@ __device__ __noinline__ bool mid_lu_solve(lu8 *base, int tid, int pos, double mi
     return true;
 }
 
+// The loop of k_mid for the LP of `a`, run by the whole workgroup.  A function of its arguments alone (no blockIdx), so
+// that k_mid_batch can run one LP per workgroup with the same code (as small_loop is for k_small / k_small_batch).
 template <int KIND, int NT>
-__global__ __launch_bounds__(NT) void k_mid(MidArgs a) {
+__device__ __forceinline__ void mid_loop(const MidArgs a) {
     unsigned long long t_prev = a.stamps ? wall_clock64() : 0ull;
     unsigned long long c_prev = a.stamps ? clock64() : 0ull;
     constexpr int NW = NT / 64;
@@ -1307,4 +1321,18 @@ __global__ __launch_bounds__(NT) void k_mid(MidArgs a) {
         __syncthreads();  // thread 0 clears the flag at the top of the next iteration
         if (stop) return;
     }
+}
+
+template <int KIND, int NT>
+__global__ __launch_bounds__(NT) void k_mid(MidArgs a) {
+    mid_loop<KIND, NT>(a);
+}
+
+// Batched solves (ellp_batch_solve_with_initial): workgroup b runs the LP of items[b] — its own arrays, factors, DevState,
+// rbuf / kbuf / flist and its own dynamic LDS — exactly as k_mid runs it alone; mid_loop parks the item in LDS where k_mid
+// parks its argument.  The item's address is uniform and the items are never written during the launch (scalar loads).
+template <int KIND, int NT>
+__global__ __launch_bounds__(NT) void k_mid_batch(const MidArgs *__restrict__ items) {
+    const MidArgs a = items[blockIdx.x];
+    mid_loop<KIND, NT>(a);
 }

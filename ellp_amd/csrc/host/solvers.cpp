@@ -357,7 +357,7 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
 }  // namespace ellp
 
 // ---- solve_batch: solve() of many problems in lock step, every device loop of every phase in one batched call
-// (ellp_batch_solve_with_initial) for the problems the small kernel takes.  Each problem takes the steps solve() takes
+// (ellp_batch_solve_with_initial) for the problems the LU-per-iteration kernels take.  Each problem takes the steps solve() takes
 // for it — the host set-up, the checks between the phases, the hand-off — and the device loops compute what the single
 // calls compute, so every outcome is solve()'s.  Problems the batch does not take run through solve() itself.
 namespace ellp {
@@ -439,6 +439,18 @@ void settle(BatchOutcome &o, Slot &slot, F &&f) {
 
 bool batchable(const StandardForm &sf, size_t n_N) { return sf.rows() > 0 && sf.rows() <= 128 && n_N > 0; }
 
+// the primal also batches 129 - 1,024 rows where solve() with these options runs k_mid for the whole solve (the engine's
+// exact_loop: pipeline 3, or pipeline 0 with m <= ELLP_MID_AUTO_MAX); an item the batch still refuses (too wide for the
+// kernel's LDS) comes back as ELLP_ERR_ARG and goes through solve()
+bool primal_batchable(const StandardForm &sf, size_t n_N, const EngineOptions &eng) {
+    if (batchable(sf, n_N)) return true;
+    const std::int64_t m = static_cast<std::int64_t>(sf.rows());
+    if (m <= 128 || m > 1024 || n_N == 0) return false;
+    if (eng.pipeline == 3) return true;
+    const char *ev = std::getenv("ELLP_MID_AUTO_MAX");
+    return eng.pipeline == 0 && ev && m <= std::atoll(ev);
+}
+
 void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which, std::uint64_t max_iter, const EngineOptions &eng,
                   std::vector<BatchOutcome> &out) {
     const PrimalSimplexSolver single = PrimalSimplexSolver(max_iter).with_engine(eng);
@@ -468,7 +480,7 @@ void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which,
             it.p1 = std::move(*p1);
         });
         if (it.slot.done) continue;
-        if (!batchable(it.p1->std_form, it.p1->point.N.size())) {
+        if (!primal_batchable(it.p1->std_form, it.p1->point.N.size(), eng)) {
             fallback(it);
             continue;
         }

@@ -188,8 +188,10 @@ ellp_status ellp_dual_solve_with_initial(
     const ellp_opts *opts, ellp_stats *stats, char *errbuf, size_t errbuf_len);
 
 /*
- * Batched solve_with_initial of many small LPs (kind: ELLP_ENGINE_PRIMAL or ELLP_ENGINE_DUAL), one workgroup per LP in
- * one launch of the LU-per-iteration kernel of ellp_small.inc.  Every item ends exactly as the single call
+ * Batched solve_with_initial of many LPs of up to 1,024 rows (kind: ELLP_ENGINE_PRIMAL or ELLP_ENGINE_DUAL), one workgroup
+ * per LP, in launches of the LU-per-iteration kernels: ellp_small.inc's up to 128 rows, ellp_mid.inc's for 129 - 1,024 rows
+ * where the single call with the same opts runs that kernel for the whole solve (pipeline 3, ELLP_FLAG_DUAL_BOUND_FLIPPING,
+ * or pipeline 0 with m <= ELLP_MID_AUTO_MAX).  Every item ends exactly as the single call
  * (ellp_primal_solve_with_initial / ellp_dual_solve_with_initial with the same opts) ends it: status, iteration counts,
  * index sets and the bits of x (y and d for the dual).  An item's arrays are the single call's arguments; x, B_index,
  * N_index, N_bound (y, d) are updated in place.
@@ -199,7 +201,11 @@ ellp_status ellp_dual_solve_with_initial(
  * and the options that make a single call take the explicit-inverse engine instead: refactor_period > 0 or btran_mode != 0
  * on pipeline 0 without ELLP_FLAG_DUAL_BOUND_FLIPPING), ELLP_ERR_DEVICE, or ELLP_OPTIMAL.  These checks and the
  * per-item ones run before any HIP call.  Per item: status_out[i], stats_out[i] (iters, pivots, bound_flips, refactors,
- * obj; may be NULL) and items[i].err.  An item the kernel cannot take (m == 0, m > 128, LDS) gets ELLP_ERR_ARG.
+ * obj; may be NULL) and items[i].err.  An item the kernels cannot take (m == 0, m > 1,024, LDS, or one the single call
+ * would run on an explicit-inverse engine, e.g. m > 128 with default opts) gets ELLP_ERR_ARG.  Large batches run in
+ * consecutive chunks whose device memory stays within a fixed budget; chunking changes no item's result.  When the call as
+ * a whole fails (any return value but ELLP_OPTIMAL), status_out, stats_out and the items' arrays are unspecified: items of
+ * chunks that ran before the failure may have been updated, the others not.
  * Of opts.flags only ELLP_FLAG_DUAL_MAX_VIOLATION and ELLP_FLAG_DUAL_BOUND_FLIPPING take effect; opts.max_iter holds per item.
  */
 typedef struct ellp_batch_item {
