@@ -279,9 +279,9 @@ class _Solver:
         """solve() of every problem in `problems`, in lock step: the device loops of each phase of all problems the
         LU-per-iteration kernels take run in batched launches, one workgroup per problem; the others are solved one by
         one.  The batch takes 1 to 128 rows (k_small), and for the primal solver also 129 to 1,024 rows where solve()
-        runs the exact kernel k_mid for the whole solve (pipeline=3, or pipeline 0 with m <= ELLP_MID_AUTO_MAX).  The
-        dual solver sends problems above 128 rows through solve() one by one: its phase-1 start is built on the device
-        from a fresh LU there, which the batch does not do.  Returns a list with one entry per problem: the SolverResult
+        runs the exact kernel k_mid for the whole solve (pipeline=3, or pipeline 0 with m <= ELLP_MID_AUTO_MAX; for the
+        dual solver also bound flipping).  The dual's phase-1 starts of those problems, which solve() builds on the device,
+        are built for all of them in one batched call (ellp_batch_dual_phase1_start).  Returns a list with one entry per problem: the SolverResult
         solve(p) returns, or, where solve(p) would raise, the exception instance it would raise (returned, not raised).
         Results are those of solve(p) to the bit."""
         problems = list(problems)

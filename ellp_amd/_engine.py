@@ -85,6 +85,9 @@ def lib():
     L.ellp_batch_solve_with_initial.restype = C.c_int
     L.ellp_batch_solve_with_initial.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p,
                                                 C.c_char_p, C.c_size_t]
+    L.ellp_batch_dual_phase1_start.restype = C.c_int
+    L.ellp_batch_dual_phase1_start.argtypes = [C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_char_p,
+                                               C.c_size_t]
     L.ellp_engine_create.restype = C.c_int
     L.ellp_engine_create.argtypes = ([C.c_int] + _PROBLEM_ARGS + [C.c_void_p, C.c_void_p] +
                                      [C.POINTER(Opts), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t])
@@ -307,6 +310,34 @@ def batch_solve_with_initial(kind, flat_problems, opts=None):
     if s != OPTIMAL:
         raise EllpHipError(s, err.value.decode())
     return [(status[k], stats[k], items[k].err.decode()) for k in range(n)]
+
+
+def batch_dual_phase1_start(problems, opts=None):
+    """ellp_batch_dual_phase1_start: DualPhase1::new's point for every (m, n, A, c, b, kind, lb, ub, B, N) in one batched
+    call.  Returns one (status, obj, errmsg, FlatProblem) per problem; the FlatProblem holds x, Nb, y and d (as
+    Engine.dual_phase1 + read_point would).  Raises EllpHipError if the call as a whole is refused (options, device)."""
+    fps = []
+    for m, n, A, c, b, kind, lb, ub, B, N in problems:
+        m, n = int(m), int(n)
+        fps.append(FlatProblem(m, n, n, A, c, b, kind, lb, ub, np.zeros(n), B, N, np.zeros(max(n - m, 0), dtype=np.uint8),
+                               y=np.zeros(m), d=np.zeros(n)))
+    k = len(fps)
+    items = (BatchItem * max(k, 1))()
+    for it, fp in zip(items, fps):
+        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
+        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
+        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
+        it.B_index, it.n_B = _p(fp.B), fp.nB
+        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(fp.Nb), fp.nN
+        it.y, it.d = _p(fp.y), _p(fp.d)
+    status = (C.c_int * max(k, 1))()
+    obj = (C.c_double * max(k, 1))()
+    o = opts or default_opts()
+    err = C.create_string_buffer(512)
+    s = lib().ellp_batch_dual_phase1_start(k, items, C.byref(o), status, obj, err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    return [(status[j], obj[j], items[j].err.decode(), fps[j]) for j in range(k)]
 
 
 class Engine:

@@ -2097,11 +2097,11 @@ struct BtranArgs {
     int rows_per_tile, ntiles;
 };
 
-__global__ __launch_bounds__(256) void k_btran_part(BtranArgs a) {
+__device__ __forceinline__ void btran_part_body(BtranArgs a, unsigned bx, unsigned by) {
     if (a.st->status != ST_RUNNING) return;
     const int64_t half = a.ld >> 1;
-    const int64_t j2 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t i0 = (int64_t)blockIdx.y * a.rows_per_tile;
+    const int64_t j2 = (int64_t)bx * 256 + threadIdx.x;
+    const int64_t i0 = (int64_t)by * a.rows_per_tile;
     const int64_t i1 = (i0 + a.rows_per_tile < a.m) ? i0 + a.rows_per_tile : a.m;
     double2 acc = make_double2(0.0, 0.0);
     if (j2 < half) {
@@ -2114,12 +2114,13 @@ __global__ __launch_bounds__(256) void k_btran_part(BtranArgs a) {
                 acc.y = fma(ci, w.y, acc.y);
             }
         }
-        reinterpret_cast<double2 *>(a.upart)[(int64_t)blockIdx.y * half + j2] = acc;
+        reinterpret_cast<double2 *>(a.upart)[(int64_t)by * half + j2] = acc;
     }
 }
-__global__ __launch_bounds__(256) void k_btran_reduce(BtranArgs a) {
+__global__ __launch_bounds__(256) void k_btran_part(BtranArgs a) { btran_part_body(a, blockIdx.x, blockIdx.y); }
+__device__ __forceinline__ void btran_reduce_body(BtranArgs a, unsigned bx) {
     if (a.st->status != ST_RUNNING) return;
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t j = (int64_t)bx * 256 + threadIdx.x;
     if (j >= a.ld) return;
     double s = 0.0;
     int t = 0;
@@ -2133,6 +2134,7 @@ __global__ __launch_bounds__(256) void k_btran_reduce(BtranArgs a) {
     for (; t < a.ntiles; ++t) s += a.upart[(int64_t)t * a.ld + j];
     (a.st->usel ? a.u_alt : a.u)[j] = s;
 }
+__global__ __launch_bounds__(256) void k_btran_reduce(BtranArgs a) { btran_reduce_body(a, blockIdx.x); }
 
 // ------------------------------------------------------------------ drift monitor of B^-1
 // The reference factorises A_B afresh every iteration; here B^-1 carries the rounding of every eta
@@ -2229,16 +2231,17 @@ struct ResyncArgs {
     int cols_per_tile, ntiles;
     int force;  // 1: adopt the recomputed x_B whatever the difference (phase hand-off of the dual)
 };
-__global__ __launch_bounds__(256) void k_resync_gather(ResyncArgs a) {
-    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void resync_gather_body(ResyncArgs a, unsigned bx) {
+    const int64_t j = (int64_t)bx * 256 + threadIdx.x;
     if (j < a.nN) a.xg[j] = a.x[a.N_index[j]];
 }
+__global__ __launch_bounds__(256) void k_resync_gather(ResyncArgs a) { resync_gather_body(a, blockIdx.x); }
 // partial[tile][i] = sum over the tile's columns j of A_N[i,j] * xg[j]   (coalesced along i)
-__global__ __launch_bounds__(256) void k_resync_part(ResyncArgs a) {
+__device__ __forceinline__ void resync_part_body(ResyncArgs a, unsigned bx, unsigned by) {
     if (a.st->status != ST_RUNNING && a.st->status != ST_NEED_MAINT) return;
     const int64_t half = a.ld >> 1;
-    const int64_t i2 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t j0 = (int64_t)blockIdx.y * a.cols_per_tile;
+    const int64_t i2 = (int64_t)bx * 256 + threadIdx.x;
+    const int64_t j0 = (int64_t)by * a.cols_per_tile;
     const int64_t j1 = (j0 + a.cols_per_tile < a.nN) ? j0 + a.cols_per_tile : a.nN;
     if (i2 >= half) return;
     const double2 *AN2 = reinterpret_cast<const double2 *>(a.A_N);
@@ -2250,22 +2253,24 @@ __global__ __launch_bounds__(256) void k_resync_part(ResyncArgs a) {
         acc.x = fma(xj, c.x, acc.x);
         acc.y = fma(xj, c.y, acc.y);
     }
-    reinterpret_cast<double2 *>(a.upart)[(int64_t)blockIdx.y * half + i2] = acc;
+    reinterpret_cast<double2 *>(a.upart)[(int64_t)by * half + i2] = acc;
 }
-__global__ __launch_bounds__(256) void k_resync_rhs(ResyncArgs a) {
+__global__ __launch_bounds__(256) void k_resync_part(ResyncArgs a) { resync_part_body(a, blockIdx.x, blockIdx.y); }
+__device__ __forceinline__ void resync_rhs_body(ResyncArgs a, unsigned bx) {
     if (a.st->status != ST_RUNNING && a.st->status != ST_NEED_MAINT) return;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = (int64_t)bx * 256 + threadIdx.x;
     if (i >= a.ld) return;
     double s = 0.0;
     for (int k = 0; k < a.ntiles; ++k) s += a.upart[(int64_t)k * a.ld + i];
     a.tvec[i] = i < a.m ? a.b[i] - s : 0.0;
 }
+__global__ __launch_bounds__(256) void k_resync_rhs(ResyncArgs a) { resync_rhs_body(a, blockIdx.x); }
 // one wave per basic row: cand_i = B^-1[i,:] . t, and the two maxima the decision needs (a maximum is
 // exact in any order: atomicMax on the bit pattern of a non-negative double)
-__global__ __launch_bounds__(256) void k_resync_xb(ResyncArgs a) {
+__device__ __forceinline__ void resync_xb_body(ResyncArgs a, unsigned bx) {
     if (a.st->status != ST_RUNNING && a.st->status != ST_NEED_MAINT) return;
     const int lane = threadIdx.x & 63;
-    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t i = (int64_t)bx * 4 + (threadIdx.x >> 6);
     if (i >= a.m) return;
     const int64_t half = a.ld >> 1;
     const double2 *row = reinterpret_cast<const double2 *>((a.st->cur ? a.W1 : a.W0) + i * a.ld);
@@ -2286,15 +2291,17 @@ __global__ __launch_bounds__(256) void k_resync_xb(ResyncArgs a) {
         if (ax == ax) atomicMax(&a.maxbits[1], (unsigned long long)__double_as_longlong(ax));
     }
 }
-__global__ __launch_bounds__(256) void k_resync_apply(ResyncArgs a) {
+__global__ __launch_bounds__(256) void k_resync_xb(ResyncArgs a) { resync_xb_body(a, blockIdx.x); }
+__device__ __forceinline__ void resync_apply_body(ResyncArgs a, unsigned bx) {
     if (a.st->status != ST_RUNNING && a.st->status != ST_NEED_MAINT) return;
     if (a.st->need_rebuild) return;  // B^-1 failed its refresh: it is rebuilt first, then x_B is checked again
     const double maxdiff = __longlong_as_double((long long)a.maxbits[0]);
     const double maxx = __longlong_as_double((long long)a.maxbits[1]);
     if (!a.force && (!(maxdiff > 1e-11 * (1.0 + maxx)) || isinf(maxdiff))) return;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = (int64_t)bx * 256 + threadIdx.x;
     if (i < a.m) a.x[a.B_index[i]] = a.cand[i];
 }
+__global__ __launch_bounds__(256) void k_resync_apply(ResyncArgs a) { resync_apply_body(a, blockIdx.x); }
 
 // ------------------------------------------------------------------ refactorisation of B^-1 from A_B
 // Product-form rebuild with partial pivoting: start from W = I and bring the m basic columns
@@ -2314,16 +2321,17 @@ struct RefArgs {
     double eps;
 };
 
-__global__ __launch_bounds__(256) void k_ref_init(RefArgs a) {
+__device__ __forceinline__ void ref_init_body(RefArgs a, unsigned bx, unsigned gx) {
     if (a.st->status != ST_RUNNING) return;
     double *W = a.st->cur ? a.W1 : a.W0;
     const int64_t total = a.m * a.ld;
-    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+    for (int64_t t = (int64_t)bx * 256 + threadIdx.x; t < total; t += (int64_t)gx * 256) {
         const int64_t i = t / a.ld, j = t - i * a.ld;
         W[t] = (i == j) ? 1.0 : 0.0;
     }
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.m; i += (int64_t)gridDim.x * 256) a.used[i] = 0;
+    for (int64_t i = (int64_t)bx * 256 + threadIdx.x; i < a.m; i += (int64_t)gx * 256) a.used[i] = 0;
 }
+__global__ __launch_bounds__(256) void k_ref_init(RefArgs a) { ref_init_body(a, blockIdx.x, gridDim.x); }
 __global__ void k_ref_begin(RefArgs a) {
     if (a.st->status != ST_RUNNING) return;
     a.st->refk = 0;
@@ -2427,22 +2435,24 @@ __global__ __launch_bounds__(256) void k_ref_update(RefArgs a) {
     eta_update_rows<false>(src, dst, a.m, a.ld, st->r, dv, st->d_r, st->alpha_r, row0, a.rows_per_block, threadIdx.x);
 }
 
-__global__ __launch_bounds__(256) void k_ref_permute(RefArgs a) {
+__device__ __forceinline__ void ref_permute_body(RefArgs a, unsigned bx) {
     // reads buffer cur, writes buffer cur^1; k_ref_finish then flips cur
     if (a.st->status != ST_RUNNING) return;
     const double *src = a.st->cur ? a.W1 : a.W0;
     double *dstb = a.st->cur ? a.W0 : a.W1;
-    const int64_t k = blockIdx.x;
+    const int64_t k = bx;
     const int64_t p = a.perm[k];
     const double2 *s = reinterpret_cast<const double2 *>(src + p * a.ld);
     double2 *dst = reinterpret_cast<double2 *>(dstb + k * a.ld);
     for (int64_t t = threadIdx.x; t < (a.ld >> 1); t += 256) dst[t] = s[t];
 }
-__global__ void k_ref_finish(RefArgs a) {
+__global__ __launch_bounds__(256) void k_ref_permute(RefArgs a) { ref_permute_body(a, blockIdx.x); }
+__device__ __forceinline__ void ref_finish_body(RefArgs a) {
     if (a.st->status != ST_RUNNING) return;
     a.st->cur ^= 1;
     a.st->do_update = 0;
 }
+__global__ void k_ref_finish(RefArgs a) { ref_finish_body(a); }
 
 // ------------------------------------------------------------------ Newton-Schulz refresh of B^-1
 // Between rebuilds the explicit inverse picks up rounding drift from the eta updates.  Instead of
@@ -2782,9 +2792,9 @@ struct DualRephaseArgs {
 };
 // one wave per variable: d_i = c_i - a_i . y (dual_problem.rs:284 / :173); nonbasic i: value and label by bound
 // kind and the sign of d_i, with the reference's assertions (:293-321 / :201)
-__global__ __launch_bounds__(256) void k_dual_rephase(DualRephaseArgs a) {
+__device__ __forceinline__ void dual_rephase_body(DualRephaseArgs a, unsigned bx) {
     const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int64_t w = (int64_t)bx * 4 + (threadIdx.x >> 6);
     if (w >= a.nN + a.m) return;
     const bool nonbasic = w < a.nN;
     const int64_t var = nonbasic ? a.N_index[w] : a.B_index[w - a.nN];
@@ -2833,6 +2843,7 @@ __global__ __launch_bounds__(256) void k_dual_rephase(DualRephaseArgs a) {
         a.st->status = ELLP_ERR_PANIC;
     }
 }
+__global__ __launch_bounds__(256) void k_dual_rephase(DualRephaseArgs a) { dual_rephase_body(a, blockIdx.x); }
 
 // primal_problem.rs:236-246: the artificial column of row i is signum(b~_i) e_i (f64::signum: +1 for +0.0,
 // -1 for -0.0) and its variable starts at |b~_i|; b~ = b - A v is in `bt`.  Basic position i holds artificial i.
@@ -6678,3 +6689,4 @@ ellp_status ellp_dual_solve_with_initial(int64_t m, int64_t n, int64_t n_c, cons
 }  // extern "C"
 
 #include "ellp_batch.inc"
+#include "ellp_dstart.inc"

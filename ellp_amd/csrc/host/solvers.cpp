@@ -451,6 +451,15 @@ bool primal_batchable(const StandardForm &sf, size_t n_N, const EngineOptions &e
     return eng.pipeline == 0 && ev && m <= std::atoll(ev);
 }
 
+// the dual batches 129 - 1,024 rows where solve() with these options runs k_mid (the same rule, plus bound flipping); their
+// phase-1 start, which solve() makes on the device (point_deferred), comes from ellp_batch_dual_phase1_start
+bool dual_mid_batchable(const StandardForm &sf, size_t n_N, const EngineOptions &eng) {
+    const std::int64_t m = static_cast<std::int64_t>(sf.rows());
+    if (m <= 128 || m > 1024 || n_N == 0) return false;
+    if (eng.flags & ELLP_FLAG_DUAL_BOUND_FLIPPING) return true;
+    return primal_batchable(sf, n_N, eng);
+}
+
 void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which, std::uint64_t max_iter, const EngineOptions &eng,
                   std::vector<BatchOutcome> &out) {
     const PrimalSimplexSolver single = PrimalSimplexSolver(max_iter).with_engine(eng);
@@ -581,6 +590,7 @@ void dual_batch(std::vector<Problem> &probs, std::uint64_t max_iter, const Engin
         it.slot.done = true;
     };
     std::vector<Seam *> seams;
+    std::vector<Item *> deferred;  // phase-1 start made on the device, in one batched call
     for (size_t k = 0; k < probs.size(); ++k) {
         Item &it = items[k];
         it.slot.out = k;
@@ -594,7 +604,12 @@ void dual_batch(std::vector<Problem> &probs, std::uint64_t max_iter, const Engin
             it.p1 = std::move(*p1);
         });
         if (it.slot.done) continue;
-        if (it.p1->point_deferred || !batchable(it.p1->std_form, it.p1->point.point.N.size())) {
+        if (it.p1->point_deferred) {
+            if (dual_mid_batchable(it.p1->std_form, it.p1->point.point.N.size(), eng)) deferred.push_back(&it);
+            else fallback(it);
+            continue;
+        }
+        if (!batchable(it.p1->std_form, it.p1->point.point.N.size())) {
             fallback(it);
             continue;
         }
@@ -602,6 +617,56 @@ void dual_batch(std::vector<Problem> &probs, std::uint64_t max_iter, const Engin
         it.seam.pt = &it.p1->point.point;
         it.seam.dp = &it.p1->point;
         seams.push_back(&it.seam);
+    }
+    if (!deferred.empty()) {
+        // the starting points solve() makes with ellp_engine_create_dual_phase1, all in one call and bit for bit the same
+        // (x, labels, y, d; the seam's starting objective is host_dual_obj of these, as the resident engine's is, and a
+        // k_mid engine's loop finds its own leaving row).  An item whose start fails (a singular basis, a panic) or that the
+        // call refuses goes through solve(), which meets the same failure
+        std::vector<Flat> fl(deferred.size());
+        std::vector<ellp_batch_item> bi(deferred.size());
+        for (size_t k = 0; k < deferred.size(); ++k) {
+            const StandardForm &sf = deferred[k]->p1->std_form;
+            DualFeasiblePoint &dp = deferred[k]->p1->point;
+            fl[k] = flatten(sf, dp.point);
+            ellp_batch_item &b = bi[k];
+            std::memset(&b, 0, sizeof(b));
+            b.m = static_cast<std::int64_t>(sf.rows());
+            b.n = static_cast<std::int64_t>(sf.cols());
+            b.n_c = static_cast<std::int64_t>(sf.bounds.size());
+            b.A = sf.A.a.data();
+            b.c = sf.c.data();
+            b.b = sf.b.data();
+            b.bound_kind = fl[k].kind.data();
+            b.lb = fl[k].lb.data();
+            b.ub = fl[k].ub.data();
+            b.x = dp.point.x.data();
+            b.B_index = fl[k].B.data();
+            b.n_B = static_cast<std::int64_t>(fl[k].B.size());
+            b.N_index = fl[k].N.data();
+            b.N_bound = fl[k].Nb.data();
+            b.n_N = static_cast<std::int64_t>(fl[k].N.size());
+            b.y = dp.y.data();
+            b.d = dp.d.data();
+        }
+        const ellp_opts o = make_opts(max_iter, eng);
+        std::vector<ellp_status> st(deferred.size(), ELLP_ERR_ARG);
+        char err[512] = {0};
+        const ellp_status rc = ellp_batch_dual_phase1_start(static_cast<std::int64_t>(bi.size()), bi.data(), &o, st.data(), nullptr,
+                                                            err, sizeof(err));
+        for (size_t k = 0; k < deferred.size(); ++k) {
+            Item &it = *deferred[k];
+            if (rc != ELLP_OPTIMAL || st[k] != ELLP_OPTIMAL) {
+                fallback(it);
+                continue;
+            }
+            unflatten(fl[k], it.p1->point.point);
+            it.p1->point_deferred = false;
+            it.seam.sf = &it.p1->std_form;
+            it.seam.pt = &it.p1->point.point;
+            it.seam.dp = &it.p1->point;
+            seams.push_back(&it.seam);
+        }
     }
     if (!run_seams(ELLP_ENGINE_DUAL, seams, max_iter, eng)) {
         for (Item &it : items)

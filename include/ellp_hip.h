@@ -339,6 +339,21 @@ ellp_status ellp_engine_create_dual_phase1(int64_t m, int64_t n, const double *A
                                            ellp_engine **out, char *errbuf, size_t errlen);
 
 /*
+ * The same starting point for many LPs at once, without an engine per LP: for every item, B^-1 from A_B (the blocked
+ * rebuild), y, d, the nonbasic labels and values, x_B, the loop's entry assertion and the starting objective, each bit
+ * for bit what ellp_engine_create_dual_phase1 followed by ellp_engine_read_point gives for that item alone with these
+ * options.  All items' kernels run in the same launches (one workgroup grid per item in grid dimension z), with one host
+ * synchronisation after the permutation probe and one read-back.  Per item (ellp_batch_item, n = n_c, n_B = m,
+ * n_N = n - m): inputs A, c, b, bound_kind, lb, ub, B_index, N_index (in the order the caller's phase-1 basis has them);
+ * outputs x (n), N_bound (n - m), y (m), d (n), err and status_out[i] (ELLP_OPTIMAL, ELLP_ERR_SINGULAR, ELLP_ERR_PANIC,
+ * ELLP_ERR_ARG); obj_out[i] (may be NULL) the starting objective.  Items the single call would not start on the
+ * LU-per-iteration kernels (m > 1,024, or options that give it the explicit-inverse engine) are refused with
+ * ELLP_ERR_ARG.  Chunks within the batch's device budget (ELLP_BATCH_MAX_BYTES) change no item's bits.  Returns
+ * ELLP_ERR_ARG for bad arguments of the call, ELLP_ERR_DEVICE on a HIP failure, otherwise ELLP_OPTIMAL. */
+ellp_status ellp_batch_dual_phase1_start(int64_t count, ellp_batch_item *items, const ellp_opts *opts,
+                                         ellp_status *status_out, double *obj_out, char *errbuf, size_t errlen);
+
+/*
  * The dual method's phase-1 -> phase-2 hand-off without leaving HBM (SURVEY.md §8 f2;
  * DualPhase2::from(phase_1), dual_problem.rs:258-404) for the common case that the box problem of phase 1
  * has the same matrix as the original standard form (no TwoSided / Fixed variable was dropped,

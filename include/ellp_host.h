@@ -56,8 +56,10 @@ int ellp_solve(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_
 void ellp_result_free(ellp_result *r);
 
 /* solve() of many problems by one solver in lock step: every phase's device loops of the problems the small kernel
- * takes (1 to 128 rows, with nonbasic columns) run in one batched ellp_batch_solve_with_initial; the rest go through
- * ellp_solve.  out[k] is exactly what ellp_solve(probs[k], ...) fills in (ellp_result_free each).  Returns ELLP_ERR_ARG
+ * takes (1 to 128 rows, with nonbasic columns), and of the 129 to 1,024-row problems the single call runs on the exact
+ * mid-size kernel (pipeline 3, ELLP_MID_AUTO_MAX, the dual's bound flipping), run in one batched
+ * ellp_batch_solve_with_initial; the dual's phase-1 starts of the latter come from one ellp_batch_dual_phase1_start.  The
+ * rest go through ellp_solve.  out[k] is exactly what ellp_solve(probs[k], ...) fills in (ellp_result_free each).  Returns ELLP_ERR_ARG
  * (count < 0, a NULL pointer, an unknown solver), ELLP_ERR_DEVICE (host memory; every out[k] says so) or 0. */
 int ellp_solve_batch(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
                      ellp_result *out);
