@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — simplex pivots/sec + achieved HBM GB/s of the HIP pivot engine.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and nothing else: it builds the LP, creates the engine, runs the W
+warm-up and the K timed steps, writes the arrays of `--dump-outputs` and prints the line.  Everything else this file
+measures or checks runs with `--full` only: the longer window, the inverse's residual, the per-kernel times and the
+rooflines made of them (a second run), `config2` / `config4` / `config4_reference_phase1` / `config5`, the whole solve
+with steepest-edge pricing and both CPU baselines.  The timed steps and the arrays written are the same either way.
 
 A "step" is one iteration of the revised-simplex loop (one pass of the hot path:
 BTRAN/pricing/entering/FTRAN/ratio/eta-update) on the synthetic dense LP of BASELINE.json's
@@ -14,8 +20,8 @@ torch or HIP, relays their output and exits with their return code.  Under torch
 set) it is one of the ranks.  N ranks cooperate on ONE pivot stream: the nonbasic columns (storage
 and pricing) are sharded, everything else is replicated ("scaling": "strong").
 
-Besides the headline workload (config 3, so that N=1 is comparable from round to round) every line
-carries a `config2` object (netlib AFIRO through the user API against the reference's known answer), a `config4`
+Besides the headline workload (config 3, so that N=1 is comparable from round to round) every line of a
+`--full` run carries a `config2` object (netlib AFIRO through the user API against the reference's known answer), a `config4`
 object (BASELINE.json's config 4: the same LP shape through the dual loop, N = 1 only) and
 a `config5` object: BASELINE.json's config 5 (m=4000, n=40000, primal), the one it names
 for 1/2/4/8 GPUs, run the same way — pivots/s, the pricing kernel's rate per GPU and its fraction
@@ -46,6 +52,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3000)
     ap.add_argument("--warmup", type=int, default=300)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the longer window, the inverse's "
+                         "residual, per-kernel times and rooflines, configs 2 / 4 / 5, the whole solve, the CPU baselines "
+                         "(the options below that size or switch those legs act with --full only)")
     ap.add_argument("--m", type=int, default=2000)
     ap.add_argument("--n", type=int, default=5000)
     ap.add_argument("--seed", type=int, default=20260301)
@@ -327,7 +337,7 @@ def measure(ctx, args, m, n, seed, solver, steps, warmup, profile_steps, long_wi
         out["long_window"] = {"steps": long_window, "value": round(long_window / ldt, 2), "unit": "pivots/s",
                               "ms_per_step": round(1e3 * ldt / long_window, 6)}
         total_after += long_window
-    out["resid"] = eng.inverse_residual() if world == 1 else None
+    out["resid"] = eng.inverse_residual() if (world == 1 and args.full) else None
     if dump:
         # outside the timed region: what a caller of the engine receives after the last timed step (read_point completes
         # the iteration the two-launch pipeline left open); copied, since the sharded branch below reads the point again
@@ -482,11 +492,15 @@ def main():
     m, n = args.m, args.n
     dual = args.solver == "dual"
     is_c3 = (m, n, args.seed, args.solver) == (2000, 5000, 20260301, "primal")
-    want_c5 = args.config5 == 1 or (args.config5 < 0 and is_c3)
-    long_window = args.long_window if (args.steps < 1000 and args.long_window > 0) else 0
+    full = args.full
+    want_c5 = full and (args.config5 == 1 or (args.config5 < 0 and is_c3))
+    want_c4 = full and (args.config4 == 1 or (args.config4 < 0 and is_c3)) and world == 1
+    # the longer window belongs to --full.  With --dump-outputs a plain run steps through it as well: the arrays are
+    # read after it, so the point they hold does not depend on --full
+    long_window = args.long_window if (args.steps < 1000 and args.long_window > 0 and (full or args.dump_outputs)) else 0
 
-    head = measure(ctx, args, m, n, args.seed, args.solver, args.steps, args.warmup, args.profile_steps, long_window,
-                   dump=bool(args.dump_outputs))
+    head = measure(ctx, args, m, n, args.seed, args.solver, args.steps, args.warmup, args.profile_steps if full else 0,
+                   long_window, dump=bool(args.dump_outputs))
     c5 = None
     if want_c5:
         c5m = measure(ctx, args, 4000, 40000, 20260305, "primal", args.config5_steps, 100,
@@ -508,7 +522,7 @@ def main():
                   "sharded_check": c5m.get("sharded_check")}
         del c5m
     c4 = None
-    if (args.config4 == 1 or (args.config4 < 0 and is_c3)) and world == 1:
+    if want_c4:
         c4m = measure(ctx, args, 2000, 5000, args.seed, "dual", args.config4_steps, 200, min(args.profile_steps, 100))
         r4 = roofline_of(c4m, 2000, 5000, "dual", 1)
         c4 = {"workload": f"random dense covering LP m=2000 n=5000 (seed {args.seed}), dual simplex from the slack basis, "
@@ -521,7 +535,7 @@ def main():
               "engine_GBps": round(c4m["engine_bytes_per_pivot"] * c4m["steps"] / c4m["dt"] / 1e9, 1)}
         del c4m
     c4ref = None
-    if (args.config4 == 1 or (args.config4 < 0 and is_c3)) and world == 1 and args.config4_reference:
+    if want_c4 and args.config4_reference:
         # config 4 on the reference's OWN dual phase-1 arrays (dual_problem.rs:89-256: the box problem of the config-3 LP,
         # basis from the LU of A^T, nonbasics at lower / upper by the sign of d), built by this repository's host mirror
         # of ellp's setup (DualPhase1::from_problem: rank check and LU of A^T on the device, the rest on the host)
@@ -554,7 +568,7 @@ def main():
         except Exception as ex:  # the headline must not depend on it
             c4ref = {"error": str(ex)[:300]}
     c3se = None
-    if is_c3 and world == 1 and args.full_solve:
+    if full and is_c3 and world == 1 and args.full_solve:
         # config 3 to OPTIMALITY through the user API with the opt-in steepest-edge extension (ellp_opts.flags = 4; not the
         # reference's pricing rule — its Dantzig rule needs 655 k pivots / 25 s for the same solve, tests/test_gpu_fullsolve.py);
         # objective against the committed independent optimum (tests/golden/synth_optimum_*.json, SciPy-HiGHS)
@@ -581,7 +595,7 @@ def main():
         except Exception as ex:  # the headline must not depend on it
             c3se = {"error": str(ex)[:300]}
     c2 = None
-    if is_c3 and world == 1:
+    if full and is_c3 and world == 1:
         # BASELINE.json's config 2: netlib AFIRO through the user API (parse_mps -> PrimalSimplexSolver::new(None).solve),
         # objective against the reference's known answer (tests/problems/mod.rs:661)
         try:
@@ -620,8 +634,8 @@ def main():
         # ~10-30 s of CPU work: one oracle pivot costs ~(2/3) m^3 flops of unblocked LU
         est = (2.0 / 3.0) * m ** 3 / 7.3e9 + 1e-3  # measured: 0.73 s per pivot at m=2000 on the box's host
         cpu_pivots = int(max(3, min(2000, 15.0 / est)))
-    if world > 1:
-        cpu_pivots = 0  # the CPU baseline is reported by the N=1 run only
+    if world > 1 or not full:
+        cpu_pivots = 0  # the CPU baselines are reported by the N=1 run with --full only
     if cpu_pivots > 0:
         rate, iters, cdt, _ = cpu_baseline(flat, cpu_pivots, args.solver)
         cpu = {"value": round(rate, 4), "unit": "pivots/s", "cores": 1, "kind": "port",
@@ -691,6 +705,12 @@ def main():
         "roofline": roofline, "roofline_dominant": roof_dom, "cpu_baseline": cpu,
         "kernels_us": {k: round(v["avg_us"], 3) for k, v in prof.items()}, "kernels_us_note": EVENT_NOTE,
     }
+    out["full"] = bool(full)
+    if not full:
+        # what a plain run does not measure is left out of its line rather than reported as null
+        for k in ("roofline", "roofline_dominant", "cpu_baseline", "kernels_us", "kernels_us_note"):
+            del out[k]
+        del out["config"]["inverse_residual_after"]
     if "long_window" in head:
         lw = head["long_window"]
         lw["vs_value"] = round(lw["value"] / pivots_per_s, 4)
