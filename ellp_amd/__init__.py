@@ -276,11 +276,14 @@ class _Solver:
             host_lib().ellp_result_free(C.byref(r))
 
     def solve_batch(self, problems):
-        """solve() of every problem in `problems`, in lock step: the device loops of each phase of all problems the
-        LU-per-iteration kernels take run in batched launches, one workgroup per problem; the others are solved one by
-        one.  The batch takes 1 to 128 rows (k_small), and for the primal solver also 129 to 1,024 rows where solve()
-        runs the exact kernel k_mid for the whole solve (pipeline=3, or pipeline 0 with m <= ELLP_MID_AUTO_MAX; for the
-        dual solver also bound flipping).  The dual's phase-1 starts of those problems, which solve() builds on the device,
+        """solve() of every problem in `problems`: the device loops of all problems the LU-per-iteration kernels take run
+        in batched launches, one workgroup per problem; the others are solved one by one.  The primal solver sends a
+        problem to the device once and runs both of its phases there (ellp_batch_primal_solve): the workgroup that ends
+        phase 1 makes the checks, hands off and goes on into phase 2, so no problem waits for another one's phase 1
+        (_engine.batch_primal_info() reports the call's launch rounds and uploaded bytes).  The dual solver runs phase by
+        phase, in lock step.  The batch takes 1 to 128 rows (k_small), and for the primal solver also 129 to 1,024 rows
+        where solve() runs the exact kernel k_mid for the whole solve (pipeline=3, or pipeline 0 with m <=
+        ELLP_MID_AUTO_MAX; for the dual solver also bound flipping).  The dual's phase-1 starts of those problems, which solve() builds on the device,
         are built for all of them in one batched call (ellp_batch_dual_phase1_start).  Returns a list with one entry per problem: the SolverResult
         solve(p) returns, or, where solve(p) would raise, the exception instance it would raise (returned, not raised).
         Results are those of solve(p) to the bit."""

@@ -85,6 +85,10 @@ def lib():
     L.ellp_batch_solve_with_initial.restype = C.c_int
     L.ellp_batch_solve_with_initial.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p,
                                                 C.c_char_p, C.c_size_t]
+    L.ellp_batch_primal_solve.restype = C.c_int
+    L.ellp_batch_primal_solve.argtypes = [C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_char_p, C.c_size_t]
+    L.ellp_batch_primal_info.restype = None
+    L.ellp_batch_primal_info.argtypes = [C.c_void_p]
     L.ellp_batch_dual_phase1_start.restype = C.c_int
     L.ellp_batch_dual_phase1_start.argtypes = [C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_char_p,
                                                C.c_size_t]
@@ -310,6 +314,55 @@ def batch_solve_with_initial(kind, flat_problems, opts=None):
     if s != OPTIMAL:
         raise EllpHipError(s, err.value.decode())
     return [(status[k], stats[k], items[k].err.decode()) for k in range(n)]
+
+
+class BatchPrimalItem(C.Structure):
+    """ellp_batch_primal_item (include/ellp_hip.h)"""
+    _fields_ = [("p1", BatchItem), ("c2", C.c_void_p), ("bound_kind2", C.c_void_p), ("lb2", C.c_void_p), ("ub2", C.c_void_p)]
+
+
+class BatchPrimalResult(C.Structure):
+    """ellp_batch_primal_result (include/ellp_hip.h)"""
+    _fields_ = [("status", C.c_int), ("stage", C.c_int32), ("iters_phase1", C.c_uint64), ("iters_phase2", C.c_uint64),
+                ("obj_phase1", C.c_double), ("obj", C.c_double)]
+
+
+def batch_primal_solve(items, opts=None):
+    """ellp_batch_primal_solve: both phases of every primal solve in one batched call.  items: (fp, c2, kind2, lb2, ub2) with
+    fp the phase-1 FlatProblem (mutated in place: the point of the phase that ended the solve) and the phase-2 costs and
+    bounds (n_c entries each).  Returns one (status, stage, iters_phase1, iters_phase2, obj_phase1, obj, errmsg) per item.
+    Raises EllpHipError if the call as a whole is refused (options, arguments, device)."""
+    items = list(items)
+    n = len(items)
+    arr = (BatchPrimalItem * max(n, 1))()
+    keep = []
+    for it, (fp, c2, kind2, lb2, ub2) in zip(arr, items):
+        c2, lb2, ub2 = _f64(c2), _f64(lb2), _f64(ub2)
+        kind2 = np.ascontiguousarray(kind2, dtype=np.uint8)
+        keep.append((c2, kind2, lb2, ub2))
+        b = it.p1
+        b.m, b.n, b.n_c = fp.m, fp.n, fp.n_c
+        b.A, b.c, b.b, b.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
+        b.lb, b.ub, b.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
+        b.B_index, b.n_B = _p(fp.B), fp.nB
+        b.N_index, b.N_bound, b.n_N = _p(fp.N), _p(fp.Nb), fp.nN
+        it.c2, it.bound_kind2, it.lb2, it.ub2 = _p(c2), _p(kind2), _p(lb2), _p(ub2)
+    res = (BatchPrimalResult * max(n, 1))()
+    o = opts or default_opts()
+    err = C.create_string_buffer(512)
+    s = lib().ellp_batch_primal_solve(n, arr, C.byref(o), res, err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    return [(res[k].status, res[k].stage, res[k].iters_phase1, res[k].iters_phase2, res[k].obj_phase1, res[k].obj,
+             arr[k].p1.err.decode()) for k in range(n)]
+
+
+def batch_primal_info():
+    """ellp_batch_primal_info: the calling thread's last ellp_batch_primal_solve (solve_batch of the primal solver makes one
+    per batch): launch rounds, bytes uploaded by the last chunk and by all chunks, chunks."""
+    out = (C.c_uint64 * 4)()
+    lib().ellp_batch_primal_info(out)
+    return {"rounds": int(out[0]), "upload_bytes": int(out[1]), "upload_bytes_total": int(out[2]), "chunks": int(out[3])}
 
 
 def batch_dual_phase1_start(problems, opts=None):

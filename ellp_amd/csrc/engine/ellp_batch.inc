@@ -19,6 +19,12 @@
 // items][SmallArgs, MidArgs of the items of the current launch round] | [device-only factors of each mid item: LUa, Ut,
 // A_Nt].  Everything left of the first '|' is the one read-back; everything left of the second is the staging buffer.
 //
+// ellp_batch_primal_solve runs BOTH phases of a primal solve on the same slab: the item goes up once with the costs and
+// bounds of both phases ([BatchPhaseRec x items] after the states; c1, c2, lb2, ub2, kind2 after each item's inputs; one
+// BatchPhaseArgs per item next to its SmallArgs), the k_small_batch_primal / k_mid_batch_primal twins hand an item from
+// phase 1 to phase 2 inside whichever launch ends its phase 1 (batch_two_phase, ellp_small.inc), a launch round gives every
+// item the cap of loop bodies whatever its phase, and between rounds the host reads the records only.
+//
 // Included at the end of ellp_engine.hip (outside its anonymous namespace and extern "C" block).
 
 namespace {
@@ -76,6 +82,17 @@ void batch_buf_release(const BatchBuf &b) {
     batch_buf_free(b);
 }
 
+const void *small_batch_primal_kernel(int nt) {
+    if (nt == 64) return reinterpret_cast<const void *>(&k_small_batch_primal<64>);
+    if (nt == 128) return reinterpret_cast<const void *>(&k_small_batch_primal<128>);
+    return reinterpret_cast<const void *>(&k_small_batch_primal<256>);
+}
+const void *mid_batch_primal_kernel(int nt) {
+    if (nt == 256) return reinterpret_cast<const void *>(&k_mid_batch_primal<256>);
+    if (nt == 512) return reinterpret_cast<const void *>(&k_mid_batch_primal<512>);
+    return reinterpret_cast<const void *>(&k_mid_batch_primal<1024>);
+}
+
 const void *small_batch_kernel(int kind, int nt) {
     if (kind == ELLP_ENGINE_PRIMAL) {
         if (nt == 64) return reinterpret_cast<const void *>(&k_small_batch<0, 64>);
@@ -97,6 +114,7 @@ struct BatchPlan {
     size_t o_x, o_B, o_N, o_Nb, o_y, o_d;                                     // outputs
     size_t o_AB, o_AN, o_cB, o_cN, o_lb, o_ub, o_kind, o_rbuf, o_kbuf, o_fl;  // inputs and scratch
     size_t o_LUa, o_Ut, o_ANt;                                               // device-only factors (mid)
+    size_t o_c1, o_c2, o_lb2, o_ub2, o_kind2;                                // whole primal solves: both phases' inputs
     size_t bytes;                                                            // the item's share of the slab (batch_layout)
     uint64_t done = 0;                                                       // loop bodies run so far
 };
@@ -116,13 +134,23 @@ size_t batch_round16(size_t b) { return (b + 15) / 16 * 16; }
 
 // Per-chunk rounding of the four argument arrays, at most (the chunk budget allows for it)
 constexpr size_t BATCH_CHUNK_SLACK = 4 * 16;
+// ... and of the records and the two BatchPhaseArgs arrays of a whole primal solve
+constexpr size_t BATCH_CHUNK_SLACK_PRIMAL = 7 * 16;
+
+// What ellp_batch_primal_solve adds to a batch: the second phase's inputs and the results, by item index
+struct BatchTwo {
+    const ellp_batch_primal_item *pitems;
+    ellp_batch_primal_result *results;
+    uint64_t rounds = 0, upload_last = 0, upload_total = 0, chunks = 0;  // ellp_batch_primal_info
+};
 
 // The slab of the items plan[0 .. R): offsets into each BatchPlan, and each item's share of the slab in BatchPlan::bytes
 // (its own arrays plus its entries of the shared arrays; a chunk's total is their sum plus at most BATCH_CHUNK_SLACK)
 struct BatchLayout {
     size_t out_bytes, o_sargs_all, o_margs_all, o_sargs_run, o_margs_run, stage_bytes, total;
+    size_t o_rec, o_pargs_all, o_pargs_run;  // whole primal solves
 };
-BatchLayout batch_layout(int kind, const ellp_batch_item *items, BatchPlan *plan, size_t R, bool bflip) {
+BatchLayout batch_layout(int kind, const ellp_batch_item *items, BatchPlan *plan, size_t R, bool bflip, bool two = false) {
     BatchLayout L{};
     size_t off = sizeof(DevState) * R;
     BatchPlan *owner = nullptr;  // the item the next takes belong to
@@ -132,12 +160,14 @@ BatchLayout batch_layout(int kind, const ellp_batch_item *items, BatchPlan *plan
         if (owner) owner->bytes += batch_round16(bytes);
         return o;
     };
+    if (two) L.o_rec = take(sizeof(BatchPhaseRec) * R);
     size_t nmid = 0;
     for (size_t k = 0; k < R; ++k) {
         BatchPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
         owner = &p;
         p.bytes = sizeof(DevState) + 2 * sizeof(SmallArgs) + (p.mid ? 2 * sizeof(MidArgs) : 0);
+        if (two) p.bytes += sizeof(BatchPhaseRec) + 2 * sizeof(BatchPhaseArgs);
         p.o_x = take(sizeof(double) * (size_t)it.n_c);
         p.o_B = take(sizeof(int64_t) * (size_t)it.m);
         p.o_N = take(sizeof(int64_t) * (size_t)p.nNa);
@@ -162,12 +192,21 @@ BatchLayout batch_layout(int kind, const ellp_batch_item *items, BatchPlan *plan
         p.o_rbuf = take(sizeof(double) * (size_t)p.nNa);
         p.o_kbuf = take(sizeof(double) * (size_t)p.nNa);
         p.o_fl = bflip ? take(sizeof(long long) * (size_t)(p.nNa + 1)) : 0;
+        if (two) {
+            p.o_c1 = take(sizeof(double) * (size_t)it.n_c);
+            p.o_c2 = take(sizeof(double) * (size_t)it.n_c);
+            p.o_lb2 = take(sizeof(double) * (size_t)it.n_c);
+            p.o_ub2 = take(sizeof(double) * (size_t)it.n_c);
+            p.o_kind2 = take((size_t)it.n_c);
+        }
     }
     owner = nullptr;  // the argument arrays: shared, counted in the items' bytes above
     L.o_sargs_all = take(sizeof(SmallArgs) * R);
     L.o_margs_all = take(sizeof(MidArgs) * nmid);
+    if (two) L.o_pargs_all = take(sizeof(BatchPhaseArgs) * R);
     L.o_sargs_run = take(sizeof(SmallArgs) * R);  // the round's argument lists are written per round
     L.o_margs_run = take(sizeof(MidArgs) * nmid);
+    if (two) L.o_pargs_run = take(sizeof(BatchPhaseArgs) * R);
     L.stage_bytes = off;
     for (size_t k = 0; k < R; ++k) {
         BatchPlan &p = plan[k];
@@ -190,9 +229,9 @@ struct BatchRun {
 
 // One chunk of runnable items, start to end: staging, upload, launch rounds, objective, read-back, per-item results
 ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPlan *plan, size_t R, BatchCleanup &cl,
-                            ellp_status *status_out, ellp_stats *stats_out, char *errbuf, size_t errlen) {
+                            ellp_status *status_out, ellp_stats *stats_out, BatchTwo *two, char *errbuf, size_t errlen) {
     const int kind = cfg.kind;
-    const BatchLayout L = batch_layout(kind, items, plan, R, cfg.bflip);
+    const BatchLayout L = batch_layout(kind, items, plan, R, cfg.bflip, two != nullptr);
     hipStream_t stream = cl.hs.stream;
     unsigned char *h = static_cast<unsigned char *>(cl.stage.p);
     unsigned char *dv = static_cast<unsigned char *>(cl.slab.p);
@@ -201,6 +240,8 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
     DevState *h_states = reinterpret_cast<DevState *>(h);
     SmallArgs *h_all = reinterpret_cast<SmallArgs *>(h + L.o_sargs_all);
     MidArgs *h_mall = reinterpret_cast<MidArgs *>(h + L.o_margs_all);
+    BatchPhaseRec *h_rec = two ? reinterpret_cast<BatchPhaseRec *>(h + L.o_rec) : nullptr;
+    BatchPhaseArgs *h_pall = two ? reinterpret_cast<BatchPhaseArgs *>(h + L.o_pargs_all) : nullptr;
     std::vector<size_t> mid_at(R, 0);  // position of a mid item in the MidArgs lists
     size_t nmid = 0;
     for (size_t k = 0; k < R; ++k) {
@@ -264,6 +305,28 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
         a.bflip = cfg.bflip ? 1 : 0;
         a.flist = cfg.bflip ? reinterpret_cast<long long *>(dv + p.o_fl) : nullptr;
         h_all[k] = a;  // k_primal_obj_batch reads every item's, mid items' included
+        if (two) {
+            const ellp_batch_primal_item &pi = two->pitems[p.item];
+            memcpy(h + p.o_c1, it.c, sizeof(double) * (size_t)it.n_c);
+            memcpy(h + p.o_c2, pi.c2, sizeof(double) * (size_t)it.n_c);
+            memcpy(h + p.o_lb2, pi.lb2, sizeof(double) * (size_t)it.n_c);
+            memcpy(h + p.o_ub2, pi.ub2, sizeof(double) * (size_t)it.n_c);
+            memcpy(h + p.o_kind2, pi.bound_kind2, (size_t)it.n_c);
+            BatchPhaseRec r{};
+            r.phase = 1;
+            r.obj1 = std::numeric_limits<double>::quiet_NaN();
+            h_rec[k] = r;
+            BatchPhaseArgs pa{};
+            pa.c1 = reinterpret_cast<const double *>(dv + p.o_c1);
+            pa.c2 = reinterpret_cast<const double *>(dv + p.o_c2);
+            pa.lb2 = reinterpret_cast<const double *>(dv + p.o_lb2);
+            pa.ub2 = reinterpret_cast<const double *>(dv + p.o_ub2);
+            pa.kind2 = reinterpret_cast<const uint8_t *>(dv + p.o_kind2);
+            pa.rec = reinterpret_cast<BatchPhaseRec *>(dv + L.o_rec) + k;
+            pa.n_c = it.n_c;
+            pa.max_iter = cfg.max_iter;
+            h_pall[k] = pa;
+        }
         if (p.mid) {
             // launch_mid's arguments, from the same arrays
             MidArgs ma{};
@@ -290,33 +353,40 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
         }
     }
     HIPCHK(hipMemcpyAsync(dv, h, L.o_sargs_run, hipMemcpyHostToDevice, stream));
+    uint64_t uploaded = L.o_sargs_run;
 
     // ---- launch rounds: every item still running, at most a cap of loop bodies each, grouped by kernel and workgroup size
     SmallArgs *h_run = reinterpret_cast<SmallArgs *>(h + L.o_sargs_run);
     SmallArgs *d_run = reinterpret_cast<SmallArgs *>(dv + L.o_sargs_run);
     MidArgs *h_mrun = reinterpret_cast<MidArgs *>(h + L.o_margs_run);
     MidArgs *d_mrun = reinterpret_cast<MidArgs *>(dv + L.o_margs_run);
+    BatchPhaseArgs *h_prun = two ? reinterpret_cast<BatchPhaseArgs *>(h + L.o_pargs_run) : nullptr;
+    BatchPhaseArgs *d_prun = two ? reinterpret_cast<BatchPhaseArgs *>(dv + L.o_pargs_run) : nullptr;
     const uint64_t max_iter = cfg.max_iter;
     std::vector<size_t> live;  // plan positions that a launch may still advance
+    // (a whole solve also takes the items without nonbasic columns: their checks and hand-off are the workgroup's too)
     for (size_t k = 0; k < R; ++k)
-        if (items[plan[k].item].n_N > 0 && max_iter > 0) live.push_back(k);
+        if (items[plan[k].item].n_N > 0 ? max_iter > 0 : two != nullptr) live.push_back(k);
     static const int nts[6] = {64, 128, 256, 256, 512, 1024};  // k_small_batch x 3, k_mid_batch x 3
     while (!live.empty()) {
-        size_t nrun = 0, nmrun = 0;
+        if (two) two->rounds += 1;
+        size_t nrun = 0, nmrun = 0, nprun = 0;
         int64_t tiles_i = 0, tiles_j = 0;  // the grid of the round's transposes
         bool more = false;                 // some item got less than what its budget still allows
-        struct Group { size_t first, cnt, lds; };
+        struct Group { size_t first, cnt, lds, pfirst; };
         Group grp[6];
         for (int g = 0; g < 6; ++g) {
             const bool gmid = g >= 3;
-            grp[g] = Group{gmid ? nmrun : nrun, 0, 0};
+            grp[g] = Group{gmid ? nmrun : nrun, 0, 0, nprun};
             for (size_t k : live) {
                 const BatchPlan &p = plan[k];
                 if (p.mid != gmid || p.nt != nts[g]) continue;
                 const uint64_t remaining = max_iter - p.done;
                 const uint64_t cap = gmid ? cfg.cap_mid : cfg.cap_small;
-                const uint64_t n = remaining < cap ? remaining : cap;
-                more = more || n < remaining;
+                // a whole solve: the cap itself, shared by the two phases, each of which may need max_iter loop bodies
+                const uint64_t n = two ? cap : (remaining < cap ? remaining : cap);
+                more = more || (two ? max_iter > cap / 2 : n < remaining);
+                if (two) h_prun[nprun++] = h_pall[k];
                 if (gmid) {
                     MidArgs a = h_mall[mid_at[k]];
                     a.max_iters = n;
@@ -334,6 +404,8 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
             }
         }
         if (nrun) HIPCHK(hipMemcpyAsync(d_run, h_run, sizeof(SmallArgs) * nrun, hipMemcpyHostToDevice, stream));
+        if (nprun) HIPCHK(hipMemcpyAsync(d_prun, h_prun, sizeof(BatchPhaseArgs) * nprun, hipMemcpyHostToDevice, stream));
+        uploaded += sizeof(SmallArgs) * nrun + sizeof(MidArgs) * nmrun + sizeof(BatchPhaseArgs) * nprun;
         if (nmrun) {
             HIPCHK(hipMemcpyAsync(d_mrun, h_mrun, sizeof(MidArgs) * nmrun, hipMemcpyHostToDevice, stream));
             // the row-major copy of A_N each k_mid launch reads, made afresh as launch_mid makes it
@@ -343,20 +415,31 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
         for (int g = 0; g < 6; ++g) {
             if (grp[g].cnt == 0) continue;
             const bool gmid = g >= 3;
-            const void *fn = gmid ? mid_batch_kernel(kind, nts[g]) : small_batch_kernel(kind, nts[g]);
+            const void *fn = two ? (gmid ? mid_batch_primal_kernel(nts[g]) : small_batch_primal_kernel(nts[g]))
+                                 : (gmid ? mid_batch_kernel(kind, nts[g]) : small_batch_kernel(kind, nts[g]));
             HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)grp[g].lds));
+            const BatchPhaseArgs *parg = two ? d_prun + grp[g].pfirst : nullptr;
             if (gmid) {
                 const MidArgs *arg = d_mrun + grp[g].first;
-                void *kargs[] = {&arg};
-                HIPCHK(hipLaunchKernel(fn, dim3((unsigned)grp[g].cnt), dim3((unsigned)nts[g]), kargs, grp[g].lds, stream));
+                void *kargs1[] = {&arg}, *kargs2[] = {&arg, &parg};  // each family gets its own parameter list
+                HIPCHK(hipLaunchKernel(fn, dim3((unsigned)grp[g].cnt), dim3((unsigned)nts[g]), two ? kargs2 : kargs1, grp[g].lds, stream));
             } else {
                 const SmallArgs *arg = d_run + grp[g].first;
-                void *kargs[] = {&arg};
-                HIPCHK(hipLaunchKernel(fn, dim3((unsigned)grp[g].cnt), dim3((unsigned)nts[g]), kargs, grp[g].lds, stream));
+                void *kargs1[] = {&arg}, *kargs2[] = {&arg, &parg};
+                HIPCHK(hipLaunchKernel(fn, dim3((unsigned)grp[g].cnt), dim3((unsigned)nts[g]), two ? kargs2 : kargs1, grp[g].lds, stream));
             }
         }
         HIPCHK(hipGetLastError());
         if (!more) break;  // every item has run to its end or to its budget
+        if (two) {  // the records say who has ended
+            HIPCHK(hipMemcpyAsync(h_rec, dv + L.o_rec, sizeof(BatchPhaseRec) * R, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            std::vector<size_t> next;
+            for (size_t k : live)
+                if (!h_rec[k].done) next.push_back(k);
+            live.swap(next);
+            continue;
+        }
         HIPCHK(hipMemcpyAsync(h_states, dv, sizeof(DevState) * R, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         std::vector<size_t> next;
@@ -372,16 +455,36 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
     HIPCHK(hipMemcpyAsync(h, dv, L.out_bytes, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
 
+    if (two) {
+        two->chunks += 1;
+        two->upload_last = uploaded;
+        two->upload_total += uploaded;
+    }
+
     // ---- per item: status (run_small), statistics (fill_stats), point (ellp_engine_read_point)
     for (size_t k = 0; k < R; ++k) {
         const BatchPlan &p = plan[k];
         ellp_batch_item &it = items[p.item];
         const DevState &s = h_states[k];
         ellp_status st;
-        if (it.n_N == 0) st = ELLP_OPTIMAL;  // primal…:149-151 / dual…:175-177
+        if (two && h_rec[k].verdict == ELLP_ERR_PANIC) {  // the checks of solve() after phase 1 (primal…:42-55)
+            set_err(it.err, sizeof(it.err), "assertion failed: obj > -EPS");
+            st = ELLP_ERR_PANIC;
+        } else if (two && h_rec[k].verdict != 0) st = (ellp_status)h_rec[k].verdict;
+        else if (it.n_N == 0) st = ELLP_OPTIMAL;  // primal…:149-151 / dual…:175-177
         else if (s.status != ST_RUNNING) st = status_message(s, it.err, sizeof(it.err));
         else st = ELLP_MAXITER;
         status_out[p.item] = st;
+        if (two) {
+            const BatchPhaseRec &r = h_rec[k];
+            ellp_batch_primal_result &o = two->results[p.item];
+            o.status = st;
+            o.stage = r.phase;
+            o.iters_phase1 = r.phase == 2 ? r.iters1 : s.iters;
+            o.iters_phase2 = r.phase == 2 ? s.iters : 0;
+            o.obj_phase1 = r.obj1;
+            o.obj = s.obj;
+        }
         if (stats_out) {
             ellp_stats &o = stats_out[p.item];
             o.iters = s.iters;
@@ -406,9 +509,9 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
 
 }  // namespace
 
-extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, ellp_batch_item *items, const ellp_opts *opts_in,
-                                                     ellp_status *status_out, ellp_stats *stats_out, char *errbuf,
-                                                     size_t errlen) {
+// ellp_batch_solve_with_initial, and with `two` ellp_batch_primal_solve (kind ELLP_ENGINE_PRIMAL; items: the phase-1 seams)
+static ellp_status batch_solve_impl(int kind, int64_t count, ellp_batch_item *items, const ellp_opts *opts_in,
+                                    ellp_status *status_out, ellp_stats *stats_out, BatchTwo *two, char *errbuf, size_t errlen) {
     if (errbuf && errlen) errbuf[0] = 0;
     if (count < 0 || (count > 0 && (!items || !status_out))) {
         set_err(errbuf, errlen, "count < 0, or items / status_out NULL");
@@ -490,6 +593,12 @@ extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, el
             s = ELLP_ERR_PANIC;
         status_out[i] = s;
         if (s != ELLP_OPTIMAL) continue;
+        if (two)
+            for (int64_t j = 0; j < it.n_c; ++j)
+                if (two->pitems[i].bound_kind2[j] > 4) {
+                    set_err(errbuf, errlen, "item %lld: bound_kind2[%lld] out of range", (long long)i, (long long)j);
+                    return ELLP_ERR_ARG;
+                }
         BatchPlan p;
         p.item = i;
         p.ld = round_up(it.m, 16);
@@ -506,18 +615,19 @@ extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, el
     std::vector<size_t> cut{0};
     size_t max_stage = 0, max_total = 0;
     {
-        (void)batch_layout(kind, items, plan.data(), plan.size(), bflip);  // every item's share of a slab
-        size_t acc = BATCH_CHUNK_SLACK;
+        const size_t slack = two ? BATCH_CHUNK_SLACK_PRIMAL : BATCH_CHUNK_SLACK;
+        (void)batch_layout(kind, items, plan.data(), plan.size(), bflip, two != nullptr);  // every item's share of a slab
+        size_t acc = slack;
         for (size_t k = 0; k < plan.size(); ++k) {
             if (k > cut.back() && (acc + plan[k].bytes > budget || k - cut.back() >= 65535)) {
                 cut.push_back(k);
-                acc = BATCH_CHUNK_SLACK;
+                acc = slack;
             }
             acc += plan[k].bytes;
         }
         cut.push_back(plan.size());
         for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const BatchLayout L = batch_layout(kind, items, plan.data() + cut[c], cut[c + 1] - cut[c], bflip);
+            const BatchLayout L = batch_layout(kind, items, plan.data() + cut[c], cut[c + 1] - cut[c], bflip, two != nullptr);
             max_stage = L.stage_bytes > max_stage ? L.stage_bytes : max_stage;
             max_total = L.total > max_total ? L.total : max_total;
         }
@@ -538,11 +648,65 @@ extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, el
     HIPCHK(batch_buf_acquire(dev, false, max_total, &cl.slab));
     for (size_t c = 0; c + 1 < cut.size(); ++c) {
         const ellp_status rc = batch_run_chunk(cfg, items, plan.data() + cut[c], cut[c + 1] - cut[c], cl, status_out, stats_out,
-                                               errbuf, errlen);
+                                               two, errbuf, errlen);
         if (rc != ELLP_OPTIMAL) {  // the items that did not run say so; the call's result is unspecified (ellp_hip.h)
             for (size_t k = cut[c]; k < plan.size(); ++k) status_out[plan[k].item] = rc;
             return rc;
         }
     }
     return ELLP_OPTIMAL;
+}
+
+extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, ellp_batch_item *items, const ellp_opts *opts_in,
+                                                     ellp_status *status_out, ellp_stats *stats_out, char *errbuf,
+                                                     size_t errlen) {
+    return batch_solve_impl(kind, count, items, opts_in, status_out, stats_out, nullptr, errbuf, errlen);
+}
+
+// the last ellp_batch_primal_solve of the calling thread that passed the checks of the call (ellp_batch_primal_info)
+static thread_local uint64_t g_batch_primal_info[4] = {0, 0, 0, 0};
+
+extern "C" ellp_status ellp_batch_primal_solve(int64_t count, ellp_batch_primal_item *items, const ellp_opts *opts_in,
+                                               ellp_batch_primal_result *results, char *errbuf, size_t errlen) {
+    if (errbuf && errlen) errbuf[0] = 0;
+    if (count < 0 || (count > 0 && (!items || !results))) {
+        set_err(errbuf, errlen, "count < 0, or items / results NULL");
+        return ELLP_ERR_ARG;
+    }
+    for (int64_t i = 0; i < count; ++i)
+        if (!items[i].c2 || !items[i].bound_kind2 || !items[i].lb2 || !items[i].ub2) {
+            set_err(errbuf, errlen, "item %lld: c2, bound_kind2, lb2 or ub2 NULL", (long long)i);
+            return ELLP_ERR_ARG;
+        }
+    // the phase-1 seams as a batch of their own; their messages go back into the caller's items
+    std::vector<ellp_batch_item> seams((size_t)count);
+    std::vector<ellp_status> status((size_t)count);
+    std::vector<ellp_stats> stats((size_t)count);
+    for (int64_t i = 0; i < count; ++i) {
+        seams[(size_t)i] = items[i].p1;
+        ellp_batch_primal_result &r = results[i];
+        memset(&r, 0, sizeof(r));
+        r.stage = 1;
+        r.obj_phase1 = std::numeric_limits<double>::quiet_NaN();
+    }
+    BatchTwo two{};
+    two.pitems = items;
+    two.results = results;
+    const ellp_status rc = batch_solve_impl(ELLP_ENGINE_PRIMAL, count, seams.data(), opts_in, status.data(), stats.data(), &two,
+                                            errbuf, errlen);
+    for (int64_t i = 0; i < count; ++i) {
+        memcpy(items[i].p1.err, seams[(size_t)i].err, sizeof(items[i].p1.err));
+        if (rc != ELLP_OPTIMAL || status[(size_t)i] < 0) results[i].status = rc != ELLP_OPTIMAL ? rc : status[(size_t)i];
+    }
+    if (rc == ELLP_ERR_ARG) return rc;  // refused by the checks of the call: the record keeps the last call that passed them
+    g_batch_primal_info[0] = two.rounds;
+    g_batch_primal_info[1] = two.upload_last;
+    g_batch_primal_info[2] = two.upload_total;
+    g_batch_primal_info[3] = two.chunks;
+    return rc;
+}
+
+extern "C" void ellp_batch_primal_info(uint64_t *out4) {
+    if (!out4) return;
+    for (int k = 0; k < 4; ++k) out4[k] = g_batch_primal_info[k];
 }

@@ -1336,3 +1336,18 @@ __global__ __launch_bounds__(NT) void k_mid_batch(const MidArgs *__restrict__ it
     const MidArgs a = items[blockIdx.x];
     mid_loop<KIND, NT>(a);
 }
+
+template <int NT>
+struct MidPrimalLoop {
+    static __device__ __forceinline__ void run(const MidArgs &a) { mid_loop<0, NT>(a); }
+};
+
+// k_mid_batch<0, NT> for a whole primal solve (batch_two_phase, ellp_small.inc).  A_Nt is the copy of A_N the round's
+// transpose made; the hand-off changes no column, so phase 2 goes on with it.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_mid_batch_primal(const MidArgs *__restrict__ items,
+                                                         const BatchPhaseArgs *__restrict__ phases) {
+    const MidArgs a = items[blockIdx.x];
+    const BatchPhaseArgs pb = phases[blockIdx.x];
+    batch_two_phase<NT, MidPrimalLoop<NT>>(a, pb);
+}

@@ -953,3 +953,147 @@ __global__ __launch_bounds__(1024) void k_primal_obj_batch(const SmallArgs *__re
     const SmallArgs a = items[blockIdx.x];
     primal_obj(a.c_B, a.c_N, a.x, a.B_index, a.N_index, a.m, a.nN, a.st);
 }
+
+// ---- both phases of a primal solve inside the batch's launches (ellp_batch_primal_solve) ----
+// The LU-per-iteration loops carry no inverse: a phase starts from x, B_index, N_index, Nb, the costs and the bounds.  So the
+// workgroup that ends an item's phase 1 makes the checks of solve() (primal_simplex_solver.rs:42-55), the hand-off of
+// PrimalPhase2::from_phase1 (k_rephase's re-gather and relabel, the reset of ellp_engine_rephase) and goes on into phase 2
+// itself, while its neighbours are wherever they are.  DevState and the loops' arguments stay as they are; what the two
+// phases need beyond them is here.
+struct BatchPhaseRec {  // per item, in the slab: read by the host between launch rounds and with the results
+    int32_t phase;    // 1 / 2: the phase the item's DevState belongs to
+    int32_t done;     // the solve has ended: no further launch takes the item
+    int32_t verdict;  // 0, or the status the checks after phase 1 ended the solve with (ELLP_ERR_PANIC, ELLP_INFEASIBLE)
+    int32_t pad;
+    unsigned long long iters1;  // loop bodies of phase 1, once it has been handed off
+    double obj1;                // c1 . x after phase 1 (NaN until phase 1 has ended Optimal)
+};
+struct BatchPhaseArgs {
+    const double *c1;  // phase 1's costs by variable (the loop has them gathered only)
+    const double *c2, *lb2, *ub2;
+    const uint8_t *kind2;
+    BatchPhaseRec *rec;
+    int64_t n_c;
+    unsigned long long max_iter;  // loop bodies each phase may run (opts.max_iter)
+};
+
+// k_primal_obj's sum by a workgroup of NT threads: thread t stands in for the threads t, t + NT, ... of its 1,024, wave by
+// wave, so every partial sum and their order are that kernel's.  It gives phase 2 the starting objective of a fresh seam
+// call; the objective a solve reports does not depend on it (k_primal_obj_batch forms it anew for every item at the end
+// of the chunk), so this sum is the first thing to drop should the twins' registers need it.
+template <int NT>
+__device__ __forceinline__ void primal_obj_wg(const double *c_B, const double *c_N, const double *x, const int64_t *B_index,
+                                              const int64_t *N_index, int64_t m, int64_t nN, DevState *st, double *s_p) {
+    for (int v0 = 0; v0 < 1024; v0 += NT) {
+        const int v = v0 + (int)threadIdx.x;
+        double acc = 0.0;
+        for (int64_t i = v; i < m; i += 1024) acc = fma(c_B[i], x[B_index[i]], acc);
+        for (int64_t j = v; j < nN; j += 1024) {
+            const double cj = c_N[j];
+            if (cj != 0.0) acc = fma(cj, x[N_index[j]], acc);
+        }
+        acc = wave_sum(acc);
+        if ((v & 63) == 0) s_p[v >> 6] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < 16; ++w) t += s_p[w];
+        st->obj = t;
+    }
+}
+
+// One launch's share of an item's solve: at most item.max_iters loop bodies, of phase 1, of phase 2, or of both with the
+// hand-off in between.  Loop::run is the item's loop (small_loop / mid_loop), called from ONE place: the second trip runs
+// phase 2 on the same arrays, LDS scratch included (every thread is past the barrier below before the loop starts again).
+template <int NT, class Loop, class Args>
+__device__ __forceinline__ void batch_two_phase(const Args &item, const BatchPhaseArgs &pb) {
+    __shared__ double s_po[16];
+    BatchPhaseRec *rec = pb.rec;
+    if (rec->done) return;
+    DevState *st = item.st;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t m = item.m, nN = item.nN;
+    int phase = rec->phase;
+    unsigned long long left = item.max_iters;  // the launch's cap, for both phases together
+#pragma unroll 1
+    for (int trip = 0; trip < 2; ++trip) {
+        Args a = item;
+        if (phase == 2) {
+            a.lb = pb.lb2;
+            a.ub = pb.ub2;
+            a.kind = pb.kind2;
+        }
+        const unsigned long long it0 = st->iters, rem = pb.max_iter - it0;
+        a.max_iters = left < rem ? left : rem;
+        // The loop's thread 0 counts its first body before the loop's first barrier: no wave may enter it before every
+        // wave has read the count above, or a late wave would see it + 1, run one body fewer and unpair the barriers.
+        __syncthreads();
+        if (nN > 0) Loop::run(a);  // without nonbasic columns the seam is Optimal as it stands (primal…:149-151)
+        __threadfence_block();
+        __syncthreads();
+        const unsigned long long it1 = st->iters;
+        const int status = nN > 0 ? st->status : (int)ELLP_OPTIMAL;
+        left -= it1 - it0;
+        if (phase == 2 || status != ELLP_OPTIMAL) {
+            if (tid == 0 && (status != ST_RUNNING || it1 >= pb.max_iter)) rec->done = 1;
+            return;
+        }
+        // ---- the checks of solve() on c1 . x, summed in index order as StandardForm::obj sums it; every wave forms the
+        // whole sum (64 products at a time, added one after the other), so no broadcast is needed
+        double obj = 0.0;
+        for (int64_t i0 = 0; i0 < pb.n_c; i0 += 64) {
+            const int64_t i = i0 + lane;
+            const double p = i < pb.n_c ? pb.c1[i] * item.x[i] : 0.0;
+            const int cnt = pb.n_c - i0 < 64 ? (int)(pb.n_c - i0) : 64;
+            for (int u = 0; u < cnt; ++u) obj += readlane_f64(p, u);
+        }
+        const int verdict = !(obj > -item.eps) ? (int)ELLP_ERR_PANIC : (!(obj < item.eps) ? (int)ELLP_INFEASIBLE : 0);
+        if (tid == 0) {
+            rec->obj1 = obj;
+            if (verdict) {
+                rec->verdict = verdict;
+                rec->done = 1;
+            }
+        }
+        if (verdict) return;
+        __syncthreads();  // every thread has read phase 1's status and count
+        // ---- PrimalPhase2::from_phase1: costs by the current index sets, Free labels (k_rephase); a fresh seam's state
+        for (int64_t k = tid; k < m; k += NT) item.c_B[k] = pb.c2[item.B_index[k]];
+        for (int64_t k = tid; k < nN; k += NT) {
+            const int64_t j = item.N_index[k];
+            item.c_N[k] = pb.c2[j];
+            if (pb.kind2[j] == ELLP_BOUND_FREE) item.Nb[k] = ELLP_NB_FREE;
+        }
+        if (tid == 0) {
+            rec->iters1 = it1;
+            rec->phase = 2;
+            st->status = ST_RUNNING;
+            st->panic_code = 0;
+            st->iters = 0;
+            st->pivots = 0;
+            st->flips = 0;
+            st->lambda = 0.0;
+        }
+        __threadfence_block();
+        __syncthreads();
+        primal_obj_wg<NT>(item.c_B, item.c_N, item.x, item.B_index, item.N_index, m, nN, st, s_po);
+        __threadfence_block();
+        __syncthreads();
+        phase = 2;
+    }
+}
+
+template <int NT>
+struct SmallPrimalLoop {
+    static __device__ __forceinline__ void run(const SmallArgs &a) { small_loop<0, NT>(a); }
+};
+
+// k_small_batch<0, NT> for a whole primal solve: workgroup b runs the LP of items[b] through both phases (phases[b])
+template <int NT>
+__global__ __launch_bounds__(NT) void k_small_batch_primal(const SmallArgs *__restrict__ items,
+                                                           const BatchPhaseArgs *__restrict__ phases) {
+    const SmallArgs a = items[blockIdx.x];
+    const BatchPhaseArgs pb = phases[blockIdx.x];
+    batch_two_phase<NT, SmallPrimalLoop<NT>>(a, pb);
+}

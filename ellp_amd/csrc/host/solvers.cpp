@@ -356,8 +356,9 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
 
 }  // namespace ellp
 
-// ---- solve_batch: solve() of many problems in lock step, every device loop of every phase in one batched call
-// (ellp_batch_solve_with_initial) for the problems the LU-per-iteration kernels take.  Each problem takes the steps solve() takes
+// ---- solve_batch: solve() of many problems, the device loops in batched calls for the problems the LU-per-iteration kernels
+// take: the primal's two phases in one call per batch (ellp_batch_primal_solve), the dual's phase by phase in lock step
+// (ellp_batch_solve_with_initial).  Each problem takes the steps solve() takes
 // for it — the host set-up, the checks between the phases, the hand-off — and the device loops compute what the single
 // calls compute, so every outcome is solve()'s.  Problems the batch does not take run through solve() itself.
 namespace ellp {
@@ -460,14 +461,50 @@ bool dual_mid_batchable(const StandardForm &sf, size_t n_N, const EngineOptions 
     return primal_batchable(sf, n_N, eng);
 }
 
+// the costs and bounds PrimalPhase2::from_phase1 (primal_problem.rs:263-291) gives phase 2, derived without consuming phase 1:
+// the whole solve goes to the device in one call (ellp_batch_primal_solve), which needs both phases' inputs up front
+struct Phase2Inputs {
+    std::vector<double> c;
+    std::vector<std::uint8_t> kind;
+    std::vector<double> lb, ub;
+};
+
+Phase2Inputs phase2_inputs(const PrimalPhase1 &p1) {
+    const StandardForm &sf = p1.std_form;
+    Phase2Inputs in;
+    in.c = sf.c;
+    std::vector<Bound> bounds = sf.bounds;
+    for (size_t i : p1.phase_1_vars) {
+        in.c[i] = 0.0;
+        bounds[i] = Bound::fixed(0.0);
+    }
+    for (size_t i = 0; i < sf.prob.variables.size(); ++i) {
+        in.c[i] = sf.prob.variables[i].obj_coeff;
+        bounds[i] = sf.prob.variables[i].bound;
+    }
+    const size_t nc = bounds.size();
+    in.kind.resize(nc);
+    in.lb.resize(nc);
+    in.ub.resize(nc);
+    for (size_t i = 0; i < nc; ++i) {  // as flatten
+        in.kind[i] = static_cast<std::uint8_t>(bounds[i].kind);
+        in.lb[i] = bounds[i].lb;
+        in.ub[i] = (bounds[i].kind == Bound::Fixed) ? bounds[i].lb : bounds[i].ub;
+    }
+    return in;
+}
+
+// solve() of every problem of `which`, both phases in ONE batched call: phase 1 is built on the host as solve() builds it,
+// the device makes the checks after phase 1 and the hand-off per item (no problem waits for another one's phase 1, and a
+// problem's matrix goes up once), and what comes back maps to SolverResult as the two switch blocks of solve() map it
 void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which, std::uint64_t max_iter, const EngineOptions &eng,
                   std::vector<BatchOutcome> &out) {
     const PrimalSimplexSolver single = PrimalSimplexSolver(max_iter).with_engine(eng);
     struct Item {
         Slot slot;
         std::optional<PrimalPhase1> p1;
-        std::optional<PrimalPhase2> p2;
-        Seam seam;
+        Flat f;
+        Phase2Inputs in2;
     };
     std::vector<Item> items(which.size());
     auto fallback = [&](Item &it) {
@@ -475,7 +512,7 @@ void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which,
         it.slot.done = true;
     };
     // phase 1 on the host
-    std::vector<Seam *> seams;
+    std::vector<Item *> run;
     for (size_t k = 0; k < which.size(); ++k) {
         Item &it = items[k];
         it.slot.out = which[k];
@@ -493,80 +530,81 @@ void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which,
             fallback(it);
             continue;
         }
-        it.seam.sf = &it.p1->std_form;
-        it.seam.pt = &it.p1->point;
-        seams.push_back(&it.seam);
+        run.push_back(&it);
     }
-    if (!run_seams(ELLP_ENGINE_PRIMAL, seams, max_iter, eng)) {
-        for (Item &it : items)
-            if (!it.slot.done) fallback(it);
+    if (run.empty()) return;
+    std::vector<ellp_batch_primal_item> bi(run.size());
+    for (size_t k = 0; k < run.size(); ++k) {
+        Item &it = *run[k];
+        const StandardForm &sf = it.p1->std_form;
+        it.f = flatten(sf, it.p1->point);
+        it.in2 = phase2_inputs(*it.p1);
+        ellp_batch_primal_item &b = bi[k];
+        std::memset(&b, 0, sizeof(b));
+        b.p1.m = static_cast<std::int64_t>(sf.rows());
+        b.p1.n = static_cast<std::int64_t>(sf.cols());
+        b.p1.n_c = static_cast<std::int64_t>(sf.bounds.size());
+        b.p1.A = sf.A.a.data();
+        b.p1.c = sf.c.data();
+        b.p1.b = sf.b.data();
+        b.p1.bound_kind = it.f.kind.data();
+        b.p1.lb = it.f.lb.data();
+        b.p1.ub = it.f.ub.data();
+        b.p1.x = it.p1->point.x.data();
+        b.p1.B_index = it.f.B.data();
+        b.p1.n_B = static_cast<std::int64_t>(it.f.B.size());
+        b.p1.N_index = it.f.N.data();
+        b.p1.N_bound = it.f.Nb.data();
+        b.p1.n_N = static_cast<std::int64_t>(it.f.N.size());
+        b.c2 = it.in2.c.data();
+        b.bound_kind2 = it.in2.kind.data();
+        b.lb2 = it.in2.lb.data();
+        b.ub2 = it.in2.ub.data();
+    }
+    const ellp_opts o = make_opts(max_iter, eng);
+    std::vector<ellp_batch_primal_result> br(run.size());
+    char err[512] = {0};
+    if (ellp_batch_primal_solve(static_cast<std::int64_t>(bi.size()), bi.data(), &o, br.data(), err, sizeof(err)) != ELLP_OPTIMAL) {
+        for (Item *it : run) fallback(*it);  // the call as a whole was refused (options, device)
         return;
     }
-    // the checks after phase 1 (solve(), primal…:42-55), phase 2 on the host
-    seams.clear();
-    for (Item &it : items) {
-        if (it.slot.done) continue;
-        if (it.seam.status == ELLP_ERR_ARG) {  // not taken by the batch kernel (LDS)
+    for (size_t k = 0; k < run.size(); ++k) {
+        Item &it = *run[k];
+        const ellp_batch_primal_result &r = br[k];
+        if (r.status == ELLP_ERR_ARG) {  // not taken by the batch kernel (LDS)
             fallback(it);
             continue;
         }
         SolverResult &res = out[it.slot.out].result;
         settle(out[it.slot.out], it.slot, [&] {
-            const SolutionStatus s1 = to_status(it.seam.status, it.seam.err.c_str());
-            res.iters_phase1 = it.seam.stats.iters;
-            switch (s1) {
-            case SolutionStatus::Optimal: {
-                const double obj = it.p1->obj();
-                if (!(obj > -EPS)) throw EllPPanic("assertion failed: obj > -EPS");
-                if (!(obj < EPS)) {
-                    res.kind = SolverResult::Infeasible;
-                    it.slot.done = true;
+            const SolutionStatus s = to_status(r.status, bi[k].p1.err);  // throws what the phase that ended the solve raised
+            unflatten(it.f, it.p1->point);
+            res.iters_phase1 = r.iters_phase1;
+            if (r.stage == 1) {  // the checks after phase 1 (solve(), primal…:42-55), made on the device
+                switch (s) {
+                case SolutionStatus::Optimal: throw EllPPanic("batch: phase 1 ended Optimal without a verdict");
+                case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; return;  // by status or by objective
+                case SolutionStatus::Unbounded: throw EllPPanic("primal phase 1 should never be unbounded");
+                case SolutionStatus::MaxIter:
+                    res.kind = SolverResult::MaxIter;
+                    res.max_iter_obj = std::numeric_limits<double>::infinity();
                     return;
                 }
-                break;
-            }
-            case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; it.slot.done = true; return;
-            case SolutionStatus::Unbounded: throw EllPPanic("primal phase 1 should never be unbounded");
-            case SolutionStatus::MaxIter:
-                res.kind = SolverResult::MaxIter;
-                res.max_iter_obj = std::numeric_limits<double>::infinity();
-                it.slot.done = true;
                 return;
             }
-            it.p2 = PrimalPhase2::from_phase1(std::move(*it.p1));
+            res.iters_phase2 = r.iters_phase2;
+            PrimalPhase2 p2 = PrimalPhase2::from_phase1(std::move(*it.p1));
             it.p1.reset();
-        });
-        if (it.slot.done) continue;
-        it.seam = Seam{};
-        it.seam.sf = &it.p2->std_form;
-        it.seam.pt = &it.p2->point;
-        seams.push_back(&it.seam);
-    }
-    if (!run_seams(ELLP_ENGINE_PRIMAL, seams, max_iter, eng)) {
-        for (Item &it : items)
-            if (!it.slot.done) fallback(it);
-        return;
-    }
-    for (Item &it : items) {
-        if (it.slot.done) continue;
-        if (it.seam.status == ELLP_ERR_ARG) {
-            fallback(it);
-            continue;
-        }
-        SolverResult &res = out[it.slot.out].result;
-        settle(out[it.slot.out], it.slot, [&] {
-            const SolutionStatus s2 = to_status(it.seam.status, it.seam.err.c_str());
-            res.iters_phase2 = it.seam.stats.iters;
-            switch (s2) {
+            switch (s) {
             case SolutionStatus::Optimal:
                 res.kind = SolverResult::Optimal;
-                res.solution = Solution{std::move(it.p2->std_form), std::move(it.p2->point)};
+                res.solution = Solution{std::move(p2.std_form), std::move(p2.point)};
                 break;
             case SolutionStatus::Infeasible: throw EllPPanic("primal phase 2 should never be infeasible");
             case SolutionStatus::Unbounded: res.kind = SolverResult::Unbounded; break;
             case SolutionStatus::MaxIter:
                 res.kind = SolverResult::MaxIter;
-                res.max_iter_obj = it.p2->obj();
+                res.max_iter_obj = p2.obj();
                 break;
             }
         });

@@ -228,6 +228,51 @@ ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, ellp_batch_it
                                           size_t errbuf_len);
 
 /*
+ * Both phases of many primal solves in one batched call: what PrimalSimplexSolver::solve does between building phase 1 and
+ * reading the result (primal_simplex_solver.rs:32-93), per item, on the kernels and with the workgroup sizes of
+ * ellp_batch_solve_with_initial(ELLP_ENGINE_PRIMAL, ...):
+ *   1. phase 1 on p1, opts.max_iter loop bodies at most;
+ *   2. the checks of solve() (:42-55): a phase-1 status other than Optimal ends the item at stage 1 with that status;
+ *      otherwise obj = c1 . x (summed in index order, as StandardForm::obj): !(obj > -eps) is ELLP_ERR_PANIC ("assertion
+ *      failed: obj > -EPS"), !(obj < eps) is ELLP_INFEASIBLE, both at stage 1;
+ *   3. the hand-off of PrimalPhase2::from_phase1 (primal_problem.rs:263-291): the costs re-gathered from c2 by the current
+ *      index sets, kinds and bounds replaced by bound_kind2 / lb2 / ub2 (n_c entries each), a nonbasic variable whose new
+ *      kind is Free labelled ELLP_NB_FREE, status and counters afresh;
+ *   4. phase 2 with opts.max_iter loop bodies of its own: its status, stage 2.
+ * The workgroup that ends an item's phase 1 does steps 2 to 4 itself, in the same launch: no item waits for another one's
+ * phase 1, and an item goes to the device once.  Every item ends as the two ellp_batch_solve_with_initial calls with the
+ * host's checks and hand-off in between end it, bit for bit.  x, B_index, N_index and N_bound of p1 hold the point of the
+ * phase that ended the solve (at stage 2 with the Free labels).  Options, refusals and chunking are those of
+ * ellp_batch_solve_with_initial (per-item errors in results[i].status and p1.err; every check runs before any HIP call);
+ * the call also returns ELLP_ERR_ARG when results is NULL, when c2, bound_kind2, lb2 or ub2 of an item is NULL, or when a
+ * bound_kind2 entry of an item that passed its own checks is above 4.  A launch gives every running item at most
+ * 16,384 (up to 128 rows) / 4,096 loop bodies, phase 1 and phase 2 together (ELLP_BATCH_LAUNCH_ITERS lowers both); an
+ * item still running is launched again from its device state in whichever phase it is, with the same bits.
+ */
+typedef struct ellp_batch_primal_item {
+    ellp_batch_item p1;         /* the phase-1 seam arrays, as for ellp_batch_solve_with_initial; updated in place */
+    const double *c2;           /* phase 2: n_c costs */
+    const uint8_t *bound_kind2; /*          n_c kinds */
+    const double *lb2, *ub2;    /*          n_c bounds */
+} ellp_batch_primal_item;
+
+typedef struct ellp_batch_primal_result {
+    ellp_status status; /* of the phase that ended the solve, or an error */
+    int32_t stage;      /* 1: ended in or after phase 1; 2: ended in phase 2 */
+    uint64_t iters_phase1, iters_phase2;
+    double obj_phase1;  /* c1.x after phase 1 (NaN if phase 1 did not end Optimal) */
+    double obj;         /* c.x of the phase that ended the solve, as ellp_stats.obj */
+} ellp_batch_primal_result;
+
+ellp_status ellp_batch_primal_solve(int64_t count, ellp_batch_primal_item *items, const ellp_opts *opts,
+                                    ellp_batch_primal_result *results, char *errbuf, size_t errbuf_len);
+
+/* Diagnostics of the calling thread's last ellp_batch_primal_solve that passed the checks of the call: out4[0] launch rounds
+ * (summed over the chunks), [1] bytes uploaded by the last chunk (the items, then the argument lists of every round),
+ * [2] bytes uploaded by all chunks, [3] chunks. */
+void ellp_batch_primal_info(uint64_t *out4);
+
+/*
  * Resident form of the same path: the tableau stays in HBM between calls, so a caller
  * (bench.py, a phase-1 -> phase-2 hand-off, a windowed parity test) can run the loop in
  * slices without re-uploading.  create = unpack + gather (primal…:99-155); run = the loop for
