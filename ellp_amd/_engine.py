@@ -162,6 +162,10 @@ def lib():
     L.ellp_shard_pack_doubles.argtypes = [C.c_int64]
     L.ellp_hip_lu_transposed.restype = C.c_int
     L.ellp_hip_lu_transposed.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+    L.ellp_hip_lu_rows.restype = C.c_int
+    L.ellp_hip_lu_rows.argtypes = [C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]
+    L.ellp_hip_lu_rows_last_ms.restype = C.c_double
+    L.ellp_hip_lu_rows_last_ms.argtypes = []
     L.ellp_engine_shard_info.restype = C.c_int
     L.ellp_engine_shard_info.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     _lib = L
@@ -195,6 +199,28 @@ def lu_transposed(A, device=-1):
     if s != OPTIMAL:
         raise EllpHipError(s, err.value.decode())
     return piv, ud
+
+
+def lu_rows(M, blocked=True, device=-1):
+    """LU with partial pivoting of a square matrix by rows on the device, as the exact loop above 1,024 rows factors the basis
+    (ellp_hip_lu_rows): blocked (panels of 16 columns) or the unblocked form, the same bytes either way.
+    Returns (factors, pivots, U_ii); lu_rows_last_ms() is the device time of the factorisation alone."""
+    M = np.ascontiguousarray(M, dtype=np.float64)
+    if M.ndim != 2 or M.shape[0] != M.shape[1]:
+        raise ValueError("lu_rows needs a square matrix")
+    m = M.shape[0]
+    fac = np.zeros((m, m), dtype=np.float64)
+    piv = np.zeros(m, dtype=np.int64)
+    ud = np.zeros(m, dtype=np.float64)
+    err = C.create_string_buffer(512)
+    s = lib().ellp_hip_lu_rows(m, _p(M), 1 if blocked else 0, _p(fac), _p(piv), _p(ud), int(device), err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    return fac, piv, ud
+
+
+def lu_rows_last_ms():
+    return float(lib().ellp_hip_lu_rows_last_ms())
 
 
 def shard_pack_doubles(ld):

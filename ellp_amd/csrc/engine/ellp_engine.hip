@@ -2978,6 +2978,7 @@ struct ellp_engine {
     bool small = false;      // run() uses k_small
     bool w_valid = true;     // the explicit inverse W (not kept by k_small) matches A_B
     bool exact_large_only = false;  // after a redo above 1,024 rows: every loop body on a fresh LU (run_exact_large), until the next phase
+    bool exact_large_always = false;  // pipeline 3 above 1,024 rows: that loop for good, from the first slice on and in every phase
     size_t small_lds = 0;
     int pp_P = 0;            // partial pricing: number of segments (<= 1: off)
     int64_t pp_S = 0;        // positions per segment
@@ -3127,7 +3128,7 @@ hipError_t dmalloc(ellp_engine *e, T **p, size_t count) {
 // `neu` (a hipMalloc of its own) takes the place of the engine array `old`
 inline void replace_alloc(ellp_engine *e, void *old, void *neu) {
     for (auto &p : e->allocs)
-        if (p == old) {
+        if (p == old && old != static_cast<void *>(e->slab)) {  // the slab's first tenant has the slab's address: not its to free
             (void)hipFree(p);
             p = neu;
             return;
@@ -4578,6 +4579,11 @@ static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_
         if (const char *v = getenv("ELLP_GUARD_ABS"); v && v[0]) e->guard_abs = atof(v);  // diagnostics
         if (const char *v = getenv("ELLP_EXACT_K"); v && v[0] && atoi(v) > 0) e->exact_K = atoi(v);  // diagnostics
     }
+    // pipeline 3 above 1,024 rows, under the condition exact_loop() sets below them: the LU-per-iteration loop over all CUs
+    // (run_exact_large) is the engine — no hybrid, certificate, guard or snapshot: the loop is its own certificate.  The
+    // explicit inverse is built, updated along and rebuilt at the end of a solve, so the phase hand-offs and read_point work.
+    if (!e->small && e->opts.pipeline == 3 && m > MID_MAX_M && m <= 8192 && n_N > 0 && e->pp_P <= 1 && !e->se)
+        e->exact_large_always = e->exact_large_only = true;
     // two launches per primal iteration from m = 1024 (ellp_lagged.inc), or on request
     {
         const int pl = e->opts.pipeline;
@@ -5034,8 +5040,9 @@ static hipError_t exact_workspace(ellp_engine *e) {
 }
 
 // "certify or redo" above 1,024 rows: after a redo every loop body runs on a fresh LU (ellp_engine::exact_large_only) — the
-// reference's LU-per-iteration loop on all CUs instead of in one workgroup: an LU (2 m launches) and two (primal) / three (dual) solves per iteration,
-// 20-40 ms at 1,000-2,000 rows; the explicit inverse is still updated along (a later phase goes back to the fast loop).
+// reference's LU-per-iteration loop on all CUs instead of in one workgroup: a blocked LU (2 ceil(m / 16) launches, ellp_lu.hip) and
+// two (primal) / three (dual) solves per iteration; the explicit inverse is still updated along (a later phase goes back to
+// the fast loop).  With pipeline 3 (ellp_engine::exact_large_always) this loop is the engine, from the first slice on.
 static ellp_status run_exact_large(ellp_engine *e, uint64_t max_iters, char *errbuf, size_t errlen) {
     HIPCHK(exact_workspace(e));
     HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
@@ -5715,6 +5722,10 @@ ellp_status ellp_engine_set_shard(ellp_engine *e, int rank, int world, void *exc
         set_err(errbuf, errlen, "bad rank/world");
         return ELLP_ERR_ARG;
     }
+    if (world > 1 && e->exact_large_always) {
+        set_err(errbuf, errlen, "pipeline 3 above 1,024 rows runs the LU-per-iteration loop on one GPU: it cannot be sharded");
+        return ELLP_ERR_ARG;
+    }
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     {
@@ -5769,6 +5780,10 @@ ellp_status ellp_engine_set_stream(ellp_engine *e, void *hip_stream) {
 ellp_status ellp_engine_step(ellp_engine *e, int phase, char *errbuf, size_t errlen) {
     if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
     if (!e) return ELLP_ERR_ARG;
+    if (e->exact_large_always) {
+        set_err(errbuf, errlen, "pipeline 3 above 1,024 rows runs the LU-per-iteration loop: ellp_engine_step drives the explicit-inverse engine only");
+        return ELLP_ERR_ARG;
+    }
     if (phase == 2) {  // second half of this iteration + first half of the next, one host call
         const ellp_status s1 = ellp_engine_step(e, 1, errbuf, errlen);
         if (s1 != ELLP_OPTIMAL) return s1;
@@ -5919,7 +5934,7 @@ ellp_status ellp_engine_rephase(ellp_engine *e, const double *c, const uint8_t *
     e->enqueued = 0;
     e->iters_seen = 0;
     e->snap.valid = false;  // a new phase starts here
-    e->exact_large_only = false;  // ... in the fast loop again
+    e->exact_large_only = e->exact_large_always;  // ... in the fast loop again, unless the caller chose the exact loop (pipeline 3)
     return ELLP_OPTIMAL;
 }
 
@@ -5937,6 +5952,22 @@ static ellp_status dual_point_from_inverse(ellp_engine *e, const double *c_dev, 
     const bool from_lu = e->hybrid && e->LUa != nullptr && e->world == 1;
     if (from_lu) {
         HIPCHK(launch_mid(e, 0, 2));
+    } else if (e->exact_large_always) {
+        // the exact loop above 1,024 rows: y = B^-T c_B from a fresh LU of the basis as well (x_B follows in every loop body)
+        HIPCHK(exact_workspace(e));
+        HIPCHK(hipMemsetAsync(e->ex_fail, 0, sizeof(int), e->stream));
+        hipLaunchKernelGGL(k_rows_from_cols, dim3((unsigned)((m + 31) / 32), (unsigned)((m + 31) / 32)), dim3(256), 0, e->stream, e->A_B, e->luw.M, m, ld);
+        ellp_lu_rows_factor(&e->luw, e->stream);
+        hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), 2 * sizeof(double) * (size_t)m, e->stream, e->luw.M, e->luw.piv, m, e->c_B, e->ex_sol, 1, e->ex_fail);
+        int failed = 0;
+        HIPCHK(hipMemcpyAsync(&failed, e->ex_fail, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (failed) {
+            set_err(errbuf, errlen, "unwrap() on None: the basis is exactly singular");
+            return ELLP_ERR_PANIC;
+        }
+        HIPCHK(hipMemsetAsync(e->y, 0, sizeof(double) * (size_t)ld, e->stream));
+        HIPCHK(hipMemcpyAsync(e->y, e->ex_sol, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, e->stream));
     } else {
         launch_btran(e);  // into e->u (a dual engine has no other use for it)
         HIPCHK(hipMemcpyAsync(e->y, e->u, sizeof(double) * (size_t)ld, hipMemcpyDeviceToDevice, e->stream));
@@ -6072,7 +6103,7 @@ ellp_status ellp_engine_dual_rephase(ellp_engine *e, const double *c, const doub
     e->enqueued = 0;
     e->iters_seen = 0;
     e->snap.valid = false;  // a new phase starts here
-    e->exact_large_only = false;  // ... in the fast loop again
+    e->exact_large_only = e->exact_large_always;  // ... in the fast loop again, unless the caller chose the exact loop (pipeline 3)
     {
         bool box = true;
         for (int64_t i = 0; i < n_c && box; ++i) box = bound_kind[i] == ELLP_BOUND_TWOSIDED || bound_kind[i] == ELLP_BOUND_FIXED;
@@ -6192,6 +6223,10 @@ ellp_status ellp_engine_comm_init(ellp_engine *e, const char *rccl_path, const v
                                   char *errbuf, size_t errlen) {
     if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
     if (!e || !id || world < 1 || rank < 0 || rank >= world) return ELLP_ERR_ARG;
+    if (e->exact_large_always) {
+        set_err(errbuf, errlen, "pipeline 3 above 1,024 rows runs the LU-per-iteration loop on one GPU: it cannot be sharded");
+        return ELLP_ERR_ARG;
+    }
     const RcclApi *api = load_rccl(rccl_path, errbuf, errlen);
     if (!api) return ELLP_ERR_DEVICE;
     HIPCHK(hipSetDevice(e->device));
@@ -6224,6 +6259,10 @@ ellp_status ellp_engine_shard_columns(ellp_engine *e, int rank, int world, char 
     if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
     if (!e || world < 1 || rank < 0 || rank >= world) return ELLP_ERR_ARG;
     if (errbuf && errlen) errbuf[0] = 0;
+    if (e->exact_large_always) {
+        set_err(errbuf, errlen, "pipeline 3 above 1,024 rows runs the LU-per-iteration loop on one GPU: it cannot be sharded");
+        return ELLP_ERR_ARG;
+    }
     if (e->kind != ELLP_ENGINE_PRIMAL) {
         set_err(errbuf, errlen, "column-sharded storage is implemented for the primal loop");
         return ELLP_ERR_ARG;

@@ -3,15 +3,16 @@
 // decides it taken from a FRESH LU factorisation of the basis, as the reference takes it every iteration
 // (primal_simplex_solver.rs:173-189,289-300,404-406; dual_simplex_solver.rs:241-253,281-284,294) —
 //   * the LU: partial pivoting, first maximum, multipliers a (1/diag), the oracle's lu_factor_inplace number for number
-//     (ellp_lu.hip's right-looking kernels on a copy of A_B stored by rows; two launches per step, all CUs);
+//     (ellp_lu.hip's blocked right-looking kernels on a copy of A_B stored by rows; two launches per 16-column panel);
 //   * the solves with it: one workgroup each, the vector in LDS, one barrier pair per step (k_lu_solve);
 //   * everything else — pricing, the entering fold, the ratio test, the updates — by the engine's own bandwidth kernels,
 //     fed the EXACT u (or rho) and the EXACT d = B^-1 a_q instead of the explicit inverse's.
 // A structural zero of B^-1 a_q is an exact zero again (the elimination never touches it), which is what the explicit
 // inverse cannot deliver on ill-conditioned bases.  Used when the explicit-inverse loop reports a terminal status: if this
 // iteration ends the same way, the status is certified; if it pivots, the pivot is made (with the exact d) and the loop
-// goes on.  Cost: the LU (0.03 s at m = 2000, 0.1 s at m = 4000) + two (primal) or three (dual) solves of m steps — paid once
-// per phase by the certificate, per iteration by a repeated phase (run_exact_large, DESIGN.md §3.1d).
+// goes on.  Cost: the LU (5.5 ms at m = 1100, 12 ms at m = 1850) + two (primal) or three (dual) solves of m steps — paid once
+// per phase by the certificate, per iteration by a repeated phase and by an engine made with pipeline = 3 above 1,024 rows
+// (run_exact_large, DESIGN.md §3.1d).
 //
 // Included inside the anonymous namespace of ellp_engine.hip.
 

@@ -23,6 +23,9 @@
 // took less than 110 us however little there was to eliminate.  A kernel boundary does that write-back once.)
 // Right-looking and unblocked: the whole trailing matrix is read and written once per step (about
 // 16·nv·m²/2 bytes in all: 0.3 TB at config 3's shape); a blocked variant would divide that by the panel width.
+//
+// The SQUARE device-resident matrix by rows (ellp_lu_rows_factor, below the rectangular kernels) has that blocked variant:
+// panels of LUP_W = 16 columns, two launches per panel instead of two per column, the same bits.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -186,6 +189,297 @@ __global__ __launch_bounds__(1024) void k_lut_fold(const double *M, int64_t m, i
     }
 }
 
+// ---- blocked form for a square matrix by rows: panels of LUP_W columns.  An entry (r, k) still receives the updates of the
+// steps i = 0 .. min(r, k) - 1 in ascending i, each a separately rounded multiply and add, skipped for a zero -M[i,k] and for
+// a skipped (zero pivot) step — so every stored number is the unblocked form's.
+//   panel kernel   ONE workgroup: columns j0 .. j0+w-1 of the rows j0 .. m-1; per column the pivot search (first maximum,
+//                  k_lut_step's NaN rule), the exchange inside the panel, the scaling and the update of the panel's later
+//                  columns; piv / udiag recorded.  No synchronisation across workgroups (see the header).  A thread keeps its
+//                  rows' 16 entries in registers up to 2 rows per thread (k_lup_panel_reg<1>, <2>: up to 1,024 / 2,048 rows
+//                  left); above that the rows stay in global memory, which is this CU's L1/L2 (k_lup_panel_mem).
+//   update kernel  one workgroup per strip of 16 columns outside the panel, all rows: the panel's exchanges in step order
+//                  (staged in LDS — everything a column needs lies in that column, so strips never wait for each other),
+//                  right of the panel the panel's 16 rows finished (a chain of up to 15 steps per entry) and the trailing
+//                  rows updated, each entry in a register through its 16 multiply-adds.
+constexpr int LUP_W = 16;
+constexpr int LUP_NT = 1024;
+
+struct LupBest {
+    double v;
+    int r;
+};
+// workgroup-wide first maximum of (v, r); every thread returns it.  s_v / s_r: 16 entries each
+__device__ __forceinline__ LupBest lup_reduce(double bv, int br, double *s_v, int *s_r) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(bv, o);
+        const int orr = __shfl_xor(br, o);
+        if (lu_better(ov, orr, bv, br)) {
+            bv = ov;
+            br = orr;
+        }
+    }
+    if (lane == 0) {
+        s_v[wave] = bv;
+        s_r[wave] = br;
+    }
+    __syncthreads();
+    bv = s_v[0];
+    br = s_r[0];
+#pragma unroll
+    for (int w = 1; w < LUP_NT / 64; ++w)
+        if (lu_better(s_v[w], s_r[w], bv, br)) {
+            bv = s_v[w];
+            br = s_r[w];
+        }
+    return LupBest{bv, br};
+}
+__device__ __forceinline__ double lup_key(double x, bool diagonal) {
+    double v = fabs(x);
+    if (v != v) v = diagonal ? INFINITY : -1.0;  // k_lut_step's rule: `v > best` is false for a NaN, only the diagonal can carry one
+    return v;
+}
+
+// one row of a thread of k_lup_panel_reg: its 16 panel entries in registers (every index is a constant once the loops are
+// unrolled: nothing may reach scratch memory)
+struct LupRow {
+    double a[LUP_W];
+    int row;  // -1: none
+    __device__ __forceinline__ void load(const double *M, int64_t m, int64_t j0, int w, int64_t r) {
+        row = r < m ? (int)r : -1;
+#pragma unroll
+        for (int c = 0; c < LUP_W; ++c) a[c] = (r < m && c < w) ? M[r * m + j0 + c] : 0.0;
+    }
+    __device__ __forceinline__ void store(double *M, int64_t m, int64_t j0, int w) const {
+        if (row < 0) return;
+#pragma unroll
+        for (int c = 0; c < LUP_W; ++c)
+            if (c < w) M[(int64_t)row * m + j0 + c] = a[c];
+    }
+    __device__ __forceinline__ void candidate(int c, int i, double &bv, int &br) const {
+        if (row >= i) {
+            const double v = lup_key(a[c], row == i);
+            if (br < 0 || v > bv) {
+                bv = v;
+                br = row;
+            }
+        }
+    }
+    __device__ __forceinline__ void publish(int p, int i, double *s_prow, double *s_irow) const {
+        if (row == p) {
+#pragma unroll
+            for (int q = 0; q < LUP_W; ++q) s_prow[q] = a[q];
+        }
+        if (row == i) {
+#pragma unroll
+            for (int q = 0; q < LUP_W; ++q) s_irow[q] = a[q];
+        }
+    }
+    __device__ __forceinline__ void eliminate(int c, int p, int i, double inv_diag, const double *s_prow, const double *s_irow) {
+        if (p != i && row == p) {
+#pragma unroll
+            for (int q = 0; q < LUP_W; ++q) a[q] = s_irow[q];
+        } else if (p != i && row == i) {
+#pragma unroll
+            for (int q = 0; q < LUP_W; ++q) a[q] = s_prow[q];
+        }
+        if (row > i) {
+            const double l = __dmul_rn(a[c], inv_diag);
+            a[c] = l;
+#pragma unroll
+            for (int q = 0; q < LUP_W; ++q)
+                if (q > c) {
+                    const double f = -s_prow[q];
+                    if (f != 0.0) a[q] = __dadd_rn(__dmul_rn(f, l), a[q]);
+                }
+        }
+    }
+};
+
+// rows j0 .. m-1 (at most RPT * 1024 of them, RPT = 1 or 2), thread t keeps rows j0 + t and j0 + t + 1024 in registers
+template <int RPT>
+__global__ __launch_bounds__(LUP_NT) void k_lup_panel_reg(double *M, int64_t m, int64_t j0, int64_t *piv, double *udiag) {
+    __shared__ double s_v[LUP_NT / 64];
+    __shared__ int s_r[LUP_NT / 64];
+    __shared__ double s_prow[LUP_W], s_irow[LUP_W];
+    const int tid = threadIdx.x;
+    const int w = (int)(m - j0 < LUP_W ? m - j0 : LUP_W);
+    LupRow r0, r1;
+    r0.load(M, m, j0, w, j0 + tid);
+    if (RPT > 1) r1.load(M, m, j0, w, j0 + tid + LUP_NT);
+#pragma unroll
+    for (int c = 0; c < LUP_W; ++c) {
+        if (c < w) {
+            const int i = (int)j0 + c;
+            double bv = -1.0;
+            int br = -1;
+            r0.candidate(c, i, bv, br);
+            if (RPT > 1) r1.candidate(c, i, bv, br);
+            const int p = lup_reduce(bv, br, s_v, s_r).r;  // >= i: row i itself is always a candidate
+            r0.publish(p, i, s_prow, s_irow);
+            if (RPT > 1) r1.publish(p, i, s_prow, s_irow);
+            __syncthreads();
+            const double diag = s_prow[c];
+            if (tid == 0) {
+                piv[i] = diag == 0.0 ? i : p;  // a skipped column appends no transposition (dense.h)
+                udiag[i] = diag;
+            }
+            if (diag != 0.0) {
+                const double inv_diag = 1.0 / diag;
+                r0.eliminate(c, p, i, inv_diag, s_prow, s_irow);
+                if (RPT > 1) r1.eliminate(c, p, i, inv_diag, s_prow, s_irow);
+            }
+        }
+    }
+    r0.store(M, m, j0, w);
+    if (RPT > 1) r1.store(M, m, j0, w);
+}
+
+// any number of rows: thread t owns rows j0 + t + 1024 k, which stay in memory
+__global__ __launch_bounds__(LUP_NT) void k_lup_panel_mem(double *M, int64_t m, int64_t j0, int64_t *piv, double *udiag) {
+    __shared__ double s_v[LUP_NT / 64];
+    __shared__ int s_r[LUP_NT / 64];
+    __shared__ double s_prow[LUP_W], s_irow[LUP_W];
+    const int tid = threadIdx.x;
+    const int w = (int)(m - j0 < LUP_W ? m - j0 : LUP_W);
+    for (int c = 0; c < w; ++c) {
+        const int64_t i = j0 + c;
+        double bv = -1.0;
+        int br = -1;
+        for (int64_t r = j0 + tid; r < m; r += LUP_NT)
+            if (r >= i) {
+                const double v = lup_key(M[r * m + i], r == i);
+                if (br < 0 || v > bv) {
+                    bv = v;
+                    br = (int)r;
+                }
+            }
+        const int64_t p = lup_reduce(bv, br, s_v, s_r).r;
+        if (tid < LUP_W) {
+            s_prow[tid] = tid < w ? M[p * m + j0 + tid] : 0.0;
+            s_irow[tid] = tid < w ? M[i * m + j0 + tid] : 0.0;
+        }
+        __syncthreads();
+        const double diag = s_prow[c];
+        if (tid == 0) {
+            piv[i] = diag == 0.0 ? i : p;
+            udiag[i] = diag;
+        }
+        if (diag != 0.0) {
+            const double inv_diag = 1.0 / diag;
+            if (p != i && tid < w) M[i * m + j0 + tid] = s_prow[tid];  // position i is read by nobody in this step
+            for (int64_t r = j0 + tid; r < m; r += LUP_NT)
+                if (r > i) {
+                    double *dst = M + r * m + j0;
+                    const bool moved = r == p;  // this position receives the row the pivot displaced (its old copy: s_irow)
+                    const double *src = moved ? s_irow : dst;
+                    const double l = __dmul_rn(src[c], inv_diag);
+                    if (moved)
+                        for (int q = 0; q < c; ++q) dst[q] = s_irow[q];
+                    dst[c] = l;
+                    for (int q = c + 1; q < w; ++q) {
+                        const double f = -s_prow[q];
+                        double val = src[q];
+                        if (f != 0.0) val = __dadd_rn(__dmul_rn(f, l), val);
+                        if (f != 0.0 || moved) dst[q] = val;
+                    }
+                }
+        }
+        // the next column's search reads what this step wrote: rows keep their threads; s_prow / s_irow are loaded from rows
+        // other threads wrote only behind the barrier inside lup_reduce
+    }
+}
+
+// strip s = columns 16 s .. 16 s + 15, all rows; the strip of the panel itself has nothing to do
+__global__ __launch_bounds__(LUP_NT) void k_lup_update(double *M, int64_t m, int64_t j0, const int64_t *piv, const double *udiag) {
+    __shared__ double s_val[2 * LUP_W][LUP_W];  // slot c: position j0 + c; slot 16 + c: the position step c exchanged with, if below the panel
+    __shared__ double s_L[LUP_W][LUP_W];        // the panel's multipliers among its own 16 rows
+    __shared__ int64_t s_pos[2 * LUP_W];        // -1: slot unused
+    __shared__ int s_slot[LUP_W];               // the slot step c exchanges slot c with (c: no exchange)
+    __shared__ int s_skip[LUP_W];
+    const int tid = threadIdx.x;
+    const int64_t k0 = (int64_t)blockIdx.x * LUP_W;
+    if (k0 == j0) return;
+    const bool right = k0 > j0;  // then the panel is a full one
+    const int w = (int)(m - j0 < LUP_W ? m - j0 : LUP_W);
+    if (tid == 0) {
+        for (int c = 0; c < 2 * LUP_W; ++c) s_pos[c] = c < w ? j0 + c : -1;
+        for (int c = 0; c < LUP_W; ++c) {
+            int slot = c;
+            if (c < w) {
+                const int64_t p = piv[j0 + c];
+                if (p < j0 + w) slot = (int)(p - j0);
+                else {
+                    slot = LUP_W + c;
+                    for (int c2 = 0; c2 < c; ++c2)
+                        if (s_pos[LUP_W + c2] == p) slot = LUP_W + c2;
+                    s_pos[slot] = p;
+                }
+            }
+            s_slot[c] = slot;
+            s_skip[c] = c < w ? (udiag[j0 + c] == 0.0) : 1;
+        }
+    } else if (right && tid >= 256 && tid < 256 + LUP_W * LUP_W) {
+        const int c = (tid - 256) >> 4, i = (tid - 256) & 15;
+        s_L[c][i] = i < c ? M[(j0 + c) * m + j0 + i] : 0.0;
+    }
+    __syncthreads();
+    const int sl = tid >> 4, cl = tid & 15;
+    const int64_t k = k0 + cl;
+    const int64_t pos = tid < 2 * LUP_W * LUP_W ? s_pos[sl] : -1;
+    if (pos >= 0 && k < m) s_val[sl][cl] = M[pos * m + k];
+    __syncthreads();
+    if (tid < LUP_W && k < m) {
+        for (int c = 0; c < w; ++c) {
+            const int s = s_slot[c];
+            if (s != c) {
+                const double t = s_val[c][cl];
+                s_val[c][cl] = s_val[s][cl];
+                s_val[s][cl] = t;
+            }
+        }
+        if (right)
+            for (int c = 1; c < LUP_W; ++c) {
+                double val = s_val[c][cl];
+                for (int i = 0; i < c; ++i) {
+                    const double f = s_skip[i] ? 0.0 : -s_val[i][cl];
+                    if (f != 0.0) val = __dadd_rn(__dmul_rn(f, s_L[c][i]), val);
+                }
+                s_val[c][cl] = val;
+            }
+    }
+    __syncthreads();
+    if (pos >= 0 && k < m) M[pos * m + k] = s_val[sl][cl];
+    if (!right) return;
+    __syncthreads();  // the trailing rows an exchange has moved are read below by other threads
+    if (k >= m) return;
+    double f[LUP_W];
+#pragma unroll
+    for (int i = 0; i < LUP_W; ++i) f[i] = s_skip[i] ? 0.0 : -s_val[i][cl];
+    for (int64_t r = j0 + LUP_W + sl; r < m; r += 2 * (LUP_NT / LUP_W)) {
+        const int64_t r2 = r + LUP_NT / LUP_W;
+        const bool two = r2 < m;
+        const int64_t rb = two ? r2 : r;
+        const double *la = M + r * m + j0, *lb = M + rb * m + j0;
+        double va = M[r * m + k], vb = M[rb * m + k];
+        double l1[LUP_W], l2[LUP_W];
+#pragma unroll
+        for (int i = 0; i < LUP_W; ++i) {
+            l1[i] = la[i];
+            l2[i] = lb[i];
+        }
+#pragma unroll
+        for (int i = 0; i < LUP_W; ++i)
+            if (f[i] != 0.0) {
+                va = __dadd_rn(__dmul_rn(f[i], l1[i]), va);
+                vb = __dadd_rn(__dmul_rn(f[i], l2[i]), vb);
+            }
+        M[r * m + k] = va;
+        if (two) M[r2 * m + k] = vb;
+    }
+}
+
 void set_err(char *errbuf, size_t len, const char *msg, hipError_t e) {
     if (errbuf && len) snprintf(errbuf, len, "%s: %s", msg, hipGetErrorString(e));
 }
@@ -217,6 +511,17 @@ void ellp_lu_rows_free(EllpLuWork *w) {
 }
 void ellp_lu_rows_factor(EllpLuWork *w, hipStream_t stream) {
     const int64_t m = w->m;
+    const unsigned strips = (unsigned)((m + LUP_W - 1) / LUP_W);
+    for (int64_t j0 = 0; j0 < m; j0 += LUP_W) {
+        const int64_t rows = m - j0;
+        if (rows <= LUP_NT) hipLaunchKernelGGL(k_lup_panel_reg<1>, dim3(1), dim3(LUP_NT), 0, stream, w->M, m, j0, w->piv, w->udiag);
+        else if (rows <= 2 * LUP_NT) hipLaunchKernelGGL(k_lup_panel_reg<2>, dim3(1), dim3(LUP_NT), 0, stream, w->M, m, j0, w->piv, w->udiag);
+        else hipLaunchKernelGGL(k_lup_panel_mem, dim3(1), dim3(LUP_NT), 0, stream, w->M, m, j0, w->piv, w->udiag);
+        if (strips > 1) hipLaunchKernelGGL(k_lup_update, dim3(strips), dim3(LUP_NT), 0, stream, w->M, m, j0, w->piv, w->udiag);
+    }
+}
+void ellp_lu_rows_factor_unblocked(EllpLuWork *w, hipStream_t stream) {
+    const int64_t m = w->m;
     (void)hipMemsetAsync(w->st, 0, sizeof(LuState), stream);
     for (int64_t i = -1; i < m; ++i) {
         const int64_t rows = m - i - 1;
@@ -227,6 +532,72 @@ void ellp_lu_rows_factor(EllpLuWork *w, hipStream_t stream) {
             hipLaunchKernelGGL(k_lut_fold, dim3(1), dim3(1024), 0, stream, w->M, m, i + 1, static_cast<const LuCand *>(w->cands), grid, w->prow,
                                w->irow, static_cast<LuState *>(w->st), w->piv, w->udiag);
     }
+}
+
+static double g_lu_rows_last_ms = 0.0;
+extern "C" double ellp_hip_lu_rows_last_ms(void) { return g_lu_rows_last_ms; }
+
+extern "C" ellp_status ellp_hip_lu_rows(int64_t m, const double *M_in, int variant, double *factors_out, int64_t *pivot_out,
+                                        double *udiag_out, int device, char *errbuf, size_t errlen) {
+    if (errbuf && errlen) errbuf[0] = 0;
+    if (m <= 0) {
+        if (errbuf && errlen) snprintf(errbuf, errlen, "ellp_hip_lu_rows: m = %lld, a square matrix of at least one row is needed", (long long)m);
+        return ELLP_ERR_ARG;
+    }
+    if (!M_in || !factors_out || !pivot_out || !udiag_out) {
+        if (errbuf && errlen) snprintf(errbuf, errlen, "ellp_hip_lu_rows: NULL pointer (M_in, factors_out, pivot_out and udiag_out are all needed)");
+        return ELLP_ERR_ARG;
+    }
+    if (variant != 0 && variant != 1) {
+        if (errbuf && errlen) snprintf(errbuf, errlen, "ellp_hip_lu_rows: unknown variant %d (0 = unblocked, 1 = blocked)", variant);
+        return ELLP_ERR_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        if (errbuf && errlen) snprintf(errbuf, errlen, "no HIP device available");
+        return ELLP_ERR_DEVICE;
+    }
+    if (device >= 0 && hipSetDevice(device) != hipSuccess) return ELLP_ERR_DEVICE;
+    EllpLuWork w;
+    memset(&w, 0, sizeof(w));
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipError_t rc = hipSuccess;
+    auto cleanup = [&] {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        ellp_lu_rows_free(&w);
+    };
+#define LCHK(expr)                                      \
+    do {                                                \
+        rc = (expr);                                    \
+        if (rc != hipSuccess) {                         \
+            set_err(errbuf, errlen, #expr, rc);         \
+            cleanup();                                  \
+            return ELLP_ERR_DEVICE;                     \
+        }                                               \
+    } while (0)
+    const size_t bytes = sizeof(double) * (size_t)(m * m);
+    LCHK(ellp_lu_rows_alloc(&w, m));
+    LCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    LCHK(hipEventCreate(&ev0));
+    LCHK(hipEventCreate(&ev1));
+    LCHK(hipMemcpyAsync(w.M, M_in, bytes, hipMemcpyHostToDevice, stream));
+    LCHK(hipEventRecord(ev0, stream));
+    if (variant == 1) ellp_lu_rows_factor(&w, stream);
+    else ellp_lu_rows_factor_unblocked(&w, stream);
+    LCHK(hipEventRecord(ev1, stream));
+    LCHK(hipGetLastError());
+    LCHK(hipMemcpyAsync(factors_out, w.M, bytes, hipMemcpyDeviceToHost, stream));
+    LCHK(hipMemcpyAsync(pivot_out, w.piv, sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToHost, stream));
+    LCHK(hipMemcpyAsync(udiag_out, w.udiag, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, stream));
+    LCHK(hipStreamSynchronize(stream));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) g_lu_rows_last_ms = (double)ms;
+#undef LCHK
+    cleanup();
+    return ELLP_OPTIMAL;
 }
 
 extern "C" ellp_status ellp_hip_lu_transposed(int64_t m, int64_t nv, const double *A, int64_t *pivot_out,

@@ -15,5 +15,8 @@ struct EllpLuWork {
 };
 hipError_t ellp_lu_rows_alloc(EllpLuWork *w, int64_t m);
 void ellp_lu_rows_free(EllpLuWork *w);
-void ellp_lu_rows_factor(EllpLuWork *w, hipStream_t stream);  // enqueues 2 m launches; no synchronisation
+// blocked, panels of 16 columns: enqueues 2 ceil(m / 16) launches; no synchronisation.  M, piv and udiag end byte for byte as
+// the unblocked form leaves them
+void ellp_lu_rows_factor(EllpLuWork *w, hipStream_t stream);
+void ellp_lu_rows_factor_unblocked(EllpLuWork *w, hipStream_t stream);  // k_lut_step / k_lut_fold: 2 m launches
 #endif

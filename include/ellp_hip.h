@@ -82,8 +82,14 @@ typedef struct ellp_opts {
                                 1 = three launches (pricing | FTRAN | eta update), 2 = two bandwidth
                                 passes (primal: pricing | eta update of the previous pivot fused with this iteration's
                                 FTRAN; dual: pricing | FTRAN fused with this iteration's eta update, + a closing block),
-                                3 = the whole loop in one persistent workgroup with an LU per iteration (m <= 1024: factors in
-                                LDS up to 128 rows, in global memory above) */
+                                3 = the reference's loop with an LU of the basis per iteration, the oracle's pivots: up to 1,024
+                                rows the whole loop in one persistent workgroup (factors in LDS up to 128 rows, in global
+                                memory above; bit for bit the oracle); from 1,025 to 8,192 rows, with full pricing
+                                (partial_segments <= 1), every loop body over all CUs — a blocked LU of the basis, the
+                                triangular solves, the bandwidth kernels fed the exact vectors (the oracle's
+                                status, iteration count and basis, values to 1e-11) — with no hybrid, certificate or redo: the
+                                loop is its own certificate.  Such an engine keeps a resident inverse for the phase hand-offs
+                                and refuses ellp_engine_step and sharding (ELLP_ERR_ARG) */
     int32_t trace_len;       /* > 0: keep the objective after each of the last `trace_len` iterations in a ring buffer on
                                 the device (ellp_engine_read_trace) — what the reference's `debug!("{iter} | {obj}")` line
                                 (primal…:161, dual…:189) prints; off by default, as the reference's logging is */
@@ -537,6 +543,20 @@ ellp_status ellp_hip_qr_transposed(int64_t m, int64_t nv, const double *A, int64
  * device < 0: current device. */
 ellp_status ellp_hip_lu_transposed(int64_t m, int64_t nv, const double *A, int64_t *pivot_out, double *udiag_out,
                                    int device, char *errbuf, size_t errbuf_len);
+
+/*
+ * The same factorisation of a SQUARE matrix stored by rows (row r at M_in + r * m, host memory), as the LU-per-iteration loop
+ * above 1,024 rows takes it of the basis every iteration: uploaded, factored, read back.  variant 0: the
+ * unblocked form, two launches per column; variant 1: the blocked form the engine uses, panels of 16 columns, two launches
+ * per panel.  factors_out (m x m by rows): L's multipliers below the diagonal, U on and above, rows in pivoted order;
+ * pivot_out[i] = the row exchanged with row i at step i (i itself: none, also for a skipped zero column); udiag_out[i] = U_ii.
+ * Both variants leave byte for byte what the host loop of ellp_amd/csrc/host/dense.h (LU) leaves.  m <= 0, a NULL pointer or
+ * an unknown variant: ELLP_ERR_ARG with a message, before any HIP call.  device < 0: current device.
+ * ellp_hip_lu_rows_last_ms: device time of the factorisation alone in the last successful call (measurements; not thread safe).
+ */
+ellp_status ellp_hip_lu_rows(int64_t m, const double *M_in, int variant, double *factors_out, int64_t *pivot_out,
+                             double *udiag_out, int device, char *errbuf, size_t errbuf_len);
+double ellp_hip_lu_rows_last_ms(void);
 
 #ifdef __cplusplus
 }
