@@ -47,19 +47,6 @@ struct DualFuArgs {
     double guard_abs;  // > 0: a pivot with |alpha_r| < guard_abs is refused (ST_NEED_EXACT)             // ELLP_FLAG_DUAL_MAX_VIOLATION: a block's record is its row of largest violation
 };
 
-// dual_violation (dual…:200-236) on values in hand
-__device__ __forceinline__ bool dual_violation_v(double xi, int k, double lbi, double ubi, double eps, double *delta, int *side) {
-    if (k == ELLP_BOUND_LOWER) {
-        if (xi < lbi - eps) { *delta = xi - lbi; *side = ELLP_NB_LOWER; return true; }
-    } else if (k == ELLP_BOUND_UPPER) {
-        if (xi > ubi + eps) { *delta = xi - ubi; *side = ELLP_NB_UPPER; return true; }
-    } else if (k == ELLP_BOUND_TWOSIDED) {
-        if (xi > ubi + eps) { *delta = xi - ubi; *side = ELLP_NB_UPPER; return true; }
-        if (xi < lbi - eps) { *delta = xi - lbi; *side = ELLP_NB_LOWER; return true; }
-    }
-    return false;
-}
-
 constexpr int DFU_BOOK = 2;  // block 0: reduced costs of the nonbasic variables, block 1: y
 
 template <int NR>  // double2 per thread per row: ceil(ld / 512), 1 / 2 / 4 / 8

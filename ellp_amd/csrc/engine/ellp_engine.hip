@@ -239,6 +239,8 @@ __device__ __forceinline__ int wave_allmin_dpp(int v) {
                min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
 
+#include "ellp_rules.inc"
+
 // one wave per column: a column with exactly one nonzero entry is recorded under its variable's index
 __global__ __launch_bounds__(256) void k_scan_singletons(const double *A, int64_t ld, int64_t m, int64_t ncols, const int64_t *index,
                                                          int32_t *vs_row, double *vs_val) {
@@ -660,14 +662,8 @@ __global__ __launch_bounds__(256) void k_price(PriceArgs a) {
             if (MODE == 0) {
                 const double rj = cd_pre - dot;
                 double key = -INFINITY;
-                if (rj != rj) {
-                    st->nan_flag = 1;
-                } else if (!(fabs(rj) < a.eps)) {
-                    const bool pos = rj > 0.0;
-                    if (pos && nb == ELLP_NB_UPPER) key = rj;
-                    else if (!pos && nb == ELLP_NB_LOWER) key = -rj;
-                    else if (nb == ELLP_NB_FREE) key = fabs(rj);
-                }
+                if (rj != rj) st->nan_flag = 1;
+                else key = primal_key(rj, nb, a.eps);
                 if (jj < plo || jj >= phi) key = -INFINITY;  // a column of a boundary block outside the segment
                 a.xc.r(jj) = rj;
                 a.xc.key(jj) = key;
@@ -675,11 +671,7 @@ __global__ __launch_bounds__(256) void k_price(PriceArgs a) {
             } else {
                 a.xc.r(jj) = dot;  // alpha (un-negated, dual…:286-288 restores the sign anyway)
                 const double al = sgn * dot;
-                bool keep;
-                if (nb == ELLP_NB_LOWER) keep = al > a.eps;
-                else if (nb == ELLP_NB_UPPER) keep = al < -a.eps;
-                else keep = true;
-                if (keep) {
+                if (dual_keep(al, nb, a.eps)) {
                     const double ratio = cd_pre / al;
                     if (ratio != ratio) st->nan_flag = 1;
                     if (bestpos < 0 || ratio < best) {  // strict '<' keeps the FIRST minimum
@@ -836,14 +828,8 @@ __global__ __launch_bounds__(256) void k_price_wave(PriceArgs a) {
             if (MODE == 0) {
                 const double rj = cd_pre - dot;
                 double key = -INFINITY;
-                if (rj != rj) {
-                    st->nan_flag = 1;
-                } else if (!(fabs(rj) < a.eps)) {
-                    const bool pos = rj > 0.0;
-                    if (pos && nb == ELLP_NB_UPPER) key = rj;
-                    else if (!pos && nb == ELLP_NB_LOWER) key = -rj;
-                    else if (nb == ELLP_NB_FREE) key = fabs(rj);
-                }
+                if (rj != rj) st->nan_flag = 1;
+                else key = primal_key(rj, nb, a.eps);
                 if (jj < plo || jj >= phi) key = -INFINITY;  // a column of a boundary block outside the segment
                 a.xc.r(jj) = rj;
                 a.xc.key(jj) = key;
@@ -851,11 +837,7 @@ __global__ __launch_bounds__(256) void k_price_wave(PriceArgs a) {
             } else {
                 a.xc.r(jj) = dot;  // alpha (un-negated, dual…:286-288 restores the sign anyway)
                 const double al = sgn * dot;
-                bool keep;
-                if (nb == ELLP_NB_LOWER) keep = al > a.eps;
-                else if (nb == ELLP_NB_UPPER) keep = al < -a.eps;
-                else keep = true;
-                if (keep) {
+                if (dual_keep(al, nb, a.eps)) {
                     const double ratio = cd_pre / al;
                     if (ratio != ratio) st->nan_flag = 1;
                     if (bestpos < 0 || ratio < best) {  // this lane's columns come in increasing position
@@ -1338,26 +1320,8 @@ __global__ __launch_bounds__(256) void k_ftran2(Ftran2Args a) {
         if (lane == 0) {
             a.d[i] = di;
             if (MODE == 0) {
-                double li = INFINITY;
-                if (!(fabs(di) < a.eps)) {
-                    if (k == ELLP_BOUND_FREE) {
-                        li = INFINITY;
-                    } else if (k == ELLP_BOUND_LOWER) {
-                        if (di > 0.0) li = INFINITY;
-                        else if (xi > lbi) li = (lbi - xi) / di;
-                        else li = 0.0;
-                    } else if (k == ELLP_BOUND_UPPER) {
-                        if (di > 0.0) li = (xi < ubi) ? (ubi - xi) / di : 0.0;
-                        else li = INFINITY;
-                    } else if (k == ELLP_BOUND_TWOSIDED) {
-                        if (di > 0.0) li = (xi < ubi) ? (ubi - xi) / di : 0.0;
-                        else if (xi < lbi) li = (lbi - xi) / di;  // quirk Q1 (primal…:359)
-                        else li = 0.0;
-                    } else {
-                        li = 0.0;  // Fixed
-                    }
-                    if (li != li) st->nan_flag = 1;
-                }
+                const double li = primal_lambda(di, xi, lbi, ubi, k, a.eps);  // primal…:320-367
+                if (li != li) st->nan_flag = 1;
                 a.lam[i] = li;
                 a.bidx[i] = (int32_t)bi;
                 a.dpos[i] = di > 0.0 ? 1 : 0;
@@ -1530,6 +1494,12 @@ __device__ __forceinline__ bool dual_violation(const int64_t *B_index, const dou
         if (xi < lb[bi] - eps) { *delta = xi - lb[bi]; *side = ELLP_NB_LOWER; return true; }
     }
     return false;
+}
+// the same rule on values in hand: one body, read through a basis of one variable
+__device__ __forceinline__ bool dual_violation_v(double xi, int k, double lbi, double ubi, double eps, double *delta, int *side) {
+    const int64_t at = 0;
+    const uint8_t k8 = (uint8_t)k;
+    return dual_violation(&at, &xi, &k8, &lbi, &ubi, eps, 0, delta, side);
 }
 // block-wide (256 threads) search for the leaving row; commits lr/ldelta/lside (lr = -1: none).  The reference takes the
 // FIRST violated basic position (dual…:200-236); maxviol (ELLP_FLAG_DUAL_MAX_VIOLATION, an extension): the one with the
@@ -2877,6 +2847,7 @@ __global__ __launch_bounds__(256) void k_rephase(const double *c, const uint8_t 
 #include "ellp_dualfu.inc"
 #include "ellp_shard.inc"
 #include "ellp_rebuild.inc"
+#include "ellp_loop_stages.inc"
 #include "ellp_small.inc"
 #include "ellp_mid.inc"
 #include "ellp_se.inc"

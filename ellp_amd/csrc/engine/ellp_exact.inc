@@ -164,23 +164,8 @@ __global__ __launch_bounds__(256) void k_exact_relam(ExactLamArgs a) {
     const int64_t bi = a.B_index[i];
     const double xi = a.x[bi], lbi = a.lb[bi], ubi = a.ub[bi];
     const int k = a.kind[bi];
-    double li = INFINITY;
-    if (!(fabs(di) < a.eps)) {
-        if (k == ELLP_BOUND_FREE) li = INFINITY;
-        else if (k == ELLP_BOUND_LOWER) {
-            if (di > 0.0) li = INFINITY;
-            else if (xi > lbi) li = (lbi - xi) / di;
-            else li = 0.0;
-        } else if (k == ELLP_BOUND_UPPER) {
-            if (di > 0.0) li = (xi < ubi) ? (ubi - xi) / di : 0.0;
-            else li = INFINITY;
-        } else if (k == ELLP_BOUND_TWOSIDED) {
-            if (di > 0.0) li = (xi < ubi) ? (ubi - xi) / di : 0.0;
-            else if (xi < lbi) li = (lbi - xi) / di;  // quirk Q1 (primal…:359)
-            else li = 0.0;
-        } else li = 0.0;  // Fixed
-        if (li != li) a.st->nan_flag = 1;
-    }
+    const double li = primal_lambda(di, xi, lbi, ubi, k, a.eps);  // primal…:320-367
+    if (li != li) a.st->nan_flag = 1;
     a.lam[i] = li;
     a.bidx[i] = (int32_t)bi;
     a.dpos[i] = di > 0.0 ? 1 : 0;

@@ -535,14 +535,8 @@ __global__ __launch_bounds__(256) void k_price2(Price2Args a) {
             const int nb = nb_pre;
             const double rj = cd_pre - dot;
             double key = -INFINITY;
-            if (rj != rj) {
-                st->nan_flag = 1;
-            } else if (!(fabs(rj) < a.p.eps)) {
-                const bool pos = rj > 0.0;
-                if (pos && nb == ELLP_NB_UPPER) key = rj;
-                else if (!pos && nb == ELLP_NB_LOWER) key = -rj;
-                else if (nb == ELLP_NB_FREE) key = fabs(rj);
-            }
+            if (rj != rj) st->nan_flag = 1;
+            else key = primal_key(rj, nb, a.p.eps);
             a.p.xc.r(jj) = rj;
             a.p.xc.key(jj) = key;
             best = fmax(best, key);
@@ -741,14 +735,8 @@ __global__ __launch_bounds__(256, 4) void k_price2_wave(Price2Args a) {  // 4 wa
             const int nb = nb_pre;
             const double rj = cd_pre - dot;
             double key = -INFINITY;
-            if (rj != rj) {
-                st->nan_flag = 1;
-            } else if (!(fabs(rj) < a.p.eps)) {
-                const bool pos = rj > 0.0;
-                if (pos && nb == ELLP_NB_UPPER) key = rj;
-                else if (!pos && nb == ELLP_NB_LOWER) key = -rj;
-                else if (nb == ELLP_NB_FREE) key = fabs(rj);
-            }
+            if (rj != rj) st->nan_flag = 1;
+            else key = primal_key(rj, nb, a.p.eps);
             a.p.xc.r(jj) = rj;
             a.p.xc.key(jj) = key;
             best = fmax(best, key);
@@ -1129,25 +1117,8 @@ __global__ __launch_bounds__(256) void k_ftran_eta(FtranEtaArgs a) {
                 const double di = sgn * (((s_dot[0][k] + s_dot[1][k]) + s_dot[2][k]) + s_dot[3][k]);
                 const double xi = xi0, lbi = lbi0, ubi = ubi0;
                 a.d[myrow] = di;
-                if (!(fabs(di) < a.eps)) {  // primal…:320-367
-                    if (k0 == ELLP_BOUND_FREE) {
-                        li = INFINITY;
-                    } else if (k0 == ELLP_BOUND_LOWER) {
-                        if (di > 0.0) li = INFINITY;
-                        else if (xi > lbi) li = (lbi - xi) / di;
-                        else li = 0.0;
-                    } else if (k0 == ELLP_BOUND_UPPER) {
-                        if (di > 0.0) li = (xi < ubi) ? (ubi - xi) / di : 0.0;
-                        else li = INFINITY;
-                    } else if (k0 == ELLP_BOUND_TWOSIDED) {
-                        if (di > 0.0) li = (xi < ubi) ? (ubi - xi) / di : 0.0;
-                        else if (xi < lbi) li = (lbi - xi) / di;  // quirk Q1 (primal…:359)
-                        else li = 0.0;
-                    } else {
-                        li = 0.0;  // Fixed
-                    }
-                    if (li != li) st->nan_flag = 1;
-                }
+                li = primal_lambda(di, xi, lbi, ubi, k0, a.eps);  // primal…:320-367
+                if (li != li) st->nan_flag = 1;
                 a.lam[myrow] = li;
                 a.bidx[myrow] = (int32_t)bi0;
                 a.dpos[myrow] = di > 0.0 ? 1 : 0;

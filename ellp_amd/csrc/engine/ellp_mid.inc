@@ -31,6 +31,12 @@
 //   * pricing reads a row-major copy of A_N (A_Nt, rebuilt at every launch, one column rewritten per pivot):
 //     lane j accumulates column j's dot product in row order with coalesced loads.
 //
+// What does NOT differ is not written twice: the stages between the solves (column classification, the first-minimum and
+// entering folds, bound-flip bookkeeping, commit) are the functions of ellp_loop_stages.inc that small_loop calls, on the
+// scalar rules of ellp_rules.inc.  This file keeps the loop's skeleton (barriers, fences, stamps, early returns), the
+// factorisation and the solves, and the three stages that file names as left in place (leaving row, primal ratio test,
+// chunk maximum).
+//
 // Included inside the anonymous namespace of ellp_engine.hip after ellp_small.inc.
 
 struct MidArgs {
@@ -787,6 +793,23 @@ __device__ __noinline__ bool mid_lu_solve(lu8 *base, int tid, int pos, double mi
     return true;
 }
 
+// Pricing's dot product of one column of the row-major copy of A_N (cj: its first entry, stride ldn) with v1, accumulated in
+// row order with eight loads in flight.  The caller clamps the address of a lane past the last column and loads
+// unconditionally (DESIGN.md §3.1b).
+__device__ __forceinline__ double mid_dot(const double *cj, int64_t ldn, int m, const double *v1) {
+    double dot = 0.0;
+    int i = 0;
+    for (; i + 8 <= m; i += 8) {
+        double pr[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) pr[u] = cj[(int64_t)(i + u) * ldn] * v1[i + u];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) dot += pr[u];
+    }
+    for (; i < m; ++i) dot += cj[(int64_t)i * ldn] * v1[i];
+    return dot;
+}
+
 // The loop of k_mid for the LP of `a`, run by the whole workgroup.  A function of its arguments alone (no blockIdx), so
 // that k_mid_batch can run one LP per workgroup with the same code (as small_loop is for k_small / k_small_batch).
 template <int KIND, int NT>
@@ -862,17 +885,7 @@ __device__ __forceinline__ void mid_loop(const MidArgs a) {
                 }
                 for (int c = wave; c < nch; c += NW) {
                     const int64_t j = (int64_t)c * 64 + lane;
-                    const double *cj = a.A_Nt + (j < nN ? j : 0);
-                    double dot = 0.0;
-                    int i = 0;
-                    for (; i + 8 <= m; i += 8) {
-                        double pr[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) pr[u] = cj[(int64_t)(i + u) * ldn] * v1[i + u];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) dot += pr[u];
-                    }
-                    for (; i < m; ++i) dot += cj[(int64_t)i * ldn] * v1[i];
+                    const double dot = mid_dot(a.A_Nt + (j < nN ? j : 0), ldn, m, v1);
                     if (j < nN) a.dd[a.N_index[j]] = a.c_N[j] - dot;
                 }
             }
@@ -967,63 +980,13 @@ __device__ __forceinline__ void mid_loop(const MidArgs a) {
             const int64_t j = (int64_t)c * 64 + lane;
             double key = (KIND == 0) ? -INFINITY : INFINITY;
             long long ppos = -1;
-            const int64_t jc = j < nN ? j : 0;
-            {
-                const double *cj = a.A_Nt + jc;
-                double dot = 0.0;
-                int i = 0;
-                for (; i + 8 <= m; i += 8) {  // eight loads in flight; the sum is still accumulated in row order
-                    double pr[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) pr[u] = cj[(int64_t)(i + u) * ldn] * v1[i + u];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) dot += pr[u];
-                }
-                for (; i < m; ++i) dot += cj[(int64_t)i * ldn] * v1[i];
-                if (j < nN) {
-                    const int nb = a.Nb[j];
-                    if (KIND == 0) {
-                        const double rj = a.c_N[j] - dot;
-                        if (rj != rj) s_nan = 1;
-                        else if (!(fabs(rj) < eps)) {
-                            const bool posr = rj > 0.0;
-                            if (posr && nb == ELLP_NB_UPPER) key = rj;
-                            else if (!posr && nb == ELLP_NB_LOWER) key = -rj;
-                            else if (nb == ELLP_NB_FREE) key = fabs(rj);
-                        }
-                        a.rbuf[j] = rj;
-                        a.kbuf[j] = key;
-                    } else {
-                        const double al = (delta < 0.0) ? -dot : dot;
-                        a.rbuf[j] = dot;  // alpha as dual…:286-288 leaves it (the negation undone)
-                        bool keep;
-                        if (nb == ELLP_NB_LOWER) keep = al > eps;
-                        else if (nb == ELLP_NB_UPPER) keep = al < -eps;
-                        else keep = true;
-                        if (keep) {
-                            const double ratio = a.dd[a.N_index[j]] / al;
-                            if (ratio != ratio) s_nan = 1;
-                            key = ratio;
-                            ppos = j;
-                        }
-                        if (a.bflip) a.kbuf[j] = keep ? key : __longlong_as_double(0x7ff8000000000000ll);
-                    }
-                }
-            }
+            const double dot = mid_dot(a.A_Nt + (j < nN ? j : 0), ldn, m, v1);
+            if (j < nN) classify_column<KIND>(a, j, dot, delta, eps, &s_nan, &key, &ppos);
             if (KIND == 0) {
                 const double v = wave_allmax_dpp(key);  // keys are never NaN
                 if (lane == 0) cmx[c] = v;
             } else {
-                // first minimum of the chunk: lexicographic (ratio, position)
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const double ok = __shfl_xor(key, o);
-                    const long long op = __shfl_xor(ppos, o);
-                    if (op >= 0 && (ppos < 0 || ok < key || (ok == key && op < ppos))) {
-                        key = ok;
-                        ppos = op;
-                    }
-                }
+                wave_first_min(&key, &ppos);  // lexicographic (ratio, position)
                 if (lane == 0) {
                     cmx[c] = key;
                     cps[c] = ppos;
@@ -1037,54 +1000,7 @@ __device__ __forceinline__ void mid_loop(const MidArgs a) {
         }
         MID_STAMP(4)
         // ---------------- entering variable
-        if (wave == 0) {
-            if (KIND == 0) {  // the reference's sequential max_by fold (primal…:271-287), exactly
-                FoldState f{false, 0.0, 0, -1};
-                for (int g0 = 0; g0 < nch; g0 += WAVE) {
-                    const double bm = (g0 + lane < nch) ? cmx[g0 + lane] : -INFINITY;
-                    int from = 0;
-                    for (;;) {
-                        const bool pred = lane >= from && bm > -INFINITY && (!f.have || f.racc - bm < eps);
-                        const unsigned long long mask = __ballot(pred);
-                        if (!mask) break;
-                        const int bl = __ffsll((long long)mask) - 1;
-                        const int64_t jb = (int64_t)(g0 + bl) * 64;
-                        const int64_t j = jb + lane;
-                        const bool valid = j < nN;
-                        const double k = valid ? a.kbuf[j] : -INFINITY;
-                        const long long idx = valid ? a.N_index[j] : 0;
-                        fold_elements(f, k, idx, jb, eps, lane);
-                        from = bl + 1;
-                    }
-                }
-                if (lane == 0) s_q = f.qacc;
-            } else {  // min_by keeps the first minimum (dual…:279)
-                double bk = INFINITY;
-                long long bp = -1;
-                for (int c = lane; c < nch; c += WAVE) {
-                    const long long p = cps[c];
-                    if (p < 0) continue;
-                    const double k = cmx[c];
-                    if (bp < 0 || k < bk || (k == bk && p < bp)) {
-                        bk = k;
-                        bp = p;
-                    }
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const double ok = __shfl_xor(bk, o);
-                    const long long op = __shfl_xor(bp, o);
-                    if (op >= 0 && (bp < 0 || ok < bk || (ok == bk && op < bp))) {
-                        bk = ok;
-                        bp = op;
-                    }
-                }
-                if (lane == 0) {
-                    s_q = bp;
-                    s_theta = (delta < 0.0) ? -bk : bk;  // dual…:286-289
-                }
-            }
-        }
+        if (wave == 0) enter_fold<KIND>(a, nch, nN, delta, eps, lane, cmx, cps, &s_q, &s_theta);
         __syncthreads();
         long long q = s_q;
         if (q < 0) {
@@ -1102,22 +1018,9 @@ __device__ __forceinline__ void mid_loop(const MidArgs a) {
             theta_sel = (delta < 0.0) ? -ck : ck;
             if (nflip > 0) {
                 __syncthreads();  // flist is complete
-                double acc = 0.0;
-                if (tid < m)
-                    for (int k = 0; k < nflip; ++k) {
-                        const long long pj = a.flist[k];
-                        const int64_t vj = a.N_index[pj];
-                        const double dx = (a.Nb[pj] == ELLP_NB_LOWER) ? (a.ub[vj] - a.lb[vj]) : (a.lb[vj] - a.ub[vj]);
-                        acc += a.A_N[pj * ld + tid] * dx;
-                    }
+                const double acc = tid < m ? flip_row_rhs(a, nflip, ld, tid) : 0.0;
                 __syncthreads();  // every thread has read the labels before they change
-                for (int k = tid; k < nflip; k += NT) {
-                    const long long pj = a.flist[k];
-                    const int64_t vj = a.N_index[pj];
-                    const bool lower = a.Nb[pj] == ELLP_NB_LOWER;
-                    a.x[vj] = lower ? a.ub[vj] : a.lb[vj];
-                    a.Nb[pj] = lower ? ELLP_NB_UPPER : ELLP_NB_LOWER;
-                }
+                flip_relabel<NT>(a, nflip, tid);
                 if (!mid_lu_solve<NT>(base, tid, pos, acc)) {
                     if (tid == 0) {
                         st->panic_code = 2940;
@@ -1131,10 +1034,7 @@ __device__ __forceinline__ void mid_loop(const MidArgs a) {
                 }
                 __threadfence_block();
                 __syncthreads();
-                {
-                    const int64_t bi = a.B_index[lr];
-                    delta_upd = (s_side == ELLP_NB_UPPER) ? a.x[bi] - a.ub[bi] : a.x[bi] - a.lb[bi];
-                }
+                delta_upd = flip_delta(a, lr, s_side);
                 __syncthreads();  // v2 is the FTRAN's next
             }
         }
@@ -1161,24 +1061,8 @@ __device__ __forceinline__ void mid_loop(const MidArgs a) {
                 v2[i] = di;
                 const int64_t bi = a.B_index[i];
                 const double xi = a.x[bi], lbi = a.lb[bi], ubi = a.ub[bi];
-                const int k = a.kind[bi];
-                double li = INFINITY;
-                if (!(fabs(di) < eps)) {
-                    if (k == ELLP_BOUND_FREE) li = INFINITY;
-                    else if (k == ELLP_BOUND_LOWER) {
-                        if (di > 0.0) li = INFINITY;
-                        else if (xi > lbi) li = (lbi - xi) / di;
-                        else li = 0.0;
-                    } else if (k == ELLP_BOUND_UPPER) {
-                        if (di > 0.0) li = (xi < ubi) ? (ubi - xi) / di : 0.0;
-                        else li = INFINITY;
-                    } else if (k == ELLP_BOUND_TWOSIDED) {
-                        if (di > 0.0) li = (xi < ubi) ? (ubi - xi) / di : 0.0;
-                        else if (xi < lbi) li = (lbi - xi) / di;  // quirk Q1 (primal…:359)
-                        else li = 0.0;
-                    } else li = 0.0;  // Fixed
-                    if (li != li) s_nan = 1;
-                }
+                const double li = primal_lambda(di, xi, lbi, ubi, a.kind[bi], eps);  // primal…:320-367
+                if (li != li) s_nan = 1;
                 lam[i] = li;
                 bidx[i] = (int32_t)bi;
                 dpos[i] = di > 0.0 ? 1 : 0;
@@ -1238,32 +1122,9 @@ __device__ __forceinline__ void mid_loop(const MidArgs a) {
                     a.A_Nt[(int64_t)tid * ldn + q] = tb;
                     a.A_B[r * ld + tid] = t;
                 }
-                if (tid == 0) {
-                    const int64_t t = a.B_index[r];
-                    a.B_index[r] = jq;
-                    a.N_index[q] = t;
-                    const double tc = a.c_N[q];
-                    a.c_N[q] = a.c_B[r];
-                    a.c_B[r] = tc;
-                    a.Nb[q] = (uint8_t)s_side;
-                    st->lambda = lambda;
-                    st->pivots += 1;
-                    if (lambda > 0.0) st->obj = st->obj + (at_lower ? lambda * a.rbuf[q] : -(lambda * a.rbuf[q]));
-                    trace_put(a.trace, st->iters, st->obj);
-                }
-            } else if (tid == 0) {  // primal…:223-231
-                const int nbq = a.Nb[q];
-                st->lambda = lambda;
-                st->flips += 1;
-                if (lambda > 0.0) st->obj = st->obj + (at_lower ? lambda * a.rbuf[q] : -(lambda * a.rbuf[q]));
-                trace_put(a.trace, st->iters, st->obj);
-                if (nbq == ELLP_NB_LOWER) a.Nb[q] = ELLP_NB_UPPER;
-                else if (nbq == ELLP_NB_UPPER) a.Nb[q] = ELLP_NB_LOWER;
-                else {
-                    st->panic_code = 229;
-                    st->status = ELLP_ERR_PANIC;
-                    s_stop = 1;
-                }
+                if (tid == 0) commit_primal_pivot(a, q, r, jq, s_side, lambda, at_lower);
+            } else if (tid == 0) {
+                commit_primal_flip(a, q, lambda, at_lower, &s_stop);
             }
         } else {
             // ---------------- dual updates (dual…:296-316) and swap (:322-333)
@@ -1289,24 +1150,7 @@ __device__ __forceinline__ void mid_loop(const MidArgs a) {
                 a.A_N[q * ld + tid] = t;
                 a.A_Nt[(int64_t)tid * ldn + q] = t;
             }
-            if (tid == 0) {
-                a.dd[lv] = -theta_d;
-                a.dd[jq] = 0.0;
-                a.x[jq] = a.x[jq] + theta_p;
-                st->obj = st->obj + theta_d * delta_upd;
-                trace_put(a.trace, st->iters, st->obj);
-                a.B_index[r] = jq;
-                a.N_index[q] = lv;
-                a.Nb[q] = (uint8_t)s_side;
-                const double tc = a.c_N[q];  // the dual loop does not use costs; kept consistent for a later hand-off
-                a.c_N[q] = a.c_B[r];
-                a.c_B[r] = tc;
-                st->pivots += 1;
-                if (theta_p != theta_p) {
-                    st->status = ELLP_ERR_NAN;
-                    s_stop = 1;
-                }
-            }
+            if (tid == 0) commit_dual_pivot(a, q, r, jq, lv, s_side, theta_d, theta_p, delta_upd, &s_stop);
         }
         __threadfence_block();
         __syncthreads();

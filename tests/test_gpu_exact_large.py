@@ -198,6 +198,83 @@ def test_dual_rephase_keeps_the_exact_loop():
     _exact_loop_alone(c, it_o1 + it_o2)
 
 
+def _all_kinds_start(seed, m=1030, n=60):
+    """A primal feasible start with every bound kind among the basic and the nonbasic variables: n sparse structural columns
+    (nonbasic on a bound, Free ones at 0) and an identity of m basic columns whose values lie inside their bounds, except a few
+    that sit exactly on one (degenerate rows).  TwoSided and Fixed basics are kept few: a TwoSided basic with d_i < 0 bounds
+    the step by 0 wherever it stands (quirk Q1), so with many of them no body would move x."""
+    rng = np.random.default_rng(seed)
+    ncols = n + m
+    A = np.zeros((m, ncols), order="F")
+    A[:, :n] = np.where(rng.random((m, n)) < 0.05, rng.normal(size=(m, n)), 0.0)
+    A[np.arange(m), n + np.arange(m)] = 1.0
+    kind = np.empty(ncols, dtype=np.uint8)
+    kind[:n] = np.arange(n) % 5
+    kind[n:] = rng.choice([0, 1, 2, 3, 4], size=m, p=[0.05, 0.55, 0.38, 0.015, 0.005])
+    lb, ub, x = np.zeros(ncols), np.zeros(ncols), np.zeros(ncols)
+    w = 0.5 + rng.random(ncols)           # distance to the one bound / half width of a box
+    t = rng.random(ncols)                 # where a basic variable stands inside
+    t[rng.random(ncols) < 0.004] = 0.0    # a few exactly on a bound
+    t[rng.random(ncols) < 0.004] = 1.0
+    two = n + np.where(kind[n:] == 3)[0]  # the few TwoSided basics: at lb, at ub, inside, in turn
+    t[two[0::3]], t[two[1::3]] = 0.0, 1.0
+    Nb = np.zeros(n, dtype=np.uint8)
+    for j in range(ncols):
+        k, basic = kind[j], j >= n
+        if k == 0:
+            x[j] = (t[j] - 0.5) if basic else 0.0
+        elif k == 1:
+            lb[j] = -w[j]
+            x[j] = lb[j] + (t[j] * w[j] if basic else 0.0)
+        elif k == 2:
+            ub[j] = w[j]
+            x[j] = ub[j] - (t[j] * w[j] if basic else 0.0)
+        elif k == 3:
+            lb[j], ub[j] = -w[j], w[j]
+            x[j] = lb[j] + (t[j] if basic else float(j % 2)) * 2 * w[j]
+        else:
+            lb[j] = ub[j] = x[j] = t[j] - 0.5
+        if not basic:
+            Nb[j] = 2 if k == 0 else (1 if (k == 2 or (k == 3 and j % 2)) else 0)
+    b = np.zeros(m)
+    for j in range(ncols):
+        if x[j] != 0.0:
+            b += A[:, j] * x[j]
+    c = np.zeros(ncols)
+    c[:n] = rng.normal(size=n)
+    return dict(m=m, n=ncols, n_c=ncols, A=A.reshape(-1, order="F"), c=c, b=b, kind=kind, lb=lb, ub=ub, x=x,
+                B=np.arange(n, ncols, dtype=np.int64), N=np.arange(n, dtype=np.int64), Nb=Nb)
+
+
+def test_every_bound_kind_reaches_the_exact_ratio_test():
+    """The starts above are all-Lower (with Fixed artificials in phase 2), so of the bounded ratio lambda_i (primal…:320-367,
+    primal_lambda in ellp_rules.inc) k_exact_relam only ever took the Lower and Fixed branches.  Here: m = 1,030 (the smallest
+    size class above k_mid), 60 structural columns, all five bound kinds basic and nonbasic, the first 30 loop bodies; status,
+    body count and basis are the oracle's, x to this file's tolerance.
+
+    Seed 2, chosen on the CPU from the oracle's run: it neither ends nor panics within the 30 bodies, 11 of them move x, and
+    over the 30 x 1,030 rows the branches are taken |d_i| < EPS 25,166 times; Free 369; Lower: d_i > 0 1,474, x_i > lb 1,504,
+    else 0 twice; Upper: d_i > 0 and x_i < ub 1,102, d_i > 0 else 0 twice, d_i <= 0 1,217; TwoSided: d_i > 0 and x_i < ub 39,
+    d_i > 0 else 0 four times, d_i <= 0 else 0 19 times; Fixed twice.  The division of quirk Q1 (TwoSided, d_i <= 0,
+    x_i < lb) is not reachable from a feasible point: its lambda_i is negative and ends the loop by the panic of primal…:402."""
+    E = _E()
+    f = _all_kinds_start(2)
+    assert sorted(set(f["kind"][f["B"]])) == sorted(set(f["kind"][f["N"]])) == [0, 1, 2, 3, 4]
+    ov = _view(f)
+    st_o, it_o, _ = eo.primal_solve_with_initial(ov, 30)
+    assert st_o == eo.MAXITER and it_o == 30, (st_o, it_o)
+    fp, eng = _engine("primal", f, max_iter=30)
+    try:
+        st, stats, msg = eng.run(30)
+        eng.read_point()
+        c = eng.counters()
+    finally:
+        eng.close()
+    assert st == E.MAXITER and int(stats.iters) == 30, (st, stats.iters, msg)
+    _same_point("primal", fp, ov)
+    _exact_loop_alone(c, 30)
+
+
 def test_sharding_and_stepping_are_refused():
     E = _E()
     fp, eng = _engine("dual", _start("dual"), max_iter=100000)
