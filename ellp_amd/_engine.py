@@ -114,6 +114,8 @@ def lib():
     L.ellp_engine_request_maintenance.argtypes = [C.c_void_p]
     L.ellp_engine_debug_scale_inverse.restype = C.c_int
     L.ellp_engine_debug_scale_inverse.argtypes = [C.c_void_p, C.c_double]
+    L.ellp_engine_debug_set_inverse.restype = C.c_int
+    L.ellp_engine_debug_set_inverse.argtypes = [C.c_void_p, C.c_void_p]
     L.ellp_engine_set_shard.restype = C.c_int
     L.ellp_engine_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_size_t]
     L.ellp_engine_segment_doubles.restype = C.c_int64
@@ -541,6 +543,14 @@ class Engine:
         s = lib().ellp_engine_debug_scale_inverse(self._h, float(factor))
         if s != OPTIMAL:
             raise EllpHipError(s, "debug_scale_inverse failed")
+
+    def debug_set_inverse(self, W):
+        """test hook: B^-1 <- W (m x m, row-major): the mirror of tap(TAP_BINV)"""
+        W_ = _f64(W).reshape(-1)
+        assert W_.size == self.fp.m * self.fp.m
+        s = lib().ellp_engine_debug_set_inverse(self._h, _p(W_))
+        if s != OPTIMAL:
+            raise EllpHipError(s, "debug_set_inverse failed")
 
     def counters(self):
         """host-side maintenance counters (TAP_STATE tail)"""

@@ -2436,6 +2436,11 @@ __global__ void k_ref_finish(RefArgs a) { ref_finish_body(a); }
 //   AMODE 1: A(i,k) = A[i*ld + k] (row-major W)            OMODE 1: out = Cin + acc       (W + W E)
 //   B(k,j) = B[k*ld + j] (row-major) in both uses.
 // WSEL picks operands from the two B^-1 buffers by st->cur on the device.
+
+// NaN-propagating maximum of two residuals (fmax returns the other operand when one is NaN, so a NaN in
+// B^-1 would fold away and the residual would look small): NaN if either is NaN, else the larger.
+__device__ __forceinline__ double nanmax(double a, double b) { return (a != a) ? a : ((b > a || b != b) ? b : a); }
+
 struct GemmArgs {
     double *W0, *W1;
     const double *A_B;
@@ -2530,16 +2535,16 @@ __global__ __launch_bounds__(256) void k_gemm128(GemmArgs a) {
             if (STEP == 0) o = (i == j ? 1.0 : 0.0) - acc[r][c];
             else o = Wc[i * ld + j] + acc[r][c];
             C[i * ld + j] = o;
-            worst = fmax(worst, fabs(o));
+            worst = nanmax(worst, fabs(o));
         }
     }
     if (STEP == 0) {
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o));
+        for (int o = 32; o > 0; o >>= 1) worst = nanmax(worst, __shfl_xor(worst, o));
         if ((tid & 63) == 0) s_red[tid >> 6] = worst;
         __syncthreads();
         if (tid == 0)
-            a.tilemax[blockIdx.y * gridDim.x + blockIdx.x] = fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3]));
+            a.tilemax[blockIdx.y * gridDim.x + blockIdx.x] = nanmax(nanmax(s_red[0], s_red[1]), nanmax(s_red[2], s_red[3]));
     }
 }
 
@@ -2617,11 +2622,11 @@ __global__ __launch_bounds__(256) void k_inv_residual(const double *W0, const do
         }
         acc = wave_sum(acc);
         const double e = fabs(acc - (i == k ? 1.0 : 0.0));
-        worst = fmax(worst, e);
+        worst = nanmax(worst, e);
     }
     if (lane == 0) s_m[wave] = worst;
     __syncthreads();
-    if (threadIdx.x == 0) out[i] = fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
+    if (threadIdx.x == 0) out[i] = nanmax(nanmax(s_m[0], s_m[1]), nanmax(s_m[2], s_m[3]));
 }
 
 // gather columns of A (m x n, ld m) into a padded destination (ld) by an index list
@@ -4314,8 +4319,11 @@ static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_
     ECHK(dmalloc(e, &e->lam, (size_t)m));
     ECHK(dmalloc(e, &e->bidx, (size_t)m));
     ECHK(dmalloc(e, &e->dpos, (size_t)m));
-    ECHK(dmalloc(e, &e->resid, (size_t)(m > 4096 ? m : 4096)));
-    ECHK(hipMemsetAsync(e->resid, 0, sizeof(double) * (size_t)(m > 4096 ? m : 4096), e->stream));
+    // m row maxima (k_inv_residual), or one maximum per 128 x 128 tile of the refresh's first GEMM: more than m above 16,384 rows
+    const int64_t resid_tiles = ((m + 127) / 128) * ((m + 127) / 128);
+    const size_t resid_len = (size_t)std::max<int64_t>(std::max<int64_t>(m, 4096), resid_tiles);
+    ECHK(dmalloc(e, &e->resid, resid_len));
+    ECHK(hipMemsetAsync(e->resid, 0, sizeof(double) * resid_len, e->stream));
     ECHK(dmalloc(e, &e->T, (size_t)(m * ld)));
     ECHK(hipMemsetAsync(e->T, 0, sizeof(double) * (size_t)(m * ld), e->stream));
     ECHK(dmalloc(e, &e->st, 1));
@@ -5665,6 +5673,24 @@ ellp_status ellp_engine_debug_scale_inverse(ellp_engine *e, double factor) {
     if (hipSetDevice(e->device) != hipSuccess) return ELLP_ERR_DEVICE;
     if (ensure_inverse(e, nullptr, 0) != ELLP_OPTIMAL) return ELLP_ERR_DEVICE;
     hipLaunchKernelGGL(k_scale_inverse, dim3(512), dim3(256), 0, e->stream, e->W, e->W2, e->st, e->m * e->ld, factor);
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return ELLP_ERR_DEVICE;
+    e->u_valid = false;
+    return ELLP_OPTIMAL;
+}
+
+ellp_status ellp_engine_debug_set_inverse(ellp_engine *e, const double *W) {
+    if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
+    if (!e || !W) return ELLP_ERR_ARG;
+    if (hipSetDevice(e->device) != hipSuccess) return ELLP_ERR_DEVICE;
+    if (ensure_inverse(e, nullptr, 0) != ELLP_OPTIMAL) return ELLP_ERR_DEVICE;
+    // the mirror of ELLP_TAP_BINV: row-major m x m without the padding, into the buffer st->cur names
+    if (hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+        hipStreamSynchronize(e->stream) != hipSuccess)
+        return ELLP_ERR_DEVICE;
+    if (e->m > 0 &&
+        hipMemcpy2DAsync(e->h_st->cur ? e->W2 : e->W, sizeof(double) * (size_t)e->ld, W, sizeof(double) * (size_t)e->m,
+                         sizeof(double) * (size_t)e->m, (size_t)e->m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return ELLP_ERR_DEVICE;
     if (hipStreamSynchronize(e->stream) != hipSuccess) return ELLP_ERR_DEVICE;
     e->u_valid = false;
     return ELLP_OPTIMAL;

@@ -136,16 +136,16 @@ __global__ __launch_bounds__(512) void k_gemm_mfma(GemmArgs a) {
                     if (STEP == 0) o = (i == j ? 1.0 : 0.0) - acc[r][c][v];
                     else o = Wc[i * ld + j] + acc[r][c][v];
                     C[i * ld + j] = o;
-                    worst = fmax(worst, fabs(o));
+                    worst = nanmax(worst, fabs(o));
                 }
             }
     if (STEP == 0) {
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o));
+        for (int o = 32; o > 0; o >>= 1) worst = nanmax(worst, __shfl_xor(worst, o));
         double *s_red = &sA[0][0][0];  // free: the last stage's readers are past the loop's final barrier
         if (lane == 0) s_red[wave] = worst;
         __syncthreads();
         if (tid == 0)
-            a.tilemax[blockIdx.y * gridDim.x + blockIdx.x] = fmax(fmax(fmax(s_red[0], s_red[1]), fmax(s_red[2], s_red[3])), fmax(fmax(s_red[4], s_red[5]), fmax(s_red[6], s_red[7])));
+            a.tilemax[blockIdx.y * gridDim.x + blockIdx.x] = nanmax(nanmax(nanmax(s_red[0], s_red[1]), nanmax(s_red[2], s_red[3])), nanmax(nanmax(s_red[4], s_red[5]), nanmax(s_red[6], s_red[7])));
     }
 }

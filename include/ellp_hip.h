@@ -500,7 +500,8 @@ int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap);
 
 /* One Newton-Schulz step W <- W + W (I - A_B W) on the resident inverse (two f64 GEMMs); this
  * is what the engine does every `refactor_period` iterations.  Returns max|I - A_B W| measured
- * before the step (NaN on error); if that is >= 1e-4 nothing is changed (rebuild instead). */
+ * before the step (NaN on error); if that is >= 1e-4 nothing is changed (rebuild instead).  A NaN or
+ * Inf in W makes the returned maximum NaN or Inf (the maximum propagates NaN), which refuses the step too. */
 double ellp_engine_refresh(ellp_engine *e);
 
 /* Forces a full rebuild of B^-1 from A_B now (used by tests and when a refresh is not safe). */
@@ -515,7 +516,13 @@ ellp_status ellp_engine_request_maintenance(ellp_engine *e);
  * which a refresh is refused and the host rebuilds from A_B). */
 ellp_status ellp_engine_debug_scale_inverse(ellp_engine *e, double factor);
 
-/* max_ij |(B^-1 A_B - I)_ij| computed on device (drift monitor; tests). */
+/* Test hook: replaces the resident B^-1 by W, m x m row-major without padding in host memory: the
+ * mirror of ELLP_TAP_BINV (what is set is what that tap reads back, bit for bit).  Nothing else of the
+ * engine's state follows: x_B stays as it is until the next maintenance. */
+ellp_status ellp_engine_debug_set_inverse(ellp_engine *e, const double *W);
+
+/* max_ij |(B^-1 A_B - I)_ij| computed on device (drift monitor; tests); NaN if any
+ * entry is NaN: never a finite number for an inverse that holds a NaN or an Inf. */
 double ellp_engine_inverse_residual(ellp_engine *e);
 
 void ellp_engine_destroy(ellp_engine *e);
