@@ -23,6 +23,7 @@ K_NAMES = ["price", "select", "ftran", "ratio", "update", "btran", "refactor", "
            "dselect", "dupdate", "event_cost"]
 K_COUNT = 12
 TAP_U, TAP_R, TAP_D, TAP_BINV, TAP_KEY, TAP_ALPHA, TAP_STATE = range(7)
+TAP_SE_GAMMA = 7  # steepest-edge weights by nonbasic position, as the LAST pricing launch left them (include/ellp_hip.h)
 
 
 class Opts(C.Structure):

@@ -5542,7 +5542,7 @@ int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap) {
         count = e->nN;
         break;
     case ELLP_TAP_D: src = e->d; count = e->m; break;
-    case 7:  // steepest-edge weights by nonbasic position (diagnostics; valid up to the last pricing launch)
+    case ELLP_TAP_SE_GAMMA:  // steepest-edge weights by nonbasic position, as the last pricing launch left them (include/ellp_hip.h)
         if (!e->se) return ELLP_ERR_ARG;
         src = e->se_gamma;
         count = e->nN;

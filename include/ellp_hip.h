@@ -495,7 +495,13 @@ enum { ELLP_TAP_U = 0, ELLP_TAP_R = 1, ELLP_TAP_D = 2, ELLP_TAP_BINV = 3, ELLP_T
                                                   terminal statuses examined, of those not confirmed, loop bodies run by the
                                                   exact kernel, rebuilds of B^-1 after a hand-over (, solves repeated by the exact
                                                   kernel)(, end points returned NOT certified: a repetition above 1,024 rows that
-                                                  ELLP_REDO_MAX_SECONDS ruled out, a singular LU in the certificate) */ };
+                                                  ELLP_REDO_MAX_SECONDS ruled out, a singular LU in the certificate) */,
+       ELLP_TAP_SE_GAMMA = 7 /* the steepest-edge weights gamma_j = 1 + |B^-1 a_j|^2 (ELLP_FLAG_PRIMAL_STEEPEST_EDGE), n_N doubles
+                                by nonbasic position.  The update a pivot asks for is applied by the NEXT pricing launch, so the
+                                weights are those of the basis and the position order that the LAST PRICING LAUNCH priced: after
+                                ellp_engine_run(e, k) they belong to the point ellp_engine_read_point returned after run(k - 1)
+                                (at creation and after ellp_engine_rephase: to the point the engine stands on).  ELLP_ERR_ARG on
+                                an engine without the flag. */ };
 int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap);
 
 /* One Newton-Schulz step W <- W + W (I - A_B W) on the resident inverse (two f64 GEMMs); this
