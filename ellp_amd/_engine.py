@@ -96,6 +96,8 @@ def lib():
     L.ellp_engine_create.restype = C.c_int
     L.ellp_engine_create.argtypes = ([C.c_int] + _PROBLEM_ARGS + [C.c_void_p, C.c_void_p] +
                                      [C.POINTER(Opts), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t])
+    L.ellp_engine_plan.restype = C.c_int
+    L.ellp_engine_plan.argtypes = [C.c_int, C.c_int64, C.c_int64, C.POINTER(Opts), C.c_int, C.c_void_p, C.c_int64, C.c_char_p, C.c_size_t]
     L.ellp_engine_run.restype = C.c_int
     L.ellp_engine_run.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(Stats), C.c_char_p, C.c_size_t]
     L.ellp_engine_read_point.restype = C.c_int
@@ -258,6 +260,25 @@ def default_opts(**kw):
             v = MAX_ITER_NONE
         setattr(o, k, v)
     return o
+
+
+# what ellp_engine_plan writes, in its order (include/ellp_hip.h)
+PLAN_FIELDS = ("ld", "cpb", "nblocks", "priceT", "price_nt", "price_wave", "upd_rows", "upd_blocks", "upd2_rows", "upd2_blocks",
+               "ftran_blocks", "btran_rows", "btran_tiles", "upd_stage", "upd_lds", "ftran_lds", "price2_lds", "bl_splits", "nbs",
+               "seg", "refactor_period", "ill_tol", "drift_every", "drift_tol", "pp_P", "pp_S", "se", "se_vpart", "dual_maxviol",
+               "dual_bflip", "small", "mid", "small_lds", "mid_lds", "small_nt", "mid_nt", "ldn", "hybrid", "cert_large",
+               "guard_abs", "exact_K", "exact_large_always", "lagged", "dual_fused", "dual_fold", "unit_table", "stamps")
+PLAN_AVAIL_SMALL, PLAN_AVAIL_MID, PLAN_AVAIL_ALL = 1, 2, 3
+
+
+def engine_plan(kind, m, n_N, opts=None, avail=PLAN_AVAIL_ALL):
+    """The engine ellp_engine_create would make for these sizes and options, decided without a device: (status, dict of
+    PLAN_FIELDS or None, message).  The environment is read as creation reads it."""
+    out = np.zeros(len(PLAN_FIELDS))
+    err = C.create_string_buffer(512)
+    s = lib().ellp_engine_plan(int(kind), int(m), int(n_N), C.byref(opts) if opts is not None else None, int(avail), _p(out),
+                               out.size, err, 512)
+    return int(s), (dict(zip(PLAN_FIELDS, out.tolist())) if s == OPTIMAL else None), err.value.decode()
 
 
 def _p(a):

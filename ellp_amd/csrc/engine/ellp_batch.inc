@@ -556,6 +556,7 @@ static ellp_status batch_solve_impl(int kind, int64_t count, ellp_batch_item *it
 
     // ---- per item: the single call's checks, then what the batch cannot take (all before any HIP call)
     std::vector<BatchPlan> plan;
+    const int64_t mid_auto = plan_env().mid_auto_max;
     for (int64_t i = 0; i < count; ++i) {
         ellp_batch_item &it = items[i];
         it.err[0] = 0;
@@ -569,7 +570,7 @@ static ellp_status batch_solve_impl(int kind, int64_t count, ellp_batch_item *it
             // explicit-inverse engine or the certified hybrid is not run at all
             slds = small_lds_bytes(it.m, it.n_N);
             mlds = mid_lds_bytes(it.m, it.n_N);
-            loop = exact_loop(opts, bflip, false, opts.partial_segments, it.m, slds, mlds);
+            loop = exact_loop(opts, bflip, false, opts.partial_segments, it.m, slds, mlds, mid_auto);
             if (loop == EXACT_NONE) {
                 if (it.m > MID_MAX_M)
                     set_err(it.err, sizeof(it.err), "batch: the LU-per-iteration kernels of a batch take up to %d rows (this LP: m = %lld)",

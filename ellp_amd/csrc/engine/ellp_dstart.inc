@@ -177,10 +177,9 @@ __global__ __launch_bounds__(256) void k_ds_resync_apply(const DStartItem *items
 }
 
 // per item: its geometry (as engine_create_impl derives it from m) and the byte offsets of its arrays in the chunk's slab
-struct DsPlan {
+struct DsPlan : RebuildGeometry {
     int64_t item;
     int64_t m, n, nN, ld;
-    int splits, btran_rows, btran_tiles, upd_rows;
     size_t o_x, o_y, o_d, o_nb;                                                // read-back region
     size_t o_AB, o_AN, o_cB, o_c, o_b, o_lb, o_ub, o_kind, o_B, o_N, o_maxb;   // upload region
     size_t o_W0, o_W1, o_Cp, o_C, o_V, o_Vs, o_Wp, o_Pm, o_nzv, o_nzr, o_nzc, o_used, o_perm, o_up, o_tv, o_cand, o_xg;  // scratch
@@ -192,13 +191,7 @@ size_t ds_al(size_t b) { return (b + 255) / 256 * 256; }
 void ds_geometry(DsPlan &p) {
     const int64_t m = p.m;
     p.ld = round_up(m, 16);
-    const int64_t nrb64 = (m + 63) / 64;
-    const int sp = (int)((256 + nrb64 - 1) / nrb64);
-    p.splits = sp < 1 ? 1 : (sp > 8 ? 8 : sp);
-    p.upd_rows = m >= 1024 ? 4 : (m >= 256 ? 2 : 1);
-    p.btran_rows = (int)((m + 63) / 64);
-    if (p.btran_rows < 8) p.btran_rows = 8;
-    p.btran_tiles = (int)((m + p.btran_rows - 1) / p.btran_rows);
+    static_cast<RebuildGeometry &>(p) = rebuild_geometry(m);
     const int64_t m_ = p.m, n = p.n, nN = p.nN, ld = p.ld, nNa = nN > 0 ? nN : 1;
     size_t o = 0;
     p.o_x = o; o += ds_al(sizeof(double) * (size_t)n);
@@ -222,7 +215,7 @@ void ds_geometry(DsPlan &p) {
     o = 0;
     p.o_W0 = o; o += ds_al(sizeof(double) * (size_t)(m_ * ld));
     p.o_W1 = o; o += ds_al(sizeof(double) * (size_t)(m_ * ld));
-    p.o_Cp = o; o += ds_al(sizeof(double) * (size_t)(p.splits * m_ * BL_NB));
+    p.o_Cp = o; o += ds_al(sizeof(double) * (size_t)(p.bl_splits * m_ * BL_NB));
     p.o_C = o; o += ds_al(sizeof(double) * (size_t)(2 * m_ * BL_NB));
     p.o_V = o; o += ds_al(sizeof(double) * (size_t)(2 * m_ * BL_NB));
     p.o_Vs = o; o += ds_al(sizeof(double) * (size_t)(m_ * 16));
@@ -336,8 +329,8 @@ ellp_status ds_run_chunk(int device, hipStream_t stream, ellp_batch_item *items,
         a.V0 = reinterpret_cast<double *>(s + p.o_V); a.V1 = a.V0 + m * BL_NB;
         a.Vs = reinterpret_cast<double *>(s + p.o_Vs); a.Wp = reinterpret_cast<double *>(s + p.o_Wp);
         a.used = used; a.perm = perm; a.Pm = reinterpret_cast<int64_t *>(s + p.o_Pm); a.st = st; a.m = m; a.ld = ld;
-        a.splits = p.splits;
-        a.ksplit = (int)round_up((m + p.splits - 1) / p.splits, 16);
+        a.splits = p.bl_splits;
+        a.ksplit = (int)round_up((m + p.bl_splits - 1) / p.bl_splits, 16);
         a.eps = 0.0;  // a dual engine's rebuild guard (launch_refactor)
         r.ref = RefArgs{W0, W1, nullptr, dAB, used, perm, st, m, ld, p.upd_rows, 0.0};
         // BTRAN straight into y: the single call writes u (DevState::usel = 0 there) and copies all ld entries into y
@@ -464,16 +457,13 @@ extern "C" ellp_status ellp_batch_dual_phase1_start(int64_t count, ellp_batch_it
     ellp_default_opts(&opts);
     if (opts_in) opts = *opts_in;
     const bool bflip = (opts.flags & ELLP_FLAG_DUAL_BOUND_FLIPPING) != 0;
-    if (bflip && (opts.pipeline == 1 || opts.pipeline == 2 || opts.partial_segments > 1)) {
-        set_err(errbuf, errlen, "ELLP_FLAG_DUAL_BOUND_FLIPPING runs on the LU-per-iteration kernels (pipeline 0 or 3, up to 1,024 rows), "
-                                "not on the explicit-inverse pipelines 1 / 2");
-        return ELLP_ERR_ARG;
-    }
+    if (refuse_bflip_pipeline(opts, bflip, opts.partial_segments, errbuf, errlen)) return ELLP_ERR_ARG;
     if (const char *v = getenv("ELLP_REBUILD"); v && !strcmp(v, "columnwise")) {
         set_err(errbuf, errlen, "dual phase-1 start batch: ELLP_REBUILD=columnwise selects the column-by-column rebuild, which a batch does not run");
         return ELLP_ERR_ARG;
     }
     const double eps = opts.eps > 0.0 ? opts.eps : 1e-10;
+    const int64_t mid_auto = plan_env().mid_auto_max;
     // ---- per item: the single call's checks, then what the batch cannot take (all before any HIP call)
     std::vector<DsPlan> plan;
     for (int64_t i = 0; i < count; ++i) {
@@ -496,7 +486,7 @@ extern "C" ellp_status ellp_batch_dual_phase1_start(int64_t count, ellp_batch_it
             s = check_problem(ELLP_ENGINE_DUAL, it.m, it.n, it.n, it.A, it.c, it.b, it.bound_kind, it.lb, it.ub, zeros.data(),
                               it.B_index, it.m, it.N_index, Nb.data(), nN, zeros.data(), zeros.data(), it.err, sizeof(it.err));
             if (s == ELLP_OPTIMAL &&
-                exact_loop(opts, bflip, false, opts.partial_segments, it.m, small_lds_bytes(it.m, nN), mid_lds_bytes(it.m, nN)) == EXACT_NONE) {
+                exact_loop(opts, bflip, false, opts.partial_segments, it.m, small_lds_bytes(it.m, nN), mid_lds_bytes(it.m, nN), mid_auto) == EXACT_NONE) {
                 set_err(it.err, sizeof(it.err), "dual phase-1 start batch: these options run m = %lld on the explicit-inverse engine "
                                                 "(its start comes from another factorisation); pipeline 3, bound flipping or "
                                                 "ELLP_MID_AUTO_MAX select the LU-per-iteration kernels", (long long)it.m);
@@ -515,12 +505,7 @@ extern "C" ellp_status ellp_batch_dual_phase1_start(int64_t count, ellp_batch_it
     }
     if (plan.empty()) return ELLP_OPTIMAL;
     // the sub-panel width and k_bl_factor variant launch_refactor picks (every item has m <= 1,024, so the same for all)
-    const int bl_nt = (getenv("ELLP_BL_NT") && atoi(getenv("ELLP_BL_NT")) == 1024) ? 1024 : 512;
-    int nbw_max = 16;
-    if (const char *v = getenv("ELLP_BL_NBW"); v && v[0]) {
-        const int w = atoi(v);
-        if ((w == 8 || w == 4) && w < nbw_max) nbw_max = w;
-    }
+    const auto [bl_nt, nbw_max] = bl_factor_variant(MID_MAX_M);
     size_t budget = (size_t)2 << 30;
     if (const char *v = getenv("ELLP_BATCH_MAX_BYTES"); v && v[0] && atoll(v) > 0 && (size_t)atoll(v) < budget) budget = (size_t)atoll(v);
     int dev = opts.device;

@@ -53,7 +53,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <mutex>
+#include <optional>
 #include <vector>
 
 #include "ellp_hip.h"
@@ -2858,6 +2860,20 @@ __global__ __launch_bounds__(256) void k_rephase(const double *c, const uint8_t 
 #include "ellp_se.inc"
 #include "ellp_exact.inc"
 
+// ---- host side from here on
+void set_err(char *errbuf, size_t len, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+void set_err(char *errbuf, size_t len, const char *fmt, ...) {
+    if (!errbuf || !len) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(errbuf, len, fmt, ap);
+    va_end(ap);
+}
+
+inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+#include "ellp_plan.inc"
+
 }  // namespace
 
 // ====================================================================== host side
@@ -2880,10 +2896,10 @@ struct HostSet {
     DevState *h_look = nullptr;
 };
 
-struct ellp_engine {
+struct ellp_engine : EnginePlan {  // the fields creation decides are the plan's (ellp_plan.inc)
     HostSet host_set;
     int kind = 0;
-    int64_t m = 0, n = 0, n_c = 0, nN = 0, ld = 0;
+    int64_t m = 0, n = 0, n_c = 0, nN = 0;
     double eps = 1e-10;
     ellp_opts opts{};
     int device = 0;
@@ -2903,18 +2919,13 @@ struct ellp_engine {
     double *bl_Cpart = nullptr, *bl_C = nullptr, *bl_V = nullptr, *bl_Vs = nullptr, *bl_Wp = nullptr, *bl_nzval = nullptr;
     int64_t *bl_Pm = nullptr, *bl_nzrow = nullptr;
     int32_t *bl_nzcnt = nullptr;
-    int bl_splits = 1;
     uint64_t rebuild_shortcuts = 0;
     double *aq_save = nullptr, *bmin = nullptr;  // two-launch pipeline: parked entering column, row-block minima of lambda
     bool hst_fresh = false;  // h_st is the device state as the previous call (an ellp_engine_run) left it: no read-back needed
     bool obj_fresh = false;  // h_st->obj is c . x of the state in h_st (primal; see ellp_engine_run / fill_stats)
-    bool lagged = false;    // two launches per primal iteration (ellp_lagged.inc)
-    bool dual_fused = false;  // dual: FTRAN and eta update in one pass over B^-1 (ellp_dualfu.inc)
-    bool dual_fold = false;   // ... and its closing work done by the next pricing launch (no tiny-pivot maintenance)
     bool dual_open = false;   // a fused iteration may still be open on the device (launch_dual_close)
     unsigned long long dual_seq = 0;  // number of the dual iteration being enqueued
     bool lag_open = false;  // a k_ftran_eta has been enqueued whose ratio test no kernel has folded yet
-    size_t price2_lds = 0;
     double *upart = nullptr, *y = nullptr, *dd = nullptr, *lam = nullptr, *resid = nullptr, *T = nullptr;
     uint64_t refreshes = 0, maint_requests = 0;
     double last_residual = 0.0;
@@ -2926,8 +2937,7 @@ struct ellp_engine {
     DevState *h_look = nullptr;  // pinned, 2 slots: status read-backs of the look-ahead loop
     hipEvent_t look_ev[2] = {nullptr, nullptr};
     // pricing shard (column-block sharding across ranks; world = 1 on a single GPU)
-    int rank = 0, world = 1, nbs = 1;
-    int64_t seg = 0;
+    int rank = 0, world = 1;
     hipStream_t own_stream = nullptr;
     bool need_dleave = true;
     // column-sharded storage of A_N (ellp_shard.inc)
@@ -2951,40 +2961,24 @@ struct ellp_engine {
     std::vector<void *> ipc_opened;
     uint64_t full_exchanges = 0, column_requests = 0;
     // small LPs (m <= 128): the reference's LU-per-iteration loop in one persistent workgroup (ellp_small.inc)
-    bool small = false;      // run() uses k_small
     bool w_valid = true;     // the explicit inverse W (not kept by k_small) matches A_B
     bool exact_large_only = false;  // after a redo above 1,024 rows: every loop body on a fresh LU (run_exact_large), until the next phase
-    bool exact_large_always = false;  // pipeline 3 above 1,024 rows: that loop for good, from the first slice on and in every phase
-    size_t small_lds = 0;
-    int pp_P = 0;            // partial pricing: number of segments (<= 1: off)
-    int64_t pp_S = 0;        // positions per segment
     char *slab = nullptr;  // see dmalloc
     size_t slab_size = 0, slab_used = 0;
     unsigned long long *small_stamps = nullptr;  // ELLP_SMALL_STAMPS: per-phase tick sums of k_small, printed at destroy
-    int small_nt = SMALL_THREADS;  // workgroup size of k_small for this LP (small_threads)
     // unit columns (PriceArgs::vs_row): per VARIABLE, made once at creation; null = the pricing kernels stream everything
     int32_t *vs_row = nullptr;
     double *vs_val = nullptr;
     uint8_t *pos_hint = nullptr;
-    int dual_maxviol = 0;  // ELLP_FLAG_DUAL_MAX_VIOLATION
-    int dual_bflip = 0;    // ELLP_FLAG_DUAL_BOUND_FLIPPING: the long-step ratio test (LU-per-iteration kernels only)
     long long *bf_list = nullptr;  // ... the positions passed in an iteration (nN entries)
-    bool se = false;       // ELLP_FLAG_PRIMAL_STEEPEST_EDGE (ellp_se.inc): three launches + one transposed GEMV per iteration
     double *se_gamma = nullptr, *se_rho = nullptr, *se_v = nullptr;
     double *se_vpart = nullptr;  // per row block of k_update2: its share of v = B^-T d (null: the separate transposed GEMV)
     int64_t unit_columns = 0;  // how many variables have one (diagnostics)
     // 128 < m <= 1024: the same loop with its factors in global memory (ellp_mid.inc); `small` is set as well, so
     // that everything that asks "is there an explicit inverse" keeps working unchanged
-    bool mid = false;
-    size_t mid_lds = 0;
-    int mid_nt = 0;
-    int64_t ldn = 0;
     double *LUa = nullptr, *Ut = nullptr, *A_Nt = nullptr;
     // certified hybrid: the explicit-inverse loop with a pivot guard; every terminal status and every
     // guarded iteration is handed to the LU-per-iteration kernel (k_mid) for up to exact_K iterations (exact_takeover)
-    bool hybrid = false;
-    double guard_abs = 0.0;
-    int exact_K = 8;
     uint64_t hy_guards = 0, hy_certs = 0, hy_disagree = 0, hy_exact_iters = 0, hy_rebuilds = 0, hy_redos = 0;
     // "certify or redo": the start of the phase (taken at the first run() after creation / a hand-off), so that a solve whose
     // end point violates an invariant of the reference's loop can be repeated by the exact kernel from where it began
@@ -2998,7 +2992,6 @@ struct ellp_engine {
     double *inv_out = nullptr;
     // above 1,024 rows (ellp_exact.inc): terminal statuses are certified by one iteration whose u / rho and d come from a fresh
     // LU of the basis (no pivot guard, no redo at these sizes)
-    bool cert_large = false;
     bool guard_off = false;   // an exact iteration is being enqueued: its pivots are the reference's, however small
     bool luw_ready = false;
     EllpLuWork luw{};
@@ -3009,26 +3002,12 @@ struct ellp_engine {
     // the LP is a "box problem" — every bound TwoSided or Fixed and b = 0: the shape of DualPhase1's LP (dual_problem.rs:89-131),
     // whose dual objective is minus the dual infeasibility of the original problem, i.e. <= 0 and = 0 at a feasible end
     bool box_problem = false;
-    double ill_tol = 0.0;  // reactive maintenance threshold (small LPs only, see ellp_engine_create)
     int maint_chain = 0;   // > 0: refresh again after the next single iteration
-    int drift_every = 0;   // iterations between two drift checks of B^-1 (0: off)
-    double drift_tol = 0.0;
     uint64_t since_drift = 0, drift_checks = 0;
-    // launch geometry
-    int cpb = 1, nblocks = 1, priceT = 1;
-    bool price_nt = false;
-    bool price_wave = false;  // wave-per-column pricing (cache-resident A_N, rows long enough to fill a wave)
-    int upd_rows = 4, upd_blocks = 1;    // refactorisation kernels (<= UPD_ROWS rows per block)
-    int upd2_rows = 4, upd2_blocks = 1;  // k_update2 (<= 2*UPD_ROWS)
-    int ftran_blocks = 1;
-    int btran_tiles = 1, btran_rows = 1;
-    int upd_stage = 1;
-    size_t upd_lds = 0, ftran_lds = 0;
     // loop bookkeeping
     uint64_t since_refactor = 0, since_btran = 0;
     uint64_t enqueued = 0;  // iterations enqueued since the counters were last reconciled with DevState::iters
     uint64_t iters_seen = 0;  // DevState::iters at that moment
-    int refactor_period = 0;
     int btran_refresh = 32;
     uint64_t refactors = 0;
     bool u_valid = false;
@@ -3048,15 +3027,6 @@ struct ellp_engine {
 };
 
 namespace {
-
-void set_err(char *errbuf, size_t len, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
-void set_err(char *errbuf, size_t len, const char *fmt, ...) {
-    if (!errbuf || !len) return;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(errbuf, len, fmt, ap);
-    va_end(ap);
-}
 
 #define HIPCHK(expr)                                                                              \
     do {                                                                                          \
@@ -3111,8 +3081,6 @@ inline void replace_alloc(ellp_engine *e, void *old, void *neu) {
         }
     e->allocs.push_back(neu);  // `old` lives in the slab
 }
-
-inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 struct Prof {
     ellp_engine *e;
@@ -3282,13 +3250,15 @@ void launch_update2(ellp_engine *e, int update_u) {
     else hipLaunchKernelGGL((k_update2<MODE, 0>), g, b, lds, e->stream, a);
 }
 
-void launch_btran(ellp_engine *e) {
-    BtranArgs a{e->W, e->W2, e->c_B, e->upart, e->u, e->u + e->ld, e->st, e->m, e->ld, e->btran_rows, e->btran_tiles};
+// out = B^-T v (two buffers of out: DevState::usel; the same one twice where there is no other)
+void launch_btran(ellp_engine *e, const double *v, double *out0, double *out1) {
+    BtranArgs a{e->W, e->W2, v, e->upart, out0, out1, e->st, e->m, e->ld, e->btran_rows, e->btran_tiles};
     const int64_t half = e->ld >> 1;
     dim3 g((unsigned)((half + 255) / 256), (unsigned)e->btran_tiles);
     hipLaunchKernelGGL(k_btran_part, g, dim3(256), 0, e->stream, a);
     hipLaunchKernelGGL(k_btran_reduce, dim3((unsigned)((e->ld + 255) / 256)), dim3(256), 0, e->stream, a);
 }
+void launch_btran(ellp_engine *e) { launch_btran(e, e->c_B, e->u, e->u + e->ld); }  // u = B^-T c_B
 
 void launch_refactor_columnwise(ellp_engine *e) {
     Prof p(e, ELLP_K_REFACTOR);
@@ -3306,6 +3276,21 @@ void launch_refactor_columnwise(ellp_engine *e) {
     e->refactors += 1;
     e->since_refactor = 0;
     e->u_valid = false;
+}
+
+// the k_bl_factor variant of a rebuild of m rows: workgroup size and sub-panel width (read per rebuild)
+struct BlFactorVariant {
+    int bl_nt, nbw_max;
+};
+BlFactorVariant bl_factor_variant(int64_t m) {
+    BlFactorVariant v;
+    v.bl_nt = (getenv("ELLP_BL_NT") && atoi(getenv("ELLP_BL_NT")) == 1024) ? 1024 : 512;
+    v.nbw_max = m <= 2048 ? 16 : (m <= 4096 ? 8 : 4);
+    if (const char *s = getenv("ELLP_BL_NBW"); s && s[0]) {  // tests: a narrower sub-panel than the size needs
+        const int w = atoi(s);
+        if ((w == 8 || w == 4) && w < v.nbw_max) v.nbw_max = w;
+    }
+    return v;
 }
 
 // Blocked rebuild (ellp_rebuild.inc).  One host synchronisation: after the probe for a generalised
@@ -3346,12 +3331,7 @@ void launch_refactor(ellp_engine *e) {
     // ---- general case
     RefArgs ra{e->W, e->W2, e->d, e->A_B, e->used, e->perm, e->st, e->m, e->ld, e->upd_rows, a.eps};
     hipLaunchKernelGGL(k_ref_init, dim3(1024), dim3(256), 0, e->stream, ra);
-    const int bl_nt = (getenv("ELLP_BL_NT") && atoi(getenv("ELLP_BL_NT")) == 1024) ? 1024 : 512;
-    int nbw_max = m <= 2048 ? 16 : (m <= 4096 ? 8 : 4);
-    if (const char *v = getenv("ELLP_BL_NBW"); v && v[0]) {  // tests: a narrower sub-panel than the size needs
-        const int w = atoi(v);
-        if ((w == 8 || w == 4) && w < nbw_max) nbw_max = w;
-    }
+    const auto [bl_nt, nbw_max] = bl_factor_variant(m);
     for (int64_t k0 = 0; k0 < m; k0 += BL_NB) {
         a.k0 = (int)k0;
         a.nbc = (int)((m - k0) < BL_NB ? (m - k0) : BL_NB);
@@ -3405,45 +3385,29 @@ void launch_refresh(ellp_engine *e) {
     e->u_valid = false;
 }
 
-// Default maintenance period, from a cost model: a refresh costs T_r ~ 2*(2 m^3)/25 TFLOP/s + 60 us
-// (two GEMM launches, a residual read-back with a host sync), an iteration T_i ~ (8 ld |N| + 24 m ld)
-// / 5 TB/s + 15 us, and the period is the smallest one whose refreshes stay within a BUDGET of the
-// loop time: 30 % up to m = 1024, falling linearly to 3 % at m = 2000 and beyond (config 3: 1000
-// iterations, as measured), never below 16.  Why so generous on small and mid-size LPs: the reference
-// factorises afresh every iteration, and the error of B^-1 a_q is cond(A_B) times that of B^-1 — a
-// tall 500 x 100 LP of the benign synthetic family left the oracle's path after 166 pivots with B^-1
-// untouched and after 162 with a period of 62 (x off by 2e-9 against EPS = 1e-10; the error grew
-// 25-fold within 9 pivots at cond 6e4), and stays on it for 1200 pivots with a period of 16.  Beyond
-// the model, the drift monitor (k_drift_part) asks for a refresh when the LP needs one.
-int64_t default_period(const ellp_engine *e) {
-    const double m = (double)e->m, ld = (double)e->ld, nN = (double)(e->nN > 0 ? e->nN : 1);
-    const double t_refresh = 4.0 * m * m * m / 25e12 + 60e-6;
-    const double t_iter = (8.0 * ld * nN + 24.0 * m * ld) / 5e12 + 15e-6;
-    double budget = 0.30;
-    if (m > 1024.0) budget = m >= 2000.0 ? 0.03 : 0.30 - 0.27 * (m - 1024.0) / 976.0;
-    int64_t p = (int64_t)std::ceil(t_refresh / (budget * t_iter));
-    if (p < 16) p = 16;
-    if (p > 1000) p = 1000;
-    return p;
-}
-
 // periodic maintenance of B^-1: Newton-Schulz refresh, full rebuild only if that is not safe
 void launch_dleave(ellp_engine *e);
 void launch_resync(ellp_engine *e, int force);
 
-// x_B from the freshly maintained B^-1 (see k_resync_part)
-void launch_resync(ellp_engine *e, int force) {
-    if (e->nN <= 0) return;
-    if (e->colshard) return;  // b - A_N x_N would need every rank's columns (a reduction over the ranks): not done
+// tvec = b - A_N x_N: the front of the resync, and of the primal phase-1 start (its b~)
+ResyncArgs launch_resync_rhs(ellp_engine *e, int force) {
     ResyncArgs a{e->A_N, e->W, e->W2, e->b_dev, e->x, e->xg, e->tvec, e->upart, e->cand, e->maxbits, e->B_index,
                  e->N_index, e->st, e->m, e->ld, e->nN, 0, e->btran_tiles, force};
-    (void)hipMemsetAsync(e->maxbits, 0, 2 * sizeof(unsigned long long), e->stream);
     a.cols_per_tile = (int)((e->nN + e->btran_tiles - 1) / e->btran_tiles);
     const int64_t half = e->ld >> 1;
     hipLaunchKernelGGL(k_resync_gather, dim3((unsigned)((e->nN + 255) / 256)), dim3(256), 0, e->stream, a);
     hipLaunchKernelGGL(k_resync_part, dim3((unsigned)((half + 255) / 256), (unsigned)e->btran_tiles), dim3(256), 0,
                        e->stream, a);
     hipLaunchKernelGGL(k_resync_rhs, dim3((unsigned)((e->ld + 255) / 256)), dim3(256), 0, e->stream, a);
+    return a;
+}
+
+// x_B from the freshly maintained B^-1 (see k_resync_part)
+void launch_resync(ellp_engine *e, int force) {
+    if (e->nN <= 0) return;
+    if (e->colshard) return;  // b - A_N x_N would need every rank's columns (a reduction over the ranks): not done
+    (void)hipMemsetAsync(e->maxbits, 0, 2 * sizeof(unsigned long long), e->stream);
+    const ResyncArgs a = launch_resync_rhs(e, force);
     hipLaunchKernelGGL(k_resync_xb, dim3((unsigned)((e->m + 3) / 4)), dim3(256), 0, e->stream, a);
     hipLaunchKernelGGL(k_resync_apply, dim3((unsigned)((e->m + 255) / 256)), dim3(256), 0, e->stream, a);
     if (e->kind == ELLP_ENGINE_DUAL) launch_dleave(e);  // the leaving row is chosen from x (dual…:200-236)
@@ -3714,10 +3678,7 @@ void launch_primal_iteration(ellp_engine *e) {
     }
     if (e->se && !e->se_vpart) {  // v = B^-T d from the inverse this iteration's FTRAN used: the weight update of the NEXT pricing launch
         Prof p(e, ELLP_K_BTRAN);
-        BtranArgs a{e->W, e->W2, e->d, e->upart, e->se_v, e->se_v, e->st, e->m, e->ld, e->btran_rows, e->btran_tiles};
-        const int64_t half = e->ld >> 1;
-        hipLaunchKernelGGL(k_btran_part, dim3((unsigned)((half + 255) / 256), (unsigned)e->btran_tiles), dim3(256), 0, e->stream, a);
-        hipLaunchKernelGGL(k_btran_reduce, dim3((unsigned)((e->ld + 255) / 256)), dim3(256), 0, e->stream, a);
+        launch_btran(e, e->d, e->se_v, e->se_v);
     }
     launch_drift_check(e);
     {
@@ -4093,23 +4054,6 @@ static ellp_status check_problem(int kind, int64_t m, int64_t n, int64_t n_c, co
     return ELLP_OPTIMAL;
 }
 
-// Which LU-per-iteration loop a single call runs for the whole solve: EXACT_SMALL (k_small), EXACT_MID (k_mid) or
-// EXACT_NONE (the explicit-inverse engine, alone or as the certified hybrid).  The exact loop ALONE is the default up to
-// m <= 128 (k_small, factors in LDS, 1-5 x slower per iteration than the explicit-inverse engine).  Above that the default
-// is the certified hybrid; pipeline = 3, the dual's bound flipping or ELLP_MID_AUTO_MAX still select k_mid for whole
-// solves up to 1024 rows (15-40 x slower).  ellp_engine_create and ellp_batch_solve_with_initial ask this alone.
-enum ExactLoop { EXACT_NONE = 0, EXACT_SMALL = 1, EXACT_MID = 2 };
-static ExactLoop exact_loop(const ellp_opts &o, bool dual_bflip, bool se, int pp_P, int64_t m, size_t small_lds, size_t mid_lds) {
-    const int pl = o.pipeline;
-    int64_t mid_auto = SMALL_MAX_M;
-    if (const char *ev = getenv("ELLP_MID_AUTO_MAX")) mid_auto = atoll(ev);
-    const bool fits = small_lds > 0 || mid_lds > 0;
-    const bool wanted = pp_P <= 1 && !se && (pl == 3 || dual_bflip || (pl == 0 && o.refactor_period <= 0 && o.btran_mode == 0 &&
-                                                                          o.profile == 0 && (m <= SMALL_MAX_M || m <= mid_auto)));
-    if (!wanted || !fits) return EXACT_NONE;
-    return small_lds > 0 ? EXACT_SMALL : EXACT_MID;
-}
-
 // The device state a fresh engine starts from: running, no pivot yet, the objective of the starting point
 static DevState initial_state(int kind, int64_t m, int64_t n_c, int64_t n_N, const double *c, const double *b,
                               const uint8_t *bound_kind, const double *lb, const double *ub, const double *x, const double *y,
@@ -4149,461 +4093,243 @@ static bool dual_start_feasible(int64_t n_N, const int64_t *N_index, const uint8
     return true;
 }
 
-static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c,
-                               const double *b, const uint8_t *bound_kind, const double *lb, const double *ub,
-                               const double *x, const int64_t *B_index, int64_t n_B, const int64_t *N_index,
-                               const uint8_t *N_bound, int64_t n_N, const double *y, const double *d,
-                               const ellp_opts *opts_in, ellp_engine **out, char *errbuf, size_t errlen,
-                               int64_t n_explicit, bool build_phase1) {
-    if (!out) return ELLP_ERR_ARG;
-    *out = nullptr;
-    if (errbuf && errlen) errbuf[0] = 0;
-    auto t0 = std::chrono::steady_clock::now();
-    {
-        const ellp_status cs = check_problem(kind, m, n, n_c, A, c, b, bound_kind, lb, ub, x, B_index, n_B, N_index, N_bound, n_N,
-                                             y, d, errbuf, errlen);
-        if (cs != ELLP_OPTIMAL) return cs;
-    }
+// ---- creation: stages over an engine that already carries its plan.  Each returns a status (HIPCHK fills errbuf); the
+// owner in engine_create_impl destroys the engine on an early return.
 
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_err(errbuf, errlen, "no HIP device available (this library has no CPU path)");
-        return ELLP_ERR_DEVICE;
-    }
-    ellp_engine *e = new ellp_engine();
-    ellp_opts defaults;
-    ellp_default_opts(&defaults);
-    e->opts = opts_in ? *opts_in : defaults;
-    e->eps = e->opts.eps > 0.0 ? e->opts.eps : 1e-10;
-    e->kind = kind;
-    e->m = m;
-    e->n = n;
-    e->n_c = n_c;
-    e->nN = n_N;
-    e->ld = round_up(m, 16);
+static ellp_status create_host_set(ellp_engine *e, char *errbuf, size_t errlen) {
     int dev = e->opts.device;
-    if (dev < 0) {
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    }
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
     e->device = dev;
-
-#define ECHK(expr)                                                                                   \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess) {                                                                      \
-            set_err(errbuf, errlen, "HIP error %s at %s:%d (%s)", hipGetErrorString(_e), __FILE__,   \
-                    __LINE__, #expr);                                                                \
-            ellp_engine_destroy(e);                                                                  \
-            return ELLP_ERR_DEVICE;                                                                  \
-        }                                                                                            \
-    } while (0)
-
-    ECHK(hipSetDevice(dev));
-    ECHK(host_set_acquire(dev, &e->host_set));
+    HIPCHK(hipSetDevice(dev));
+    HIPCHK(host_set_acquire(dev, &e->host_set));
     e->stream = e->host_set.stream;
     e->own_stream = e->stream;
     e->h_st = e->host_set.h_st;
     e->h_look = e->host_set.h_look;
-    const int64_t ld = e->ld;
-    const int64_t nNa = n_N > 0 ? n_N : 1;
-    // geometry
-    {
-        // A_N far beyond the Infinity Cache -> stream it with nt loads from ~2048 blocks; otherwise
-        // ~1024 blocks (the entering fold stages one maximum per block).  tools/price_bench.hip
-        e->price_nt = 8.0 * (double)ld * (double)nNa > 160e6;
-        int64_t cpb = e->price_nt ? (n_N + 2047) / 2048 : (n_N + 1023) / 1024;
-        if (cpb < 1) cpb = 1;
-        if (cpb > 64) cpb = 64;
-        // wave-per-column pricing: cache-resident A_N, rows that fill a wave, and >= 5 columns per
-        // block so that all four waves of a block have a column pair (measured at C3/C4: 18.9 -> 18.0
-        // and 15.8 -> 14.3 us; the number of columns per block between 5 and 16 makes no difference)
-        e->price_wave = !e->price_nt && ld >= 512 && cpb >= 5;
-        e->cpb = (int)cpb;
-        e->nblocks = (int)((nNa + cpb - 1) / cpb);
-        const int64_t need = ((ld >> 1) + 255) / 256;
-        e->priceT = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 16;
-        if (need > 16) {
-            set_err(errbuf, errlen, "m = %lld exceeds this build's pricing tile (m <= 8192)", (long long)m);
-            ellp_engine_destroy(e);
-            return ELLP_ERR_ARG;
-        }
-        e->upd_rows = m >= 1024 ? 4 : (m >= 256 ? 2 : 1);
-        e->upd_blocks = (int)((m + e->upd_rows - 1) / e->upd_rows);
-        // 8 rows per block once m is large: half as many blocks re-stage the fold inputs (13 m bytes
-        // each) and re-read the pivot row; measured -9 us of 58 at m=4000, +0.4 us at m=2000
-        e->upd2_rows = m >= 3072 ? 8 : e->upd_rows;
-        e->upd2_blocks = (int)((m + e->upd2_rows - 1) / e->upd2_rows);
-        int64_t fw = m < 2048 ? m : 2048;
-        e->ftran_blocks = (int)((fw + 3) / 4);
-        e->btran_rows = (int)((m + 63) / 64);
-        if (e->btran_rows < 8) e->btran_rows = 8;
-        e->btran_tiles = (int)((m + e->btran_rows - 1) / e->btran_rows);
-        const int nchunks = (int)((m + 63) >> 6);
-        const size_t staged = sizeof(double) * (size_t)nchunks + (size_t)m * (8 + 4 + 1) + 16;
-        if (staged <= 40 * 1024) {  // keep >= 4 update blocks per CU resident
-            e->upd_stage = 1;
-            e->upd_lds = staged;
-        } else {
-            e->upd_stage = 0;
-            e->upd_lds = sizeof(double) * (size_t)nchunks + 16;
-        }
-        e->ftran_lds = sizeof(double) * (size_t)e->nblocks + 16;
-        e->refactor_period = e->opts.refactor_period > 0 ? e->opts.refactor_period : 0;
-        // reactive maintenance after a tiny pivot (|alpha_r| < ill_tol * max|alpha|): small LPs, and steepest edge at any
-        // size — its longer steps meet such pivots often enough that at config 5 a variable once left the basis 0.03
-        // off its bound between two looks of the drift monitor; costs the look-ahead of the run loop
-        const bool se_wanted = kind == ELLP_ENGINE_PRIMAL && (e->opts.flags & ELLP_FLAG_PRIMAL_STEEPEST_EDGE);
-        e->ill_tol = (m <= 512 || se_wanted) ? 1e-3 : 0.0;
-        if (const char *it = getenv("ELLP_ILL_TOL")) e->ill_tol = atof(it);  // diagnostics
-        // drift monitor: only where refreshes are rare (period > 64), four checks per period; one GEMV
-        // over A_B + a one-block fold, ~70 us at config 3 (0.7 % of the loop)
-        {
-            const int64_t p = e->refactor_period > 0 ? e->refactor_period : default_period(e);
-            e->drift_every = p > 64 ? (int)(p / 4 > 64 ? p / 4 : 64) : 0;
-        }
-        e->drift_tol = 1e-10;  // a backstop: config 3 drifts to 1.4e-11 in 3000 updates without any refresh
-        if (const char *v = getenv("ELLP_DRIFT_EVERY"); v && v[0]) e->drift_every = atoi(v);  // diagnostics
-        if (const char *v = getenv("ELLP_DRIFT_TOL"); v && v[0]) e->drift_tol = atof(v);        // diagnostics
-    }
+    return ELLP_OPTIMAL;
+}
 
-    ECHK(dmalloc(e, &e->A_B, (size_t)(ld * m)));
-    ECHK(dmalloc(e, &e->A_N, (size_t)(ld * nNa)));
-    ECHK(dmalloc(e, &e->W, (size_t)(m * ld)));
-    ECHK(dmalloc(e, &e->W2, (size_t)(m * ld)));
-    ECHK(dmalloc(e, &e->c_B, (size_t)m));
-    ECHK(dmalloc(e, &e->c_N, (size_t)nNa));
-    ECHK(dmalloc(e, &e->u, (size_t)(2 * ld)));  // two buffers (DevState::usel): the two-launch pipeline reads one, writes the other
-    ECHK(dmalloc(e, &e->aq_save, (size_t)ld));
-    ECHK(dmalloc(e, &e->bmin, (size_t)(2 * m)));  // smallest | second smallest per row block
-    ECHK(dmalloc(e, &e->binfo, (size_t)m));
+static ellp_status create_core_arrays(ellp_engine *e, char *errbuf, size_t errlen) {
+    const int64_t m = e->m, ld = e->ld, n_c = e->n_c, nNa = e->nN > 0 ? e->nN : 1;
+    HIPCHK(dmalloc(e, &e->A_B, (size_t)(ld * m)));
+    HIPCHK(dmalloc(e, &e->A_N, (size_t)(ld * nNa)));
+    HIPCHK(dmalloc(e, &e->W, (size_t)(m * ld)));
+    HIPCHK(dmalloc(e, &e->W2, (size_t)(m * ld)));
+    HIPCHK(dmalloc(e, &e->c_B, (size_t)m));
+    HIPCHK(dmalloc(e, &e->c_N, (size_t)nNa));
+    HIPCHK(dmalloc(e, &e->u, (size_t)(2 * ld)));  // two buffers (DevState::usel): the two-launch pipeline reads one, writes the other
+    HIPCHK(dmalloc(e, &e->aq_save, (size_t)ld));
+    HIPCHK(dmalloc(e, &e->bmin, (size_t)(2 * m)));  // smallest | second smallest per row block
+    HIPCHK(dmalloc(e, &e->binfo, (size_t)m));
     e->trace_len = e->opts.trace_len > 0 ? e->opts.trace_len : 0;
     if (e->trace_len > 0) {
-        ECHK(dmalloc(e, &e->trace_obj, (size_t)e->trace_len));
-        ECHK(dmalloc(e, &e->trace_it, (size_t)e->trace_len));
-        ECHK(hipMemsetAsync(e->trace_it, 0, sizeof(unsigned long long) * (size_t)e->trace_len, e->stream));
+        HIPCHK(dmalloc(e, &e->trace_obj, (size_t)e->trace_len));
+        HIPCHK(dmalloc(e, &e->trace_it, (size_t)e->trace_len));
+        HIPCHK(hipMemsetAsync(e->trace_it, 0, sizeof(unsigned long long) * (size_t)e->trace_len, e->stream));
     }
-    if (m <= 8192) {  // blocked rebuild (k_bl_factor keeps m / 1024 rows per thread)
-        const int64_t nrb64 = (m + 63) / 64;
-        int sp = (int)((256 + nrb64 - 1) / nrb64);
-        e->bl_splits = sp < 1 ? 1 : (sp > 8 ? 8 : sp);
-        ECHK(dmalloc(e, &e->bl_Cpart, (size_t)(e->bl_splits * m * BL_NB)));
-        ECHK(dmalloc(e, &e->bl_C, (size_t)(2 * m * BL_NB)));
-        ECHK(dmalloc(e, &e->bl_V, (size_t)(2 * m * BL_NB)));
-        ECHK(dmalloc(e, &e->bl_Vs, (size_t)(m * 16)));
-        ECHK(dmalloc(e, &e->bl_Wp, (size_t)(BL_NB * ld)));
-        ECHK(dmalloc(e, &e->bl_Pm, (size_t)BL_NB));
-        ECHK(dmalloc(e, &e->bl_nzval, (size_t)m));
-        ECHK(dmalloc(e, &e->bl_nzrow, (size_t)m));
-        ECHK(dmalloc(e, &e->bl_nzcnt, (size_t)m));
-    }
-    e->nbs = e->nblocks;
-    e->seg = 2 * (int64_t)e->nbs + 2 * (int64_t)e->nbs * e->cpb;
-    ECHK(dmalloc(e, &e->X, (size_t)e->seg));
-    ECHK(dmalloc(e, &e->x, (size_t)n_c));
-    ECHK(dmalloc(e, &e->lb, (size_t)n_c));
-    ECHK(dmalloc(e, &e->ub, (size_t)n_c));
-    ECHK(dmalloc(e, &e->kindv, (size_t)n_c));
-    ECHK(dmalloc(e, &e->d, (size_t)ld));
-    ECHK(dmalloc(e, &e->b_dev, (size_t)ld));
-    ECHK(dmalloc(e, &e->tvec, (size_t)ld));
-    ECHK(dmalloc(e, &e->cand, (size_t)ld));
-    ECHK(dmalloc(e, &e->maxbits, (size_t)2));
-    ECHK(dmalloc(e, &e->xg, (size_t)nNa));
-    ECHK(hipMemsetAsync(e->b_dev, 0, sizeof(double) * (size_t)ld, e->stream));
-    ECHK(dmalloc(e, &e->upart, (size_t)(e->btran_tiles * ld)));
-    ECHK(dmalloc(e, &e->B_index, (size_t)m));
-    ECHK(dmalloc(e, &e->N_index, (size_t)nNa));
-    ECHK(dmalloc(e, &e->Nb, (size_t)nNa));
-    ECHK(dmalloc(e, &e->perm, (size_t)m));
-    ECHK(dmalloc(e, &e->used, (size_t)m));
-    ECHK(dmalloc(e, &e->lam, (size_t)m));
-    ECHK(dmalloc(e, &e->bidx, (size_t)m));
-    ECHK(dmalloc(e, &e->dpos, (size_t)m));
+    // blocked rebuild (k_bl_factor keeps m / 1024 rows per thread: up to PLAN_MAX_M rows)
+    HIPCHK(dmalloc(e, &e->bl_Cpart, (size_t)(e->bl_splits * m * BL_NB)));
+    HIPCHK(dmalloc(e, &e->bl_C, (size_t)(2 * m * BL_NB)));
+    HIPCHK(dmalloc(e, &e->bl_V, (size_t)(2 * m * BL_NB)));
+    HIPCHK(dmalloc(e, &e->bl_Vs, (size_t)(m * 16)));
+    HIPCHK(dmalloc(e, &e->bl_Wp, (size_t)(BL_NB * ld)));
+    HIPCHK(dmalloc(e, &e->bl_Pm, (size_t)BL_NB));
+    HIPCHK(dmalloc(e, &e->bl_nzval, (size_t)m));
+    HIPCHK(dmalloc(e, &e->bl_nzrow, (size_t)m));
+    HIPCHK(dmalloc(e, &e->bl_nzcnt, (size_t)m));
+    HIPCHK(dmalloc(e, &e->X, (size_t)e->seg));
+    HIPCHK(dmalloc(e, &e->x, (size_t)n_c));
+    HIPCHK(dmalloc(e, &e->lb, (size_t)n_c));
+    HIPCHK(dmalloc(e, &e->ub, (size_t)n_c));
+    HIPCHK(dmalloc(e, &e->kindv, (size_t)n_c));
+    HIPCHK(dmalloc(e, &e->d, (size_t)ld));
+    HIPCHK(dmalloc(e, &e->b_dev, (size_t)ld));
+    HIPCHK(dmalloc(e, &e->tvec, (size_t)ld));
+    HIPCHK(dmalloc(e, &e->cand, (size_t)ld));
+    HIPCHK(dmalloc(e, &e->maxbits, (size_t)2));
+    HIPCHK(dmalloc(e, &e->xg, (size_t)nNa));
+    HIPCHK(hipMemsetAsync(e->b_dev, 0, sizeof(double) * (size_t)ld, e->stream));
+    HIPCHK(dmalloc(e, &e->upart, (size_t)(e->btran_tiles * ld)));
+    HIPCHK(dmalloc(e, &e->B_index, (size_t)m));
+    HIPCHK(dmalloc(e, &e->N_index, (size_t)nNa));
+    HIPCHK(dmalloc(e, &e->Nb, (size_t)nNa));
+    HIPCHK(dmalloc(e, &e->perm, (size_t)m));
+    HIPCHK(dmalloc(e, &e->used, (size_t)m));
+    HIPCHK(dmalloc(e, &e->lam, (size_t)m));
+    HIPCHK(dmalloc(e, &e->bidx, (size_t)m));
+    HIPCHK(dmalloc(e, &e->dpos, (size_t)m));
     // m row maxima (k_inv_residual), or one maximum per 128 x 128 tile of the refresh's first GEMM: more than m above 16,384 rows
     const int64_t resid_tiles = ((m + 127) / 128) * ((m + 127) / 128);
     const size_t resid_len = (size_t)std::max<int64_t>(std::max<int64_t>(m, 4096), resid_tiles);
-    ECHK(dmalloc(e, &e->resid, resid_len));
-    ECHK(hipMemsetAsync(e->resid, 0, sizeof(double) * resid_len, e->stream));
-    ECHK(dmalloc(e, &e->T, (size_t)(m * ld)));
-    ECHK(hipMemsetAsync(e->T, 0, sizeof(double) * (size_t)(m * ld), e->stream));
-    ECHK(dmalloc(e, &e->st, 1));
-    if (kind == ELLP_ENGINE_DUAL) {
-        ECHK(dmalloc(e, &e->y, (size_t)ld));
-        ECHK(dmalloc(e, &e->dd, (size_t)n_c));
+    HIPCHK(dmalloc(e, &e->resid, resid_len));
+    HIPCHK(hipMemsetAsync(e->resid, 0, sizeof(double) * resid_len, e->stream));
+    HIPCHK(dmalloc(e, &e->T, (size_t)(m * ld)));
+    HIPCHK(hipMemsetAsync(e->T, 0, sizeof(double) * (size_t)(m * ld), e->stream));
+    HIPCHK(dmalloc(e, &e->st, 1));
+    if (e->kind == ELLP_ENGINE_DUAL) {
+        HIPCHK(dmalloc(e, &e->y, (size_t)ld));
+        HIPCHK(dmalloc(e, &e->dd, (size_t)n_c));
     }
-    ECHK(hipMemsetAsync(e->u, 0, sizeof(double) * (size_t)(2 * ld), e->stream));
-    ECHK(hipMemsetAsync(e->aq_save, 0, sizeof(double) * (size_t)ld, e->stream));
-    ECHK(hipMemsetAsync(e->d, 0, sizeof(double) * (size_t)ld, e->stream));
+    HIPCHK(hipMemsetAsync(e->u, 0, sizeof(double) * (size_t)(2 * ld), e->stream));
+    HIPCHK(hipMemsetAsync(e->aq_save, 0, sizeof(double) * (size_t)ld, e->stream));
+    HIPCHK(hipMemsetAsync(e->d, 0, sizeof(double) * (size_t)ld, e->stream));
+    return ELLP_OPTIMAL;
+}
 
-    // upload (A goes through a temporary full copy, then columns are gathered on the device)
-    {
-        double *A_full = nullptr, *c_full = nullptr;
-        ECHK(hipMalloc(reinterpret_cast<void **>(&A_full), sizeof(double) * (size_t)(m * n > 0 ? m * n : 1)));
-        hipError_t rc = hipMalloc(reinterpret_cast<void **>(&c_full), sizeof(double) * (size_t)n_c);
-        if (rc != hipSuccess) {
-            (void)hipFree(A_full);
-            ECHK(rc);
-        }
-        auto fail = [&](hipError_t err) {
-            (void)hipStreamSynchronize(e->stream);
-            (void)hipFree(A_full);
-            (void)hipFree(c_full);
-            return err;
-        };
-#define UCHK(expr)                              \
-    do {                                        \
-        hipError_t _u = (expr);                 \
-        if (_u != hipSuccess) { ECHK(fail(_u)); } \
-    } while (0)
-        UCHK(hipMemcpyAsync(A_full, A, sizeof(double) * (size_t)(m * n_explicit), hipMemcpyHostToDevice, e->stream));
-        if (n_explicit < n)  // the artificial columns: zero here, their +-1 is set once b~ is known (k_phase1_art)
-            UCHK(hipMemsetAsync(A_full + m * n_explicit, 0, sizeof(double) * (size_t)(m * (n - n_explicit)), e->stream));
-        UCHK(hipMemcpyAsync(c_full, c, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-        UCHK(hipMemcpyAsync(e->B_index, B_index, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-        if (n_N > 0) {
-            UCHK(hipMemcpyAsync(e->N_index, N_index, sizeof(int64_t) * (size_t)n_N, hipMemcpyHostToDevice, e->stream));
-            UCHK(hipMemcpyAsync(e->Nb, N_bound, (size_t)n_N, hipMemcpyHostToDevice, e->stream));
-        }
-        UCHK(hipMemcpyAsync(e->x, x, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-        UCHK(hipMemcpyAsync(e->b_dev, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-        UCHK(hipMemcpyAsync(e->lb, lb, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-        UCHK(hipMemcpyAsync(e->ub, ub, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-        UCHK(hipMemcpyAsync(e->kindv, bound_kind, (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-        hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)m), dim3(256), 0, e->stream, A_full, m, e->B_index, e->A_B, ld);
-        hipLaunchKernelGGL(k_gather_vec, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, c_full,
-                           e->B_index, e->c_B, m);
-        if (n_N > 0) {
-            hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)n_N), dim3(256), 0, e->stream, A_full, m, e->N_index,
-                               e->A_N, ld);
-            hipLaunchKernelGGL(k_gather_vec, dim3((unsigned)((n_N + 255) / 256)), dim3(256), 0, e->stream, c_full,
-                               e->N_index, e->c_N, n_N);
-        }
-        UCHK(hipGetLastError());
-        DevState init = initial_state(kind, m, n_c, n_N, c, b, bound_kind, lb, ub, x, y, d);
-        if (kind == ELLP_ENGINE_PRIMAL && e->opts.partial_segments > 1 && n_N > 0) {
-            // partial pricing (f4): segments of ceil(|N| / P) positions, never more segments than positions
-            int P = e->opts.partial_segments;
-            if ((int64_t)P > n_N) P = (int)n_N;
-            const int64_t S = (n_N + P - 1) / P;
-            P = (int)((n_N + S - 1) / S);
-            if (P > 1) {
-                e->pp_P = P;
-                e->pp_S = S;
-                init.pp_P = P;
-                init.pp_S = S;
-                init.pp_hi = S;
-            }
-        }
-        if (kind == ELLP_ENGINE_DUAL) {
-            UCHK(hipMemsetAsync(e->y, 0, sizeof(double) * (size_t)ld, e->stream));
-            UCHK(hipMemcpyAsync(e->y, y, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-            UCHK(hipMemcpyAsync(e->dd, d, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-        }
-        *e->h_st = init;
-        UCHK(hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream));
-        UCHK(hipStreamSynchronize(e->stream));
+// the upload's two temporaries: released on every way out of the stage, once the stream that reads them has drained
+struct UploadTemps {
+    hipStream_t stream;
+    double *A_full = nullptr, *c_full = nullptr;
+    ~UploadTemps() {
+        if (!A_full) return;
+        (void)hipStreamSynchronize(stream);
         (void)hipFree(A_full);
         (void)hipFree(c_full);
-#undef UCHK
     }
-    if (build_phase1) {
-        // primal_problem.rs:236-246 on the device: b~ = b - A v over the nonbasic (= all structural) columns,
-        // artificial column i = signum(b~_i) e_i with value |b~_i| (the kernels of launch_resync form b - A_N x_N)
-        ResyncArgs ra{e->A_N, e->W, e->W2, e->b_dev, e->x, e->xg, e->tvec, e->upart, e->cand, e->maxbits, e->B_index,
-                      e->N_index, e->st, e->m, e->ld, e->nN, 0, e->btran_tiles, 0};
-        ra.cols_per_tile = (int)((e->nN + e->btran_tiles - 1) / e->btran_tiles);
-        const int64_t half = e->ld >> 1;
-        hipLaunchKernelGGL(k_resync_gather, dim3((unsigned)((e->nN + 255) / 256)), dim3(256), 0, e->stream, ra);
-        hipLaunchKernelGGL(k_resync_part, dim3((unsigned)((half + 255) / 256), (unsigned)e->btran_tiles), dim3(256), 0, e->stream, ra);
-        hipLaunchKernelGGL(k_resync_rhs, dim3((unsigned)((e->ld + 255) / 256)), dim3(256), 0, e->stream, ra);
-        hipLaunchKernelGGL(k_phase1_art, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, e->tvec, e->A_B, e->x,
-                           e->B_index, m, e->ld);
-        // the carried objective (and the trace) start from c . x WITH the artificials at |b~_i|, not from the host's value
-        hipLaunchKernelGGL(k_primal_obj, dim3(1), dim3(1024), 0, e->stream, e->c_B, e->c_N, e->x, e->B_index, e->N_index, e->m,
-                           e->nN, e->st);
+};
+
+// upload (A goes through a temporary full copy, then columns are gathered on the device) and the starting DevState
+static ellp_status create_upload(ellp_engine *e, const double *A, const double *c, const double *b, const uint8_t *bound_kind,
+                                 const double *lb, const double *ub, const double *x, const int64_t *B_index, const int64_t *N_index,
+                                 const uint8_t *N_bound, const double *y, const double *d, int64_t n_explicit, char *errbuf,
+                                 size_t errlen) {
+    const int64_t m = e->m, n = e->n, n_c = e->n_c, n_N = e->nN, ld = e->ld;
+    UploadTemps t{e->stream};
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&t.A_full), sizeof(double) * (size_t)(m * n > 0 ? m * n : 1)));
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&t.c_full), sizeof(double) * (size_t)n_c));
+    HIPCHK(hipMemcpyAsync(t.A_full, A, sizeof(double) * (size_t)(m * n_explicit), hipMemcpyHostToDevice, e->stream));
+    if (n_explicit < n)  // the artificial columns: zero here, their +-1 is set once b~ is known (k_phase1_art)
+        HIPCHK(hipMemsetAsync(t.A_full + m * n_explicit, 0, sizeof(double) * (size_t)(m * (n - n_explicit)), e->stream));
+    HIPCHK(hipMemcpyAsync(t.c_full, c, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->B_index, B_index, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    if (n_N > 0) {
+        HIPCHK(hipMemcpyAsync(e->N_index, N_index, sizeof(int64_t) * (size_t)n_N, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->Nb, N_bound, (size_t)n_N, hipMemcpyHostToDevice, e->stream));
     }
-    // dual: initial dual feasibility assertion (dual…:139-151) — host side, data is in hand
-    if (kind == ELLP_ENGINE_DUAL && !dual_start_feasible(n_N, N_index, N_bound, d, e->eps, errbuf, errlen)) {
-        ellp_engine_destroy(e);
-        return ELLP_ERR_PANIC;
+    HIPCHK(hipMemcpyAsync(e->x, x, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->b_dev, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->lb, lb, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->ub, ub, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->kindv, bound_kind, (size_t)n_c, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)m), dim3(256), 0, e->stream, t.A_full, m, e->B_index, e->A_B, ld);
+    hipLaunchKernelGGL(k_gather_vec, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, t.c_full, e->B_index, e->c_B, m);
+    if (n_N > 0) {
+        hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)n_N), dim3(256), 0, e->stream, t.A_full, m, e->N_index, e->A_N, ld);
+        hipLaunchKernelGGL(k_gather_vec, dim3((unsigned)((n_N + 255) / 256)), dim3(256), 0, e->stream, t.c_full, e->N_index, e->c_N,
+                           n_N);
     }
-    e->dual_maxviol = (kind == ELLP_ENGINE_DUAL && (e->opts.flags & ELLP_FLAG_DUAL_MAX_VIOLATION)) ? 1 : 0;
-    e->dual_bflip = (kind == ELLP_ENGINE_DUAL && (e->opts.flags & ELLP_FLAG_DUAL_BOUND_FLIPPING)) ? 1 : 0;
-    if (e->dual_bflip && (e->opts.pipeline == 1 || e->opts.pipeline == 2 || e->pp_P > 1)) {
-        set_err(errbuf, errlen, "ELLP_FLAG_DUAL_BOUND_FLIPPING runs on the LU-per-iteration kernels (pipeline 0 or 3, up to 1,024 rows), "
-                                "not on the explicit-inverse pipelines 1 / 2");
-        ellp_engine_destroy(e);
-        return ELLP_ERR_ARG;
+    HIPCHK(hipGetLastError());
+    DevState init = initial_state(e->kind, m, n_c, n_N, c, b, bound_kind, lb, ub, x, y, d);
+    if (e->pp_P > 1) {  // partial pricing: the first segment
+        init.pp_P = e->pp_P;
+        init.pp_S = e->pp_S;
+        init.pp_hi = e->pp_S;
     }
-    if (kind == ELLP_ENGINE_DUAL) {
-        bool box = true;
-        for (int64_t i = 0; i < n_c && box; ++i) box = bound_kind[i] == ELLP_BOUND_TWOSIDED || bound_kind[i] == ELLP_BOUND_FIXED;
-        for (int64_t i = 0; i < m && box; ++i) box = b[i] == 0.0;
-        e->box_problem = box;
+    if (e->kind == ELLP_ENGINE_DUAL) {
+        HIPCHK(hipMemsetAsync(e->y, 0, sizeof(double) * (size_t)ld, e->stream));
+        HIPCHK(hipMemcpyAsync(e->y, y, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->dd, d, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
     }
-    if (kind == ELLP_ENGINE_PRIMAL && (e->opts.flags & ELLP_FLAG_PRIMAL_STEEPEST_EDGE) &&
-        (e->pp_P > 1 || e->opts.pipeline == 2 || e->opts.pipeline == 3 || e->opts.btran_mode == 1)) {
-        // the caller must be able to tell which rule ran: steepest edge exists on the three-launch explicit-inverse engine only
-        set_err(errbuf, errlen, "ELLP_FLAG_PRIMAL_STEEPEST_EDGE runs on the three-launch pipeline (pipeline 0 or 1) with full "
-                                "pricing and the incremental BTRAN: not with partial_segments > 1, pipeline 2 / 3 or btran_mode 1");
-        ellp_engine_destroy(e);
-        return ELLP_ERR_ARG;
+    *e->h_st = init;
+    HIPCHK(hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return ELLP_OPTIMAL;
+}
+
+// primal_problem.rs:236-246 on the device: b~ = b - A v over the nonbasic (= all structural) columns, artificial column
+// i = signum(b~_i) e_i with value |b~_i|
+static ellp_status create_phase1_start(ellp_engine *e) {
+    launch_resync_rhs(e, 0);
+    hipLaunchKernelGGL(k_phase1_art, dim3((unsigned)((e->m + 255) / 256)), dim3(256), 0, e->stream, e->tvec, e->A_B, e->x, e->B_index,
+                       e->m, e->ld);
+    // the carried objective (and the trace) start from c . x WITH the artificials at |b~_i|, not from the host's value
+    hipLaunchKernelGGL(k_primal_obj, dim3(1), dim3(1024), 0, e->stream, e->c_B, e->c_N, e->x, e->B_index, e->N_index, e->m, e->nN,
+                       e->st);
+    return ELLP_OPTIMAL;
+}
+
+// the unit-column table (PriceArgs::vs_row), per VARIABLE; without memory for it the pricing kernels stream everything
+static ellp_status create_unit_table(ellp_engine *e, char *errbuf, size_t errlen) {
+    const int64_t m = e->m, n_N = e->nN, n_c = e->n_c;
+    if (dmalloc(e, &e->vs_row, (size_t)n_c) != hipSuccess || dmalloc(e, &e->vs_val, (size_t)n_c) != hipSuccess ||
+        dmalloc(e, &e->pos_hint, (size_t)n_N + 64) != hipSuccess) {
+        (void)hipGetLastError();
+        e->vs_row = nullptr;
+        e->vs_val = nullptr;
+        return ELLP_OPTIMAL;
     }
-    e->se = kind == ELLP_ENGINE_PRIMAL && (e->opts.flags & ELLP_FLAG_PRIMAL_STEEPEST_EDGE) && n_N > 0 && e->pp_P <= 1;
-    // unit columns of the matrix (slacks, artificials, any other column with a single nonzero): the table the pricing
-    // kernels of both loops consult (PriceArgs::vs_row).  ellp_opts.flags bit 0 or ELLP_NO_UNIT_COLUMNS=1: off.
-    if (n_N > 0 && (e->se || (!(e->opts.flags & ELLP_FLAG_DENSE_PRICING) && getenv("ELLP_NO_UNIT_COLUMNS") == nullptr))) {
-        if (dmalloc(e, &e->vs_row, (size_t)n_c) == hipSuccess && dmalloc(e, &e->vs_val, (size_t)n_c) == hipSuccess &&
-            dmalloc(e, &e->pos_hint, (size_t)n_N + 64) == hipSuccess) {
-            ECHK(hipMemsetAsync(e->vs_row, 0xff, sizeof(int32_t) * (size_t)n_c, e->stream));
-            ECHK(hipMemsetAsync(e->pos_hint, 0, (size_t)n_N + 64, e->stream));
-            hipLaunchKernelGGL(k_scan_singletons, dim3((unsigned)((n_N + 3) / 4)), dim3(256), 0, e->stream, e->A_N, e->ld, m, n_N,
-                               e->N_index, e->vs_row, e->vs_val);
-            hipLaunchKernelGGL(k_scan_singletons, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, e->stream, e->A_B, e->ld, m, m,
-                               e->B_index, e->vs_row, e->vs_val);
-        } else {
-            (void)hipGetLastError();
-            e->vs_row = nullptr;
-            e->vs_val = nullptr;
-        }
+    HIPCHK(hipMemsetAsync(e->vs_row, 0xff, sizeof(int32_t) * (size_t)n_c, e->stream));
+    HIPCHK(hipMemsetAsync(e->pos_hint, 0, (size_t)n_N + 64, e->stream));
+    hipLaunchKernelGGL(k_scan_singletons, dim3((unsigned)((n_N + 3) / 4)), dim3(256), 0, e->stream, e->A_N, e->ld, m, n_N, e->N_index,
+                       e->vs_row, e->vs_val);
+    hipLaunchKernelGGL(k_scan_singletons, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, e->stream, e->A_B, e->ld, m, m, e->B_index,
+                       e->vs_row, e->vs_val);
+    return ELLP_OPTIMAL;
+}
+
+// what k_mid needs, as the whole loop (mid) or as the hybrid's certifier: its LDS attribute and its factor arrays
+static hipError_t acquire_mid_factors(ellp_engine *e) {
+    hipError_t rc = hipFuncSetAttribute(mid_kernel(e->kind, e->mid_nt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->mid_lds);
+    if (rc == hipSuccess) rc = dmalloc(e, &e->LUa, (size_t)(e->ld * e->ld));
+    if (rc == hipSuccess) rc = dmalloc(e, &e->Ut, (size_t)(e->ld * e->ld));
+    if (rc == hipSuccess) rc = dmalloc(e, &e->A_Nt, (size_t)(e->ld * e->ldn));
+    return rc;
+}
+
+// The resources of the LU-per-iteration kernels the plan asks for.  One that cannot be had is struck from `avail` and the
+// engine is planned again: the downgrade, or the refusal, is the plan's (plan_engine), and nothing is acquired twice.
+static ellp_status create_exact_loop(ellp_engine *e, const PlanEnv &env, char *errbuf, size_t errlen) {
+    if (e->want_stamps) {
+        if (dmalloc(e, &e->small_stamps, 32) == hipSuccess) (void)hipMemsetAsync(e->small_stamps, 0, 256, e->stream);
+        else e->small_stamps = nullptr;
     }
-    // small LPs: the reference's own loop in one persistent workgroup (ellp_small.inc) unless the caller
-    // asked for the explicit-inverse engine (a maintenance period, a launch structure, profiling)
-    {
-        const int pl = e->opts.pipeline;
-        e->small_lds = small_lds_bytes(m, n_N);
-        e->mid_lds = mid_lds_bytes(m, n_N);
-        const ExactLoop loop = exact_loop(e->opts, e->dual_bflip, e->se, e->pp_P, m, e->small_lds, e->mid_lds);
-        e->small = loop != EXACT_NONE;
-        e->mid = loop == EXACT_MID;
-        if (e->small && getenv("ELLP_SMALL_STAMPS") && !e->small_stamps) {
-            if (dmalloc(e, &e->small_stamps, 32) == hipSuccess) (void)hipMemsetAsync(e->small_stamps, 0, 256, e->stream);
-            else e->small_stamps = nullptr;
-        }
-        if (e->mid) {
-            e->mid_nt = mid_threads(m);
-            e->ldn = (n_N + 15) / 16 * 16;
-            const void *fn = mid_kernel(e->kind, e->mid_nt);
-            hipError_t ra = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->mid_lds);
-            if (ra == hipSuccess) ra = dmalloc(e, &e->LUa, (size_t)(ld * ld));
-            if (ra == hipSuccess) ra = dmalloc(e, &e->Ut, (size_t)(ld * ld));
-            if (ra == hipSuccess) ra = dmalloc(e, &e->A_Nt, (size_t)(ld * e->ldn));
-            if (ra != hipSuccess) {
-                (void)hipGetLastError();
-                if (pl == 3 || e->dual_bflip) {
-                    set_err(errbuf, errlen, "pipeline 3: no device memory for the factors of the persistent-workgroup loop");
-                    ellp_engine_destroy(e);
-                    return ELLP_ERR_DEVICE;
-                }
-                e->small = e->mid = false;  // the large engine handles it
-            }
-        } else if (e->small) {
-            int nt = small_threads(m, n_N);
-            if (const char *ev = getenv("ELLP_SMALL_NT")) {  // measurement: force a workgroup size that still has a thread per row
-                const int v = atoi(ev);
-                if ((v == 64 || v == 128 || v == 256) && v >= m) nt = v;
-            }
-            e->small_nt = nt;
-            const void *fn = small_kernel(e->kind, nt);
-            hipError_t ra = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->small_lds);
-            if (ra != hipSuccess) {
-                (void)hipGetLastError();
-                e->small = false;  // the large engine handles it
-            }
-        }
+    for (int avail = PLAN_AVAIL_ALL;;) {
+        int lost = 0;
+        if ((e->mid || e->hybrid) && acquire_mid_factors(e) != hipSuccess) lost = PLAN_AVAIL_MID;
+        else if (e->small && !e->mid && hipFuncSetAttribute(small_kernel(e->kind, e->small_nt), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                            (int)e->small_lds) != hipSuccess)
+            lost = PLAN_AVAIL_SMALL;
+        if (!lost) break;
+        (void)hipGetLastError();
+        avail &= ~lost;
+        EnginePlan plan;
+        const ellp_status s = plan_engine(e->kind, e->m, e->nN, e->opts, env, avail, &plan, errbuf, errlen);
+        if (s != ELLP_OPTIMAL) return s;
+        static_cast<EnginePlan &>(*e) = plan;
     }
-    if (e->dual_bflip) {
-        // the long-step ratio test exists in k_small / k_mid only (a selection walk and one more solve with the iteration's LU)
-        if (!e->small && n_N > 0) {
-            set_err(errbuf, errlen, "ELLP_FLAG_DUAL_BOUND_FLIPPING: the LU-per-iteration kernels take up to 1,024 rows (this LP: %lld)", (long long)m);
-            ellp_engine_destroy(e);
-            return ELLP_ERR_ARG;
-        }
-        if (n_N > 0 && dmalloc(e, &e->bf_list, (size_t)n_N + 1) != hipSuccess) {
-            (void)hipGetLastError();
-            set_err(errbuf, errlen, "ELLP_FLAG_DUAL_BOUND_FLIPPING: no device memory for the list of passed positions");
-            ellp_engine_destroy(e);
-            return ELLP_ERR_DEVICE;
-        }
+    if (e->dual_bflip && e->nN > 0 && dmalloc(e, &e->bf_list, (size_t)e->nN + 1) != hipSuccess) {
+        (void)hipGetLastError();
+        set_err(errbuf, errlen, "ELLP_FLAG_DUAL_BOUND_FLIPPING: no device memory for the list of passed positions");
+        return ELLP_ERR_DEVICE;
     }
-    // Certified hybrid (restated in oracle/ellp_oracle.c: hybrid_run), the default for 128 < m <= 1024: the
-    // explicit-inverse loop on the three-launch pipeline (its ratio-test fold sits in front of every store of the iteration,
-    // so a guarded pivot can be refused by all blocks alike) with the pivot guard on; every terminal status and every
-    // guarded iteration is re-examined by the LU-per-iteration kernel k_mid from the same arrays (exact_takeover).  Off with
-    // an explicit pipeline, ELLP_FLAG_NO_CERTIFY, partial pricing, steepest edge, btran_mode 1 and on sharded engines.
-    if (!e->small && e->opts.pipeline == 0 && !(e->opts.flags & ELLP_FLAG_NO_CERTIFY) && e->mid_lds > 0 && n_N > 0 && e->pp_P <= 1 &&
-        !e->se && e->opts.btran_mode == 0 && getenv("ELLP_NO_HYBRID") == nullptr) {
-        e->mid_nt = mid_threads(m);
-        e->ldn = (n_N + 15) / 16 * 16;
-        const void *fn = mid_kernel(e->kind, e->mid_nt);
-        hipError_t ra = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->mid_lds);
-        if (ra == hipSuccess) ra = dmalloc(e, &e->LUa, (size_t)(ld * ld));
-        if (ra == hipSuccess) ra = dmalloc(e, &e->Ut, (size_t)(ld * ld));
-        if (ra == hipSuccess) ra = dmalloc(e, &e->A_Nt, (size_t)(ld * e->ldn));
-        if (ra == hipSuccess) {
-            e->hybrid = true;
-            e->guard_abs = 1e-7;
-            if (const char *v = getenv("ELLP_GUARD_ABS"); v && v[0]) e->guard_abs = atof(v);  // diagnostics
-            if (const char *v = getenv("ELLP_EXACT_K"); v && v[0] && atoi(v) > 0) e->exact_K = atoi(v);  // diagnostics
-        } else {
-            (void)hipGetLastError();  // no memory for the factors: the plain explicit-inverse engine
-        }
+    return ELLP_OPTIMAL;
+}
+
+// steepest-edge weights (ellp_se.inc): exact — at a signed-permutation basis from the columns alone, otherwise from B^-1
+// (create_initial_inverse)
+static ellp_status create_steepest_edge(ellp_engine *e, char *errbuf, size_t errlen) {
+    const int64_t m = e->m, n_N = e->nN, ld = e->ld;
+    if (!e->vs_row) {
+        set_err(errbuf, errlen, "no device memory for the steepest-edge tables");
+        return ELLP_ERR_DEVICE;
     }
-    // above 1,024 rows (the persistent kernel's limit): terminal statuses certified by an exact-LU iteration (ellp_exact.inc)
-    if (!e->small && !e->hybrid && e->opts.pipeline == 0 && !(e->opts.flags & ELLP_FLAG_NO_CERTIFY) && m > MID_MAX_M && m <= 8192 &&
-        n_N > 0 && e->pp_P <= 1 && !e->se && e->opts.btran_mode == 0 && getenv("ELLP_NO_HYBRID") == nullptr)
-    {
-        e->cert_large = true;
-        e->guard_abs = 1e-7;
-        if (const char *v = getenv("ELLP_GUARD_ABS"); v && v[0]) e->guard_abs = atof(v);  // diagnostics
-        if (const char *v = getenv("ELLP_EXACT_K"); v && v[0] && atoi(v) > 0) e->exact_K = atoi(v);  // diagnostics
-    }
-    // pipeline 3 above 1,024 rows, under the condition exact_loop() sets below them: the LU-per-iteration loop over all CUs
-    // (run_exact_large) is the engine — no hybrid, certificate, guard or snapshot: the loop is its own certificate.  The
-    // explicit inverse is built, updated along and rebuilt at the end of a solve, so the phase hand-offs and read_point work.
-    if (!e->small && e->opts.pipeline == 3 && m > MID_MAX_M && m <= 8192 && n_N > 0 && e->pp_P <= 1 && !e->se)
-        e->exact_large_always = e->exact_large_only = true;
-    // two launches per primal iteration from m = 1024 (ellp_lagged.inc), or on request
-    {
-        const int pl = e->opts.pipeline;
-        e->lagged = !e->small && !e->hybrid && !e->se && kind == ELLP_ENGINE_PRIMAL && e->opts.btran_mode == 0 && n_N > 0 && e->pp_P <= 1 &&
-                    (pl == 2 || (pl == 0 && m >= 384));  // partial pricing runs on the three-launch pipeline; tools/pipeline_threshold.py for the size
-        e->dual_fused = !e->small && !e->hybrid && kind == ELLP_ENGINE_DUAL && n_N > 0 && ld <= 4096 && (pl == 2 || (pl == 0 && m >= 384));
-        e->dual_fold = e->dual_fused && e->ill_tol <= 0.0 && getenv("ELLP_DUAL_FOLD_OFF") == nullptr;
-        if (e->lagged && e->price_wave && ld > 4096) e->price_wave = false;  // k_price2_wave keeps u in 8 double2 per thread
-        e->price2_lds = sizeof(double) * (size_t)((m + 63) / 64) + 16;
-    }
-    // steepest-edge weights (ellp_se.inc): exact — at a signed-permutation basis from the columns alone, otherwise from B^-1 (below)
-    if (e->se) {
-        if (!e->vs_row) {
-            set_err(errbuf, errlen, "no device memory for the steepest-edge tables");
-            ellp_engine_destroy(e);
-            return ELLP_ERR_DEVICE;
-        }
-        int32_t *perm = nullptr;
-        ECHK(dmalloc(e, &e->se_gamma, (size_t)n_N));
-        ECHK(dmalloc(e, &e->se_rho, (size_t)ld));
-        ECHK(dmalloc(e, &e->se_v, (size_t)ld));
-        // v = B^-T d accumulated by k_update2's row blocks (their rows of the old inverse are in registers there) where every
-        // row of a block goes through the register path: <= 4 rows per block and NR > 0 (ld <= 4096); otherwise the GEMV
-        if (ld <= 4096 && getenv("ELLP_SE_BTRAN") == nullptr) {
-            if (e->upd2_rows > UPD_ROWS) {
-                e->upd2_rows = UPD_ROWS;
-                e->upd2_blocks = (int)((m + e->upd2_rows - 1) / e->upd2_rows);
-            }
-            ECHK(dmalloc(e, &e->se_vpart, (size_t)((int64_t)e->upd2_blocks * ld)));
-        }
-        ECHK(dmalloc(e, &perm, 4));
-        ECHK(hipMemsetAsync(e->se_rho, 0, sizeof(double) * (size_t)ld, e->stream));
-        ECHK(hipMemsetAsync(e->se_v, 0, sizeof(double) * (size_t)ld, e->stream));
-        e->se_perm = perm;
-        hipLaunchKernelGGL(k_se_perm, dim3(1), dim3(256), 0, e->stream, e->B_index, m, e->vs_row, e->vs_val, perm);
-        hipLaunchKernelGGL(k_se_init, dim3((unsigned)((n_N + 3) / 4)), dim3(256), 0, e->stream, e->A_N, ld, m, n_N, perm, e->se_gamma);
-        if (e->opts.flags & ELLP_FLAG_DENSE_PRICING) {  // the table was only needed for the permutation test
-            e->pos_hint = nullptr;
-        }
-    }
-    // initial B^-1 (k_small keeps none: its LU is redone every iteration, with the reference's guard)
+    HIPCHK(dmalloc(e, &e->se_gamma, (size_t)n_N));
+    HIPCHK(dmalloc(e, &e->se_rho, (size_t)ld));
+    HIPCHK(dmalloc(e, &e->se_v, (size_t)ld));
+    if (e->want_se_vpart) HIPCHK(dmalloc(e, &e->se_vpart, (size_t)((int64_t)e->upd2_blocks * ld)));
+    HIPCHK(dmalloc(e, &e->se_perm, 4));
+    HIPCHK(hipMemsetAsync(e->se_rho, 0, sizeof(double) * (size_t)ld, e->stream));
+    HIPCHK(hipMemsetAsync(e->se_v, 0, sizeof(double) * (size_t)ld, e->stream));
+    hipLaunchKernelGGL(k_se_perm, dim3(1), dim3(256), 0, e->stream, e->B_index, m, e->vs_row, e->vs_val, e->se_perm);
+    hipLaunchKernelGGL(k_se_init, dim3((unsigned)((n_N + 3) / 4)), dim3(256), 0, e->stream, e->A_N, ld, m, n_N, e->se_perm, e->se_gamma);
+    if (e->opts.flags & ELLP_FLAG_DENSE_PRICING) e->pos_hint = nullptr;  // the table was only needed for the permutation test
+    return ELLP_OPTIMAL;
+}
+
+// initial B^-1 (k_small keeps none: its LU is redone every iteration, with the reference's guard), the steepest-edge
+// weights that need it, and the read-back that says whether the basis could be inverted
+static ellp_status create_initial_inverse(ellp_engine *e, char *errbuf, size_t errlen) {
+    const int64_t m = e->m, n_N = e->nN, ld = e->ld;
     if (e->small) e->w_valid = false;
     else launch_refactor(e);
     if (e->se && e->se_perm) {  // steepest-edge weights at a basis that is not a signed permutation: exact, from the inverse just built
@@ -4620,21 +4346,78 @@ static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_
             (void)hipGetLastError();  // no scratch memory: the weights stay at 1 (a reference-framework start)
         }
     }
-    ECHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    ECHK(hipStreamSynchronize(e->stream));
-    ECHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipGetLastError());
     prof_collect(e);
-    if (e->h_st->status != ST_RUNNING) {
-        ellp_status s = status_message(*e->h_st, errbuf, errlen);
-        if (getenv("ELLP_DEBUG"))
-            fprintf(stderr, "ellp: initial rebuild failed: status %d, column %lld, pivot row %lld, |pivot| %.3e\n", (int)s,
-                    (long long)e->h_st->refk, (long long)e->h_st->r, e->h_st->d_r);
-        ellp_engine_destroy(e);
-        return s;
+    if (e->h_st->status == ST_RUNNING) return ELLP_OPTIMAL;
+    const ellp_status s = status_message(*e->h_st, errbuf, errlen);
+    if (getenv("ELLP_DEBUG"))
+        fprintf(stderr, "ellp: initial rebuild failed: status %d, column %lld, pivot row %lld, |pivot| %.3e\n", (int)s,
+                (long long)e->h_st->refk, (long long)e->h_st->r, e->h_st->d_r);
+    return s;
+}
+
+// Validation and the plan (with its refusals) come before the first HIP call; then the stages, in the order in which
+// their work has always been enqueued.
+static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c,
+                               const double *b, const uint8_t *bound_kind, const double *lb, const double *ub,
+                               const double *x, const int64_t *B_index, int64_t n_B, const int64_t *N_index,
+                               const uint8_t *N_bound, int64_t n_N, const double *y, const double *d,
+                               const ellp_opts *opts_in, ellp_engine **out, char *errbuf, size_t errlen,
+                               int64_t n_explicit, bool build_phase1) {
+    if (!out) return ELLP_ERR_ARG;
+    *out = nullptr;
+    if (errbuf && errlen) errbuf[0] = 0;
+    auto t0 = std::chrono::steady_clock::now();
+    const ellp_status cs = check_problem(kind, m, n, n_c, A, c, b, bound_kind, lb, ub, x, B_index, n_B, N_index, N_bound, n_N, y, d,
+                                         errbuf, errlen);
+    if (cs != ELLP_OPTIMAL) return cs;
+    ellp_opts opts;
+    ellp_default_opts(&opts);
+    if (opts_in) opts = *opts_in;
+    const double eps = opts.eps > 0.0 ? opts.eps : 1e-10;
+    const PlanEnv env = plan_env();
+    EnginePlan plan;
+    const ellp_status ps = plan_engine(kind, m, n_N, opts, env, PLAN_AVAIL_ALL, &plan, errbuf, errlen);
+    if (ps != ELLP_OPTIMAL && m > PLAN_MAX_M) return ps;  // the pricing tile is answered before the dual's starting point ...
+    // dual: initial dual feasibility assertion (dual…:139-151) — host side, data is in hand
+    if (kind == ELLP_ENGINE_DUAL && !dual_start_feasible(n_N, N_index, N_bound, d, eps, errbuf, errlen)) return ELLP_ERR_PANIC;
+    if (ps != ELLP_OPTIMAL) return ps;  // ... the options after it
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_err(errbuf, errlen, "no HIP device available (this library has no CPU path)");
+        return ELLP_ERR_DEVICE;
     }
-#undef ECHK
+    std::unique_ptr<ellp_engine, void (*)(ellp_engine *)> own(new ellp_engine(), ellp_engine_destroy);  // destroys it on an early return
+    ellp_engine *e = own.get();
+    static_cast<EnginePlan &>(*e) = plan;
+    e->exact_large_only = e->exact_large_always;
+    e->opts = opts;
+    e->eps = eps;
+    e->kind = kind;
+    e->m = m;
+    e->n = n;
+    e->n_c = n_c;
+    e->nN = n_N;
+    if (kind == ELLP_ENGINE_DUAL) {
+        bool box = true;
+        for (int64_t i = 0; i < n_c && box; ++i) box = bound_kind[i] == ELLP_BOUND_TWOSIDED || bound_kind[i] == ELLP_BOUND_FIXED;
+        for (int64_t i = 0; i < m && box; ++i) box = b[i] == 0.0;
+        e->box_problem = box;
+    }
+    ellp_status s = create_host_set(e, errbuf, errlen);
+    if (s == ELLP_OPTIMAL) s = create_core_arrays(e, errbuf, errlen);
+    if (s == ELLP_OPTIMAL) s = create_upload(e, A, c, b, bound_kind, lb, ub, x, B_index, N_index, N_bound, y, d, n_explicit, errbuf, errlen);
+    if (s == ELLP_OPTIMAL && build_phase1) s = create_phase1_start(e);
+    if (s == ELLP_OPTIMAL && e->want_unit_table) s = create_unit_table(e, errbuf, errlen);
+    if (s == ELLP_OPTIMAL) s = create_exact_loop(e, env, errbuf, errlen);
+    if (s == ELLP_OPTIMAL && e->se) s = create_steepest_edge(e, errbuf, errlen);
+    if (s == ELLP_OPTIMAL) s = create_initial_inverse(e, errbuf, errlen);
+    if (s != ELLP_OPTIMAL) return s;
     e->t_setup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    *out = e;
+    *out = own.release();
     return ELLP_OPTIMAL;
 }
 
@@ -4645,6 +4428,33 @@ ellp_status ellp_engine_create(int kind, int64_t m, int64_t n, int64_t n_c, cons
                                const ellp_opts *opts_in, ellp_engine **out, char *errbuf, size_t errlen) {
     return engine_create_impl(kind, m, n, n_c, A, c, b, bound_kind, lb, ub, x, B_index, n_B, N_index, N_bound, n_N, y, d,
                               opts_in, out, errbuf, errlen, n, false);
+}
+
+ellp_status ellp_engine_plan(int kind, int64_t m, int64_t n_N, const ellp_opts *opts_in, int avail_mask, double *out, int64_t cap,
+                             char *errbuf, size_t errlen) {
+    if (errbuf && errlen) errbuf[0] = 0;
+    if ((kind != ELLP_ENGINE_PRIMAL && kind != ELLP_ENGINE_DUAL) || m < 1 || n_N < 0 || !out || cap < ELLP_PLAN_FIELDS) {
+        set_err(errbuf, errlen, "unknown kind, m < 1, n_N < 0, or out NULL / shorter than ELLP_PLAN_FIELDS");
+        return ELLP_ERR_ARG;
+    }
+    ellp_opts opts;
+    ellp_default_opts(&opts);
+    if (opts_in) opts = *opts_in;
+    EnginePlan p;
+    const ellp_status s = plan_engine(kind, m, n_N, opts, plan_env(), avail_mask, &p, errbuf, errlen);
+    if (s != ELLP_OPTIMAL) return s;
+    const double v[ELLP_PLAN_FIELDS] = {
+        (double)p.ld, (double)p.cpb, (double)p.nblocks, (double)p.priceT, (double)p.price_nt, (double)p.price_wave,
+        (double)p.upd_rows, (double)p.upd_blocks, (double)p.upd2_rows, (double)p.upd2_blocks, (double)p.ftran_blocks,
+        (double)p.btran_rows, (double)p.btran_tiles, (double)p.upd_stage, (double)p.upd_lds, (double)p.ftran_lds,
+        (double)p.price2_lds, (double)p.bl_splits, (double)p.nbs, (double)p.seg,
+        (double)p.refactor_period, p.ill_tol, (double)p.drift_every, p.drift_tol,
+        (double)p.pp_P, (double)p.pp_S, (double)p.se, (double)p.want_se_vpart, (double)p.dual_maxviol, (double)p.dual_bflip,
+        (double)p.small, (double)p.mid, (double)p.small_lds, (double)p.mid_lds, (double)p.small_nt, (double)p.mid_nt, (double)p.ldn,
+        (double)p.hybrid, (double)p.cert_large, p.guard_abs, (double)p.exact_K, (double)p.exact_large_always,
+        (double)p.lagged, (double)p.dual_fused, (double)p.dual_fold, (double)p.want_unit_table, (double)p.want_stamps};
+    memcpy(out, v, sizeof(v));
+    return ELLP_OPTIMAL;
 }
 
 ellp_status ellp_engine_create_primal_phase1(int64_t m, int64_t n, const double *A, const double *b,
@@ -5262,7 +5072,7 @@ ellp_status ellp_engine_run(ellp_engine *e, uint64_t max_iters, ellp_stats *stat
     auto t0 = std::chrono::steady_clock::now();
     const uint64_t poll = e->opts.poll_interval > 0 ? (uint64_t)e->opts.poll_interval : (e->m <= 256 ? 64 : 16);
     int64_t period = e->refactor_period;
-    if (period <= 0) period = default_period(e);
+    if (period <= 0) period = default_period(e->m, e->ld, e->nN);
     ellp_status result = ELLP_MAXITER;
     if ((e->hybrid || e->cert_large) && !e->snap.valid && e->world == 1 && !e->colshard && e->nN > 0 && getenv("ELLP_NO_REDO") == nullptr) {
         launch_flush(e);
@@ -5794,7 +5604,7 @@ ellp_status ellp_engine_step(ellp_engine *e, int phase, char *errbuf, size_t err
         if (si != ELLP_OPTIMAL) return si;
     }
     if (phase == 0) {
-        int64_t period = e->refactor_period > 0 ? e->refactor_period : default_period(e);
+        int64_t period = e->refactor_period > 0 ? e->refactor_period : default_period(e->m, e->ld, e->nN);
         if (e->since_refactor >= (uint64_t)period) maintain_inverse(e);
         // the follow-up of a serviced maintenance request (see ellp_engine_run): B^-1 is refreshed once
         // more after the single iteration that follows the request.  maint_chain: 1 = that iteration
@@ -6582,7 +6392,7 @@ static ellp_status run_colsharded(ellp_engine *e, uint64_t max_iters, ellp_stats
     const uint64_t iters0 = sp->iters;
     uint64_t remaining = max_iters;
     const uint64_t poll = e->opts.poll_interval > 0 ? (uint64_t)e->opts.poll_interval : 32;
-    int64_t period = e->refactor_period > 0 ? e->refactor_period : default_period(e);
+    int64_t period = e->refactor_period > 0 ? e->refactor_period : default_period(e->m, e->ld, e->nN);
     auto rearm = [&]() {
         static const int32_t running = ST_RUNNING;  // static: the copy is asynchronous
         (void)hipMemcpyAsync(&e->st->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);

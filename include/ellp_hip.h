@@ -483,6 +483,25 @@ int64_t ellp_shard_pack_doubles(int64_t ld);
  */
 int64_t ellp_engine_read_trace(ellp_engine *e, uint64_t *iters_out, double *obj_out, int64_t cap);
 
+/* The engine ellp_engine_create would make for (kind, m rows, n_N nonbasic columns, opts; NULL: the defaults) — its launch
+ * geometry, maintenance settings and mode, decided as creation decides them (the same function, the same environment
+ * variables) but without any HIP call: for tests, and for asking "who runs what" on a machine without a device.
+ * avail_mask: which of the resources creation may fail to obtain it got: bit 0 the LDS attribute of k_small, bit 1 k_mid's
+ * attribute and factor arrays; 3 = all, what creation assumes first.  Writes ELLP_PLAN_FIELDS doubles to out, in this order:
+ *   0 ld, 1 cpb, 2 nblocks, 3 priceT, 4 price_nt, 5 price_wave, 6 upd_rows, 7 upd_blocks, 8 upd2_rows, 9 upd2_blocks,
+ *   10 ftran_blocks, 11 btran_rows, 12 btran_tiles, 13 upd_stage, 14 upd_lds, 15 ftran_lds, 16 price2_lds, 17 bl_splits,
+ *   18 nbs, 19 seg, 20 refactor_period, 21 ill_tol, 22 drift_every, 23 drift_tol, 24 pp_P, 25 pp_S, 26 se, 27 se_vpart wanted,
+ *   28 dual_maxviol, 29 dual_bflip, 30 small, 31 mid, 32 small_lds, 33 mid_lds, 34 small_nt, 35 mid_nt, 36 ldn, 37 hybrid,
+ *   38 cert_large, 39 guard_abs, 40 exact_K, 41 exact_large_always, 42 lagged, 43 dual_fused, 44 dual_fold,
+ *   45 unit-column table wanted, 46 stamps wanted.
+ * Returns ELLP_OPTIMAL, or the refusal ellp_engine_create would answer for these options with its text: ELLP_ERR_ARG (in the
+ * order: m > 8192; bound flipping with pipeline 1 / 2; steepest edge with partial pricing, pipeline 2 / 3 or btran_mode 1;
+ * bound flipping above 1,024 rows), ELLP_ERR_DEVICE where avail_mask takes k_mid from pipeline 3 or bound flipping; and
+ * ELLP_ERR_ARG for an unknown kind, m < 1, n_N < 0, out NULL or cap < ELLP_PLAN_FIELDS. */
+#define ELLP_PLAN_FIELDS 47
+ellp_status ellp_engine_plan(int kind, int64_t m, int64_t n_N, const ellp_opts *opts, int avail_mask, double *out, int64_t cap,
+                             char *errbuf, size_t errbuf_len);
+
 /* Debug/parity taps: copy an internal device vector to host. what: see ELLP_TAP_*. Returns
  * the number of doubles written (<= cap) or a negative ellp_status. */
 enum { ELLP_TAP_U = 0, ELLP_TAP_R = 1, ELLP_TAP_D = 2, ELLP_TAP_BINV = 3, ELLP_TAP_KEY = 4,

@@ -178,3 +178,19 @@ def fixture_violation(fx, x):
             worst_b = max(worst_b, abs(x[j] - lb))
     return worst_c, worst_b
 
+
+
+def unit_basis_problem(kind, m, nN):
+    """A FlatProblem an engine of `kind` (0 primal, 1 dual) can be created from at any size: A = [A_N | I] with the
+    identity basic (the rebuild takes its permutation shortcut), every variable at its lower bound 0; d = 0 is dual
+    feasible"""
+    import numpy as np
+    from ellp_amd import _engine as E
+    n = m + nN
+    A = np.zeros((m, n), order="F")
+    A[0, :nN] = 1.0
+    A[np.arange(m), nN + np.arange(m)] = 1.0
+    z = np.zeros(n)
+    y, d = (np.zeros(m), np.zeros(n)) if kind == E.ENGINE_DUAL else (None, None)
+    return E.FlatProblem(m, n, n, A.reshape(-1, order="F"), z, np.zeros(m), np.full(n, 1, dtype=np.uint8), z, np.full(n, np.inf), z,
+                         nN + np.arange(m, dtype=np.int64), np.arange(nN, dtype=np.int64), np.zeros(nN, dtype=np.uint8), y=y, d=d)
