@@ -119,6 +119,8 @@ def lib():
     L.ellp_engine_debug_scale_inverse.argtypes = [C.c_void_p, C.c_double]
     L.ellp_engine_debug_set_inverse.restype = C.c_int
     L.ellp_engine_debug_set_inverse.argtypes = [C.c_void_p, C.c_void_p]
+    L.ellp_engine_debug_set_x.restype = C.c_int
+    L.ellp_engine_debug_set_x.argtypes = [C.c_void_p, C.c_void_p]
     L.ellp_engine_set_shard.restype = C.c_int
     L.ellp_engine_set_shard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_size_t]
     L.ellp_engine_segment_doubles.restype = C.c_int64
@@ -573,6 +575,14 @@ class Engine:
         s = lib().ellp_engine_debug_set_inverse(self._h, _p(W_))
         if s != OPTIMAL:
             raise EllpHipError(s, "debug_set_inverse failed")
+
+    def debug_set_x(self, x):
+        """test hook: x <- x (n_c doubles by variable index): the mirror of the x read_point returns"""
+        x_ = _f64(x).reshape(-1)
+        assert x_.size == self.fp.n_c
+        s = lib().ellp_engine_debug_set_x(self._h, _p(x_))
+        if s != OPTIMAL:
+            raise EllpHipError(s, "debug_set_x failed")
 
     def counters(self):
         """host-side maintenance counters (TAP_STATE tail)"""

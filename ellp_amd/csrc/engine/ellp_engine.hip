@@ -2118,7 +2118,12 @@ __global__ __launch_bounds__(256) void k_btran_reduce(BtranArgs a) { btran_reduc
 // same shape as k_btran_part: tiles of basis columns, coalesced along the rows, partials in
 // `upart`; k_drift_reduce folds them in a fixed order (deterministic: replicated engines of a
 // sharded run must take the same decision) and raises DevState::tiny — the maintenance request of
-// a tiny pivot — when max|t| exceeds drift_tol * max|a_q|.
+// a tiny pivot — when max|t| exceeds drift_tol * max|a_q|, or is not a number.
+
+// NaN-propagating maximum of two residuals (fmax returns the other operand when one is NaN, so a NaN in
+// B^-1 would fold away and the residual would look small): NaN if either is NaN, else the larger.
+__device__ __forceinline__ double nanmax(double a, double b) { return (a != a) ? a : ((b > a || b != b) ? b : a); }
+
 struct DriftArgs {
     const double *A_B, *A_N, *d;
     const double *aq_cur;  // column-sharded engines: the entering column
@@ -2157,13 +2162,13 @@ __global__ __launch_bounds__(1024) void k_drift_reduce(DriftArgs a) {
         double t = 0.0;
         for (int k = 0; k < a.ntiles; ++k) t += a.upart[(int64_t)k * a.ld + i];
         const double q = aq[i];
-        res = fmax(res, fabs(sgn * t - q));
-        scale = fmax(scale, fabs(q));
+        res = nanmax(res, fabs(sgn * t - q));
+        scale = nanmax(scale, fabs(q));
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        res = fmax(res, __shfl_xor(res, o));
-        scale = fmax(scale, __shfl_xor(scale, o));
+        res = nanmax(res, __shfl_xor(res, o));
+        scale = nanmax(scale, __shfl_xor(scale, o));
     }
     if (lane == 0) {
         s_r[wave] = res;
@@ -2172,8 +2177,8 @@ __global__ __launch_bounds__(1024) void k_drift_reduce(DriftArgs a) {
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 16; ++w) {
-            res = fmax(res, s_r[w]);
-            scale = fmax(scale, s_s[w]);
+            res = nanmax(res, s_r[w]);
+            scale = nanmax(scale, s_s[w]);
         }
         const double rel = res / (scale > 0.0 ? scale : 1.0);
         st->drift = rel;
@@ -2439,9 +2444,7 @@ __global__ void k_ref_finish(RefArgs a) { ref_finish_body(a); }
 //   B(k,j) = B[k*ld + j] (row-major) in both uses.
 // WSEL picks operands from the two B^-1 buffers by st->cur on the device.
 
-// NaN-propagating maximum of two residuals (fmax returns the other operand when one is NaN, so a NaN in
-// B^-1 would fold away and the residual would look small): NaN if either is NaN, else the larger.
-__device__ __forceinline__ double nanmax(double a, double b) { return (a != a) ? a : ((b > a || b != b) ? b : a); }
+// The residual folds below use nanmax (defined above the drift monitor, which folds with it too).
 
 struct GemmArgs {
     double *W0, *W1;
@@ -5503,6 +5506,18 @@ ellp_status ellp_engine_debug_set_inverse(ellp_engine *e, const double *W) {
         return ELLP_ERR_DEVICE;
     if (hipStreamSynchronize(e->stream) != hipSuccess) return ELLP_ERR_DEVICE;
     e->u_valid = false;
+    return ELLP_OPTIMAL;
+}
+
+ellp_status ellp_engine_debug_set_x(ellp_engine *e, const double *x) {
+    if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
+    if (!e || !x) return ELLP_ERR_ARG;
+    if (hipSetDevice(e->device) != hipSuccess) return ELLP_ERR_DEVICE;
+    // the mirror of the x of ellp_engine_read_point: n_c doubles by variable index, on a complete state as there
+    launch_flush(e);  // two-launch pipeline: the open iteration's update of x comes first, not on top of what is set
+    if (e->n_c > 0 && hipMemcpyAsync(e->x, x, sizeof(double) * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream) != hipSuccess)
+        return ELLP_ERR_DEVICE;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return ELLP_ERR_DEVICE;
     return ELLP_OPTIMAL;
 }
 

@@ -546,6 +546,13 @@ ellp_status ellp_engine_debug_scale_inverse(ellp_engine *e, double factor);
  * engine's state follows: x_B stays as it is until the next maintenance. */
 ellp_status ellp_engine_debug_set_inverse(ellp_engine *e, const double *W);
 
+/* Test hook: replaces the engine's point by x, n_c doubles by variable index in host memory: the mirror
+ * of the x that ellp_engine_read_point returns (what is set is what it reads back, bit for bit).  Nothing
+ * else of the engine's state follows (the carried objective, the dual's leaving row): it is there to put
+ * a chosen x_B in front of the next maintenance.  An iteration the two-launch pipeline has left open is
+ * completed first, as ellp_engine_read_point does. */
+ellp_status ellp_engine_debug_set_x(ellp_engine *e, const double *x);
+
 /* max_ij |(B^-1 A_B - I)_ij| computed on device (drift monitor; tests); NaN if any
  * entry is NaN: never a finite number for an inverse that holds a NaN or an Inf. */
 double ellp_engine_inverse_residual(ellp_engine *e);
