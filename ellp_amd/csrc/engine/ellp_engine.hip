@@ -2070,42 +2070,103 @@ struct BtranArgs {
     int rows_per_tile, ntiles;
 };
 
+// The streaming loop the three tiled GEMVs of this file share (BTRAN, drift monitor, front of the resync): one thread
+// owns the double2 column c2 of a tile of rows [i0, i1) of M2 (`half` double2 a row) and folds
+//     acc = fma(coef[i], M2[i][c2], acc)   for i ascending, with SKIP only where coef[i] != 0
+// — that order is the arithmetic and stays.  What is arranged here is when the loads are issued: a load behind a test of
+// coef[i] is a basic block of its own and the rows come in one round trip after the other.  So wave 0 first compacts the
+// rows that take part (the same for every thread of the workgroup), 64 at a time and in ascending order, into LDS; then
+// every thread fetches them in batches of TILE_BATCH loads that are all issued before the first fma that needs one.  A
+// short last batch repeats its last row's load (a valid address) and leaves the fma out.
+// Called by every thread of a 256-thread workgroup (it synchronises); `active`: this thread has a column.
+constexpr int TILE_BATCH = 8;
+// keeps a batch of loads a batch: the value has to be in its register here, so the compiler cannot sink a load into the
+// branch that uses it (which it does with the loads of a short batch, one round trip each)
+__device__ __forceinline__ void loaded(double &v) { asm volatile("" : "+v"(v)); }
+__device__ __forceinline__ void loaded(double2 &v) {
+    loaded(v.x);
+    loaded(v.y);
+}
+template <bool SKIP>
+__device__ __forceinline__ double2 tile_stream(const double2 *M2, int64_t half, int64_t c2, bool active, const double *coef,
+                                               int64_t i0, int64_t i1) {
+    __shared__ double s_c[WAVE];
+    __shared__ int s_i[WAVE];
+    __shared__ int s_n;
+    double2 acc = make_double2(0.0, 0.0);
+    for (int64_t base = i0; base < i1; base += WAVE) {
+        if (threadIdx.x < WAVE) {
+            const int lane = threadIdx.x;
+            const int64_t i = base + lane;
+            const double ci = i < i1 ? coef[i] : 0.0;
+            const bool keep = i < i1 && (!SKIP || ci != 0.0);
+            const unsigned long long mask = __ballot(keep);
+            if (keep) {
+                const int p = __popcll(mask & ((1ull << lane) - 1ull));
+                s_c[p] = ci;
+                s_i[p] = lane;
+            }
+            if (lane == 0) s_n = __popcll(mask);
+        }
+        __syncthreads();
+        const int n = s_n;
+        if (active) {
+            const double2 *col = M2 + base * half + c2;
+            for (int k = 0; k < n; k += TILE_BATCH) {
+                double2 w[TILE_BATCH];
+#pragma unroll
+                for (int b = 0; b < TILE_BATCH; ++b) w[b] = col[(int64_t)s_i[k + b < n ? k + b : n - 1] * half];
+#pragma unroll
+                for (int b = 0; b < TILE_BATCH; ++b) loaded(w[b]);
+#pragma unroll
+                for (int b = 0; b < TILE_BATCH; ++b) {
+                    if (k + b < n) {
+                        const double ci = s_c[k + b];
+                        acc.x = fma(ci, w[b].x, acc.x);
+                        acc.y = fma(ci, w[b].y, acc.y);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    return acc;
+}
+
+// s = 0.0; s += p[t * ld] for t ascending: what folds the partials of the three tiled GEMVs, one thread per entry.  The loads
+// come in batches of FOLD_BATCH (a short last batch repeats its first load and leaves the addition out), the additions in order.
+constexpr int FOLD_BATCH = 16;
+__device__ __forceinline__ double fold_tiles(const double *p, int64_t ld, int ntiles) {
+    double s = 0.0;
+    for (int t = 0; t < ntiles; t += FOLD_BATCH) {
+        double v[FOLD_BATCH];
+#pragma unroll
+        for (int b = 0; b < FOLD_BATCH; ++b) v[b] = p[(int64_t)(t + b < ntiles ? t + b : t) * ld];
+#pragma unroll
+        for (int b = 0; b < FOLD_BATCH; ++b) loaded(v[b]);
+#pragma unroll
+        for (int b = 0; b < FOLD_BATCH; ++b)
+            if (t + b < ntiles) s += v[b];
+    }
+    return s;
+}
+
 __device__ __forceinline__ void btran_part_body(BtranArgs a, unsigned bx, unsigned by) {
     if (a.st->status != ST_RUNNING) return;
     const int64_t half = a.ld >> 1;
     const int64_t j2 = (int64_t)bx * 256 + threadIdx.x;
     const int64_t i0 = (int64_t)by * a.rows_per_tile;
     const int64_t i1 = (i0 + a.rows_per_tile < a.m) ? i0 + a.rows_per_tile : a.m;
-    double2 acc = make_double2(0.0, 0.0);
-    if (j2 < half) {
-        const double2 *W2 = reinterpret_cast<const double2 *>(a.st->cur ? a.W1 : a.W0);
-        for (int64_t i = i0; i < i1; ++i) {
-            const double ci = a.c_B[i];
-            if (ci != 0.0) {
-                const double2 w = W2[i * half + j2];
-                acc.x = fma(ci, w.x, acc.x);
-                acc.y = fma(ci, w.y, acc.y);
-            }
-        }
-        reinterpret_cast<double2 *>(a.upart)[(int64_t)by * half + j2] = acc;
-    }
+    const double2 *W2 = reinterpret_cast<const double2 *>(a.st->cur ? a.W1 : a.W0);
+    const double2 acc = tile_stream<true>(W2, half, j2, j2 < half, a.c_B, i0, i1);
+    if (j2 < half) reinterpret_cast<double2 *>(a.upart)[(int64_t)by * half + j2] = acc;
 }
 __global__ __launch_bounds__(256) void k_btran_part(BtranArgs a) { btran_part_body(a, blockIdx.x, blockIdx.y); }
 __device__ __forceinline__ void btran_reduce_body(BtranArgs a, unsigned bx) {
     if (a.st->status != ST_RUNNING) return;
     const int64_t j = (int64_t)bx * 256 + threadIdx.x;
     if (j >= a.ld) return;
-    double s = 0.0;
-    int t = 0;
-    for (; t + 8 <= a.ntiles; t += 8) {
-        double v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = a.upart[(int64_t)(t + k) * a.ld + j];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += v[k];
-    }
-    for (; t < a.ntiles; ++t) s += a.upart[(int64_t)t * a.ld + j];
-    (a.st->usel ? a.u_alt : a.u)[j] = s;
+    (a.st->usel ? a.u_alt : a.u)[j] = fold_tiles(a.upart + j, a.ld, a.ntiles);
 }
 __global__ __launch_bounds__(256) void k_btran_reduce(BtranArgs a) { btran_reduce_body(a, blockIdx.x); }
 
@@ -2139,31 +2200,35 @@ __global__ __launch_bounds__(256) void k_drift_part(DriftArgs a) {
     const int64_t i2 = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t k0 = (int64_t)blockIdx.y * a.cols_per_tile;
     const int64_t k1 = (k0 + a.cols_per_tile < a.m) ? k0 + a.cols_per_tile : a.m;
-    if (i2 >= half) return;
-    const double2 *AB2 = reinterpret_cast<const double2 *>(a.A_B);
-    double2 acc = make_double2(0.0, 0.0);
-    for (int64_t k = k0; k < k1; ++k) {
-        const double dk = a.d[k];
-        const double2 c = AB2[k * half + i2];
-        acc.x = fma(dk, c.x, acc.x);
-        acc.y = fma(dk, c.y, acc.y);
-    }
-    reinterpret_cast<double2 *>(a.upart)[(int64_t)blockIdx.y * half + i2] = acc;
+    // k_drift_reduce folds its maxima into DevState::drift with atomicMax: start it from +0.0
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.st->drift = 0.0;
+    const double2 acc = tile_stream<false>(reinterpret_cast<const double2 *>(a.A_B), half, i2, i2 < half, a.d, k0, k1);
+    if (i2 < half) reinterpret_cast<double2 *>(a.upart)[(int64_t)blockIdx.y * half + i2] = acc;
 }
-__global__ __launch_bounds__(1024) void k_drift_reduce(DriftArgs a) {
-    __shared__ double s_r[16], s_s[16];
+// One wave per 64 rows, one row per lane: t_i = the partials of row i added in tile order (fold_tiles).  There is no workgroup that sees every row, and none is needed: max|a_q| does not
+// depend on the partials, so every wave takes it over all of a_q itself (8 m bytes out of the L2); dividing by one positive
+// scale is monotone, so the largest of the waves' res / scale IS max res / scale, bit for bit; and the bit pattern of
+// a non-negative double orders like the number, with every NaN (fabs has cleared its sign) above +Inf.  So each wave
+// folds its quotient into DevState::drift (which k_drift_part has put to +0.0) with atomicMax on the bit pattern, NaN wins
+// as it does in nanmax, and the wave whose quotient exceeds the tolerance, or is NaN, raises the request.
+__global__ __launch_bounds__(WAVE) void k_drift_reduce(DriftArgs a) {
     DevState *st = a.st;
     if (st->status != ST_RUNNING || st->pp_skip) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * WAVE + lane;
     const double sgn = st->s_at_lower ? -1.0 : 1.0;  // alpha = sgn * d (k_ftran2 stores d = +-alpha)
     const double *aq = a.aq_cur ? a.aq_cur : a.A_N + st->s_q * a.ld;
     double res = 0.0, scale = 0.0;
-    for (int64_t i = tid; i < a.m; i += 1024) {
-        double t = 0.0;
-        for (int k = 0; k < a.ntiles; ++k) t += a.upart[(int64_t)k * a.ld + i];
-        const double q = aq[i];
-        res = nanmax(res, fabs(sgn * t - q));
-        scale = nanmax(scale, fabs(q));
+    for (int64_t r0 = lane; r0 < a.m; r0 += 8 * WAVE) {
+        double q[8];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) q[b] = aq[r0 + b * WAVE < a.m ? r0 + b * WAVE : r0];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) scale = nanmax(scale, fabs(q[b]));  // a repeated entry changes no maximum
+    }
+    if (i < a.m) {
+        const double t = fold_tiles(a.upart + i, a.ld, a.ntiles);
+        res = nanmax(res, fabs(sgn * t - aq[i]));
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -2171,17 +2236,8 @@ __global__ __launch_bounds__(1024) void k_drift_reduce(DriftArgs a) {
         scale = nanmax(scale, __shfl_xor(scale, o));
     }
     if (lane == 0) {
-        s_r[wave] = res;
-        s_s[wave] = scale;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 16; ++w) {
-            res = nanmax(res, s_r[w]);
-            scale = nanmax(scale, s_s[w]);
-        }
         const double rel = res / (scale > 0.0 ? scale : 1.0);
-        st->drift = rel;
+        atomicMax(reinterpret_cast<unsigned long long *>(&st->drift), (unsigned long long)__double_as_longlong(rel));
         if (rel > a.tol || rel != rel) st->tiny = 1;
     }
 }
@@ -2221,25 +2277,17 @@ __device__ __forceinline__ void resync_part_body(ResyncArgs a, unsigned bx, unsi
     const int64_t i2 = (int64_t)bx * 256 + threadIdx.x;
     const int64_t j0 = (int64_t)by * a.cols_per_tile;
     const int64_t j1 = (j0 + a.cols_per_tile < a.nN) ? j0 + a.cols_per_tile : a.nN;
-    if (i2 >= half) return;
-    const double2 *AN2 = reinterpret_cast<const double2 *>(a.A_N);
-    double2 acc = make_double2(0.0, 0.0);
-    for (int64_t j = j0; j < j1; ++j) {
-        const double xj = a.xg[j];
-        if (xj == 0.0) continue;
-        const double2 c = AN2[j * half + i2];
-        acc.x = fma(xj, c.x, acc.x);
-        acc.y = fma(xj, c.y, acc.y);
-    }
-    reinterpret_cast<double2 *>(a.upart)[(int64_t)by * half + i2] = acc;
+    const double2 acc = tile_stream<true>(reinterpret_cast<const double2 *>(a.A_N), half, i2, i2 < half, a.xg, j0, j1);
+    if (i2 < half) reinterpret_cast<double2 *>(a.upart)[(int64_t)by * half + i2] = acc;
 }
 __global__ __launch_bounds__(256) void k_resync_part(ResyncArgs a) { resync_part_body(a, blockIdx.x, blockIdx.y); }
 __device__ __forceinline__ void resync_rhs_body(ResyncArgs a, unsigned bx) {
+    // the two maxima of k_resync_xb, which runs behind this kernel, start from +0.0 (whatever the status: as the memset did)
+    if (bx == 0 && threadIdx.x == 0) a.maxbits[0] = a.maxbits[1] = 0ull;
     if (a.st->status != ST_RUNNING && a.st->status != ST_NEED_MAINT) return;
     const int64_t i = (int64_t)bx * 256 + threadIdx.x;
     if (i >= a.ld) return;
-    double s = 0.0;
-    for (int k = 0; k < a.ntiles; ++k) s += a.upart[(int64_t)k * a.ld + i];
+    const double s = fold_tiles(a.upart + i, a.ld, a.ntiles);
     a.tvec[i] = i < a.m ? a.b[i] - s : 0.0;
 }
 __global__ __launch_bounds__(256) void k_resync_rhs(ResyncArgs a) { resync_rhs_body(a, blockIdx.x); }
@@ -2254,19 +2302,44 @@ __device__ __forceinline__ void resync_xb_body(ResyncArgs a, unsigned bx) {
     const double2 *row = reinterpret_cast<const double2 *>((a.st->cur ? a.W1 : a.W0) + i * a.ld);
     const double2 *t2 = reinterpret_cast<const double2 *>(a.tvec);
     double acc0 = 0.0, acc1 = 0.0;
-    for (int64_t t = lane; t < half; t += WAVE) {
-        const double2 w = row[t], v = t2[t];
-        acc0 = fma(w.x, v.x, acc0);
-        acc1 = fma(w.y, v.y, acc1);
+    // per lane t = lane, lane + 64, ... as ever; eight rows' and eight t's loads are issued before the first fma (a lane
+    // past the end of the row repeats its first load and leaves the fma out)
+    for (int64_t t0 = lane; t0 < half; t0 += 8 * WAVE) {
+        double2 w[8], v[8];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const int64_t t = t0 + b * WAVE < half ? t0 + b * WAVE : t0;
+            w[b] = row[t];
+            v[b] = t2[t];
+        }
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            loaded(w[b]);
+            loaded(v[b]);
+        }
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            if (t0 + b * WAVE < half) {
+                acc0 = fma(w[b].x, v[b].x, acc0);
+                acc1 = fma(w[b].y, v[b].y, acc1);
+            }
+        }
     }
     const double r = wave_sum(acc0 + acc1);
     if (lane == 0) {
         const double xo = a.x[a.B_index[i]];
         a.cand[i] = r;
         const double df = fabs(r - xo), ax = fabs(xo);
-        if (df == df) atomicMax(&a.maxbits[0], (unsigned long long)__double_as_longlong(df));
-        else atomicMax(&a.maxbits[0], 0x7ff0000000000000ull);  // NaN: adopt nothing sensible anyway
-        if (ax == ax) atomicMax(&a.maxbits[1], (unsigned long long)__double_as_longlong(ax));
+        // m atomics on one address queue up behind each other (25 ns a row: the whole kernel's time at 2,000 rows).  A maximum
+        // only grows, so a row whose value is not above what the word holds already (read plainly; a stale, smaller value
+        // only costs the atomic it would have cost anyway) has nothing to add.
+        const unsigned long long dbits = df == df ? (unsigned long long)__double_as_longlong(df)
+                                                  : 0x7ff0000000000000ull;  // NaN: adopt nothing sensible anyway
+        if (dbits > __atomic_load_n(&a.maxbits[0], __ATOMIC_RELAXED)) atomicMax(&a.maxbits[0], dbits);
+        if (ax == ax) {
+            const unsigned long long xbits = (unsigned long long)__double_as_longlong(ax);
+            if (xbits > __atomic_load_n(&a.maxbits[1], __ATOMIC_RELAXED)) atomicMax(&a.maxbits[1], xbits);
+        }
     }
 }
 __global__ __launch_bounds__(256) void k_resync_xb(ResyncArgs a) { resync_xb_body(a, blockIdx.x); }
@@ -3409,8 +3482,7 @@ ResyncArgs launch_resync_rhs(ellp_engine *e, int force) {
 void launch_resync(ellp_engine *e, int force) {
     if (e->nN <= 0) return;
     if (e->colshard) return;  // b - A_N x_N would need every rank's columns (a reduction over the ranks): not done
-    (void)hipMemsetAsync(e->maxbits, 0, 2 * sizeof(unsigned long long), e->stream);
-    const ResyncArgs a = launch_resync_rhs(e, force);
+    const ResyncArgs a = launch_resync_rhs(e, force);  // k_resync_rhs also zeroes maxbits
     hipLaunchKernelGGL(k_resync_xb, dim3((unsigned)((e->m + 3) / 4)), dim3(256), 0, e->stream, a);
     hipLaunchKernelGGL(k_resync_apply, dim3((unsigned)((e->m + 255) / 256)), dim3(256), 0, e->stream, a);
     if (e->kind == ELLP_ENGINE_DUAL) launch_dleave(e);  // the leaving row is chosen from x (dual…:200-236)
@@ -3507,7 +3579,7 @@ void launch_drift_check(ellp_engine *e) {
     const int64_t half = e->ld >> 1;
     hipLaunchKernelGGL(k_drift_part, dim3((unsigned)((half + 255) / 256), (unsigned)e->btran_tiles), dim3(256), 0,
                        e->stream, a);
-    hipLaunchKernelGGL(k_drift_reduce, dim3(1), dim3(1024), 0, e->stream, a);
+    hipLaunchKernelGGL(k_drift_reduce, dim3((unsigned)((e->m + WAVE - 1) / WAVE)), dim3(WAVE), 0, e->stream, a);
 }
 
 // ---- two-launch pipeline (ellp_lagged.inc) -------------------------------------------------------
@@ -5355,6 +5427,8 @@ int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap) {
         count = e->nN;
         break;
     case ELLP_TAP_D: src = e->d; count = e->m; break;
+    case ELLP_TAP_RESYNC_T: src = e->tvec; count = e->m; break;
+    case ELLP_TAP_RESYNC_CAND: src = e->cand; count = e->m; break;
     case ELLP_TAP_SE_GAMMA:  // steepest-edge weights by nonbasic position, as the last pricing launch left them (include/ellp_hip.h)
         if (!e->se) return ELLP_ERR_ARG;
         src = e->se_gamma;

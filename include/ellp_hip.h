@@ -520,7 +520,9 @@ enum { ELLP_TAP_U = 0, ELLP_TAP_R = 1, ELLP_TAP_D = 2, ELLP_TAP_BINV = 3, ELLP_T
                                 weights are those of the basis and the position order that the LAST PRICING LAUNCH priced: after
                                 ellp_engine_run(e, k) they belong to the point ellp_engine_read_point returned after run(k - 1)
                                 (at creation and after ellp_engine_rephase: to the point the engine stands on).  ELLP_ERR_ARG on
-                                an engine without the flag. */ };
+                                an engine without the flag. */,
+       ELLP_TAP_RESYNC_T = 8 /* t = b - A_N x_N as the last x_B resync (or the primal phase-1 start) formed it, m doubles */,
+       ELLP_TAP_RESYNC_CAND = 9 /* cand = B^-1 t of the last x_B resync, adopted or not, m doubles */ };
 int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap);
 
 /* One Newton-Schulz step W <- W + W (I - A_B W) on the resident inverse (two f64 GEMMs); this
