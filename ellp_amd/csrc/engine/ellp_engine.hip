@@ -150,9 +150,10 @@ struct DevState {
 };
 
 #ifdef ELLP_DBG_STAMPS
-#define STAMP(kern, slot)                                                                          \
+#define STAMP(kern, slot) STAMP_AT(kern, slot, 0)
+#define STAMP_AT(kern, slot, thr)                                                                  \
     do {                                                                                           \
-        if (threadIdx.x == 0) {                                                                    \
+        if (threadIdx.x == (thr)) {                                                                \
             const int bsel_ = blockIdx.x == 0 ? 0 : blockIdx.x == 1 ? 1 : blockIdx.x == gridDim.x / 2 ? 2 \
                               : blockIdx.x == gridDim.x - 1 ? 3 : -1;                              \
             if (bsel_ >= 0) a.st->dbg[kern][bsel_][slot] = wall_clock64();                         \
@@ -160,6 +161,7 @@ struct DevState {
     } while (0)
 #else
 #define STAMP(kern, slot) do { } while (0)
+#define STAMP_AT(kern, slot, thr) do { } while (0)
 #endif
 
 // optional objective trace (ellp_opts.trace_len): ring of (iteration, objective) pairs, written by whichever
@@ -3673,9 +3675,11 @@ void launch_ftran_eta(ellp_engine *e) {
         else hipLaunchKernelGGL((k_ftran_eta<0, true>), g, b, e->ftran_lds, e->stream, a);
         return;
     }
-    if (nr <= 1) hipLaunchKernelGGL((k_ftran_eta<1>), g, b, e->ftran_lds, e->stream, a);
-    else if (nr <= 2) hipLaunchKernelGGL((k_ftran_eta<2>), g, b, e->ftran_lds, e->stream, a);
-    else if (nr <= 4) hipLaunchKernelGGL((k_ftran_eta<4>), g, b, e->ftran_lds, e->stream, a);
+    // rows in registers up to 2,048 doubles: wave 0 hands the entering column to the other waves through LDS (+8 ld bytes)
+    const size_t hand_lds = ftran_col_offset(e->nblocks) + sizeof(double) * (size_t)e->ld;
+    if (nr <= 1) hipLaunchKernelGGL((k_ftran_eta<1>), g, b, hand_lds, e->stream, a);
+    else if (nr <= 2) hipLaunchKernelGGL((k_ftran_eta<2>), g, b, hand_lds, e->stream, a);
+    else if (nr <= 4) hipLaunchKernelGGL((k_ftran_eta<4>), g, b, hand_lds, e->stream, a);
     else if (nr <= 8) hipLaunchKernelGGL((k_ftran_eta<8>), g, b, e->ftran_lds, e->stream, a);
     else hipLaunchKernelGGL((k_ftran_eta<0>), g, b, e->ftran_lds, e->stream, a);
 }

@@ -829,9 +829,11 @@ __device__ __forceinline__ void eta_ftran_rows_stream(const double *src, double 
 }
 
 // NR = double2 per thread per row held in registers for the block's first UPD_ROWS rows (ceil(ld/512));
-// NR == 0: all rows are streamed after the fold
-template <int NR, bool SH = false>
-__global__ __launch_bounds__(256) void k_ftran_eta(FtranEtaArgs a) {
+// NR == 0: all rows are streamed after the fold.
+// Every wave folds, stores and reduces in the same order: the body of the sharded instantiations, of NR == 0 and of NR == 8
+// (the unsharded NR = 1, 2, 4 run ftran_eta_handoff below).
+template <int NR, bool SH>
+__device__ __forceinline__ void ftran_eta_whole(const FtranEtaArgs &a) {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ long long s_q;
     __shared__ double s_wk[4];
@@ -1187,4 +1189,429 @@ __global__ __launch_bounds__(256) void k_ftran_eta(FtranEtaArgs a) {
             st->s_lambda0 = (kk == ELLP_BOUND_TWOSIDED) ? a.ub[jq] - a.lb[jq] : (kk == ELLP_BOUND_FIXED ? 0.0 : INFINITY);
         }
     }
+}
+
+// ------------------------------------------------------------------ F, unsharded, rows in registers: one wave decides, three stream
+// A wave has ONE outstanding-memory counter for loads and stores.  A wave that has row stores in flight and then consumes a
+// global load therefore waits for its own store burst to be acknowledged.  So the work of a row block is divided:
+//   wave 0      folds alone (same functions, same values), reads Nb[q], fetches the entering column and leaves column, q and
+//               the sign in LDS; only then it updates and stores its own quarter of the block's columns;
+//   waves 1..3  load their quarter of the rows and the pivot row, store the updated rows as soon as those are there, and take
+//               q and the column from LDS at the hand-off barrier.
+// Rule for every wave: between its first row store and the end of the kernel it consumes no global load.
+// The arithmetic is that of ftran_eta_whole: the same fmas on the same operands in the same order, every thread owns the same
+// columns, every row keeps its butterfly order and the four waves their order ((s0 + s1) + s2) + s3.
+
+// the lanes of one wave run in lockstep: what one lane wrote to LDS is there for the others once the wave's LDS traffic retired
+__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// a use the compiler cannot move: the wait for the load behind `v` stands HERE and not at a later first use
+template <class T>
+__device__ __forceinline__ void retire_here(T &v) { asm volatile("" : "+v"(v)); }
+// byte offset of the entering column behind the staged block maxima in the dynamic LDS of k_ftran_eta
+__host__ __device__ constexpr size_t ftran_col_offset(int nblocks) { return (sizeof(double) * (size_t)nblocks + 16 + 15) & ~(size_t)15; }
+
+// K rows reduced together: every step issues all K exchanges before it waits for one; each row's order is wave_sum's
+template <int K>
+__device__ __forceinline__ void wave_sum_rows(double s[UPD_ROWS]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        double t[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) t[k] = __shfl_xor(s[k], o);
+#pragma unroll
+        for (int k = 0; k < K; ++k) s[k] += t[k];
+    }
+}
+
+template <int NR>
+__device__ __forceinline__ void ftran_eta_handoff(const FtranEtaArgs &a) {
+    static_assert(NR >= 1 && NR <= 4, "rows of at most 2,048 doubles: at most UPD_ROWS rows per block");
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ long long s_q;
+    __shared__ int s_leave, s_atl, s_nh, s_band;
+    __shared__ int s_hblk[FC_SLOTS];
+    __shared__ double s_hkey[FC_SLOTS * 64];
+    __shared__ int32_t s_hidx[FC_SLOTS * 64];
+    __shared__ double s_dot[4][UPD_ROWS];
+    __shared__ double s_lam[UPD_ROWS];
+    __shared__ int s_dp[UPD_ROWS];
+    DevState *st = a.st;
+    STAMP(1, 0);  // -DELLP_DBG_STAMPS builds (tools/stamps.py): 0 entry, 5 block maxima staged, 6 candidates chosen, 1 q known,
+                  // 7 column published, 2 first stores of a streaming wave issued (thread 64), 3 dot products reduced, 4 end
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the ways out that do not depend on q, decided ONCE per block (another block of this launch may raise nan_flag meanwhile)
+    if (tid == 0) s_leave = st->status != ST_RUNNING ? 1 : (st->nan_flag ? 2 : 0);
+    const int src_sel = st->f_src;
+    const int apply = st->pe_valid;
+    const int64_t r = st->pe_r;
+    const double d_r = st->pe_d_r, alpha_r = st->pe_alpha_r;
+    const double *src = src_sel ? a.W1 : a.W0;
+    double *dst = src_sel ? a.W0 : a.W1;
+    const int64_t half = a.ld >> 1, m = a.m;
+    constexpr int NBK = 1;
+    const bool row_block = blockIdx.x >= NBK;
+    const int R = a.rows_per_block;  // <= UPD_ROWS: eight rows per block start at m = 3,072, NR <= 4 ends at ld = 2,048
+    const int64_t row0 = ((int64_t)blockIdx.x - NBK) * R;
+    double *s_bk = reinterpret_cast<double *>(smem);
+    double2 *s_col = reinterpret_cast<double2 *>(smem + ftran_col_offset(a.nblocks));
+
+    // ---- every global value a wave will ever need, requested at entry.  Wave 0: the block maxima of the fold first
+    constexpr int FB = 16;  // block maxima per lane held in registers across the row loads (1,024 pricing blocks)
+    double v0[FB];  // as loaded: every select on a loaded value waits where its branch is taken up again, not here
+    // threads 0..R-1 (in wave 0) own the lambda_i of the block's rows: their gathers hang off B_index
+    const int64_t myrow = row0 + tid;
+    const bool own = row_block && tid < R && myrow < m;
+    int64_t bi0 = 0;
+    if (wave == 0) {
+        const double *pb[FB];
+#pragma unroll
+        for (int u = 0; u < FB; ++u) {
+            const int b = lane + 64 * u;
+            pb[u] = &a.xc.bk(b < a.nblocks ? b : 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // all addresses, then all loads: one round trip
+#pragma unroll
+        for (int u = 0; u < FB; ++u) v0[u] = *pb[u];
+        bi0 = a.B_index[own ? myrow : 0];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    double dv[UPD_ROWS];
+#pragma unroll
+    for (int k = 0; k < UPD_ROWS; ++k) dv[k] = (row_block && k < R && row0 + k < m) ? a.d[row0 + k] : 0.0;
+    // rows and pivot row as loaded (clamped addresses): what lies outside the block's rows or beyond the row's end is
+    // never stored, and reaches the dot products as zero
+    double2 wreg[UPD_ROWS][NR], pr[NR];
+#pragma unroll
+    for (int k = 0; k < UPD_ROWS; ++k) {
+        const int64_t i = row0 + k;
+        const bool ok = row_block && k < R && i < m;
+        const double2 *srow = reinterpret_cast<const double2 *>(src + (ok ? i : 0) * a.ld);
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            const int64_t t = tid + 256 * u;
+            wreg[k][u] = srow[t < half ? t : 0];
+        }
+    }
+    {  // the pivot row of the eta update is known from the state: it comes with the rows
+        const double2 *rho2 = reinterpret_cast<const double2 *>(src + (apply ? r : 0) * a.ld);
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            const int64_t t = tid + 256 * u;
+            pr[u] = rho2[t < half ? t : 0];
+        }
+    }
+    double xi0 = 0.0, lbi0 = 0.0, ubi0 = 0.0;
+    int k0 = 0;
+    lds_barrier();  // every wave of the block arrives: nothing above leaves the kernel
+    const int leave = s_leave;
+    if (leave) {  // block-uniform (LDS).  Nothing of this launch has been stored
+        if (leave == 2 && blockIdx.x == 0 && tid == 0) st->status = ELLP_ERR_NAN;  // fatal: nothing of this engine is used afterwards
+        return;
+    }
+
+    // eta update of this thread's columns of the block's rows: store them, keep the new values for the dot products
+    auto eta_store = [&]() {
+        if (!apply) return;
+#pragma unroll
+        for (int k = 0; k < UPD_ROWS; ++k) {
+            const int64_t i = row0 + k;
+            if (!(k < R && i < m)) continue;
+            const double f = (i != r) ? -(dv[k] / d_r) : 0.0;
+            double2 *drow = reinterpret_cast<double2 *>(dst + i * a.ld);
+#pragma unroll
+            for (int u = 0; u < NR; ++u) {
+                const int64_t t = tid + 256 * u;
+                if (t >= half) continue;
+                double2 o;
+                if (i == r) {
+                    o = make_double2(pr[u].x / alpha_r, pr[u].y / alpha_r);
+                } else {
+                    o.x = fma(f, pr[u].x, wreg[k][u].x);
+                    o.y = fma(f, pr[u].y, wreg[k][u].y);
+                }
+                store_row2<true>(drow + t, o);
+                wreg[k][u] = o;
+            }
+        }
+    };
+
+    // the wait for rows and pivot row stands in front of a wave's first store, whole: a counted wait for a load between
+    // two stores waits for the older store as well
+    auto rows_retired = [&]() {
+#pragma unroll
+        for (int k = 0; k < UPD_ROWS; ++k) {
+            retire_here(dv[k]);
+#pragma unroll
+            for (int u = 0; u < NR; ++u) {
+                retire_here(wreg[k][u].x);
+                retire_here(wreg[k][u].y);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            retire_here(pr[u].x);
+            retire_here(pr[u].y);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), as an instruction the compiler's own wait insertion accounts for
+    };
+
+    if (wave == 0) {
+        // the gathers of the lambda owners (threads 0..R-1 are this wave's): issued here, in no other wave's path
+        xi0 = a.x[bi0];
+        lbi0 = a.lb[bi0];
+        ubi0 = a.ub[bi0];
+        k0 = a.kind[bi0];
+        // ---- the entering fold, by this wave alone: lockstep lanes and wave_lds_sync() stand where the block's barriers stood
+        double tmax = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < FB; ++u) {
+            const bool in = lane + 64 * u < a.nblocks;
+            if (in) s_bk[lane + 64 * u] = v0[u];
+            tmax = fmax(tmax, in ? v0[u] : -INFINITY);
+        }
+        for (int b0 = lane + 64 * FB; b0 < a.nblocks; b0 += 64 * FB) {
+            double v[FB];
+#pragma unroll
+            for (int u = 0; u < FB; ++u) {
+                const int b = b0 + 64 * u;
+                const double t = a.xc.bk(b < a.nblocks ? b : 0);
+                v[u] = b < a.nblocks ? t : -INFINITY;
+            }
+#pragma unroll
+            for (int u = 0; u < FB; ++u) {
+                if (b0 + 64 * u < a.nblocks) s_bk[b0 + 64 * u] = v[u];
+                tmax = fmax(tmax, v[u]);
+            }
+        }
+        if (lane == 0) {
+            s_nh = 0;
+            s_band = 0;
+        }
+        const double M = wave_allmax_dpp(tmax);  // DPP butterfly + readlane (no NaN here: keys are never NaN)
+        wave_lds_sync();
+        STAMP(1, 5);
+        for (int b = lane; b < a.nblocks; b += 64) {
+            const double v = s_bk[b];
+            if (M - v < 4.0 * a.eps) {
+                const int slot = atomicAdd(&s_nh, 1);
+                if (slot < FC_SLOTS) s_hblk[slot] = b;
+            } else if (M - v < 6.0 * a.eps) {
+                s_band = 1;
+            }
+        }
+        wave_lds_sync();
+        STAMP(1, 6);
+        const int nh = s_nh;
+        const bool fast = M > -INFINITY && nh <= FC_SLOTS && !s_band;
+        if (fast) {
+            if (lane == 0) {
+                for (int i = 1; i < nh; ++i) {
+                    const int v = s_hblk[i];
+                    int j = i - 1;
+                    while (j >= 0 && s_hblk[j] > v) {
+                        s_hblk[j + 1] = s_hblk[j];
+                        --j;
+                    }
+                    s_hblk[j + 1] = v;
+                }
+            }
+            wave_lds_sync();
+            for (int sl = 0; sl < nh; ++sl) {
+                const int64_t j = (int64_t)s_hblk[sl] * a.cpb + lane;
+                const bool ok = lane < a.cpb && j < a.nN;
+                const int64_t jc = ok ? j : 0;
+                const double kl = a.xc.key(jc);
+                const int64_t il = a.N_index[jc];
+                const double kv = ok ? kl : -INFINITY;
+                s_hkey[sl * 64 + lane] = kv;
+                s_hidx[sl * 64 + lane] = ok ? (int32_t)il : 0;
+                if (M - kv < 6.0 * a.eps && !(M - kv < 4.0 * a.eps)) s_band = 1;
+            }
+            wave_lds_sync();
+        }
+        long long q = -1;
+        bool done = false;
+        if (fast && !s_band) {
+            FoldState f{false, 0.0, 0, -1};
+            for (int sl = 0; sl < nh; ++sl)
+                fold_elements(f, s_hkey[sl * 64 + lane], s_hidx[sl * 64 + lane], (int64_t)s_hblk[sl] * a.cpb, a.eps, lane);
+            q = f.qacc;
+            done = true;
+        }
+        if (!done && M > -INFINITY) q = entering_fold_full(s_bk, a.nblocks, a.cpb, a.nN, a.xc, a.N_index, a.eps, lane);
+        STAMP(1, 1);
+        // ---- Nb[q] and the column in one round trip; the column goes to LDS for all four waves
+        const bool hc = q >= 0;
+        int nbq = a.Nb[hc ? q : 0];
+        if (row_block && hc) {
+            const double2 *col = reinterpret_cast<const double2 *>(a.A_N + q * a.ld);
+            double2 cv[4 * NR];
+#pragma unroll
+            for (int u = 0; u < 4 * NR; ++u) {
+                const int64_t t = lane + 64 * u;
+                cv[u] = col[t < half ? t : 0];
+            }
+            __builtin_amdgcn_sched_barrier(0);  // all loads, one wait, then the LDS writes: not a round trip per element
+#pragma unroll
+            for (int u = 0; u < 4 * NR; ++u) {
+                retire_here(cv[u].x);
+                retire_here(cv[u].y);
+            }
+#pragma unroll
+            for (int u = 0; u < 4 * NR; ++u) {
+                const int64_t t = lane + 64 * u;
+                if (t < half) s_col[t] = cv[u];
+            }
+        }
+        // every load of this wave is retired here, ahead of the barrier and of its stores
+        retire_here(nbq);
+        retire_here(xi0);
+        retire_here(lbi0);
+        retire_here(ubi0);
+        retire_here(k0);
+        if (lane == 0) {
+            s_q = q;
+            s_atl = hc ? (nbq == ELLP_NB_LOWER ? 1 : 0) : 0;
+        }
+        STAMP(1, 7);
+    }
+    // Passed by every wave on every path, so that no load counts as pending behind it: wave 0 comes here with all its loads
+    // retired by the column's wait, the streaming waves come here straight from the barrier above
+    rows_retired();
+    if (wave != 0 && row_block) {
+        // ---- streaming waves: the update needs rows, rho and the previous d only, nothing the fold produces
+        eta_store();
+        STAMP_AT(1, 2, 64);
+    }
+    // The hand-off.  Every wave that passed the barrier above reaches this one: the only way out in between is `leave`, read
+    // from LDS after that barrier and therefore the same in all four waves, and nothing above returns, whatever the
+    // fold found (q < 0 included: the optimal end still applies the eta update in all waves).  It waits for LDS traffic only,
+    // so the streaming waves' stores stay in flight across it.
+    lds_barrier();
+    const long long q = s_q;
+    const bool have_col = q >= 0;  // block-uniform: LDS
+    const int at_lower = s_atl;
+
+    if (!row_block) {
+        // ---------------- block 0: the deferred half of the column move, then the commit of this iteration
+        if (st->mv_pending) {
+            const int64_t mr = st->mv_r;
+            double2 *cb = reinterpret_cast<double2 *>(a.A_B + mr * a.ld);
+            const double2 *sv = reinterpret_cast<const double2 *>(a.aq_save);
+            for (int64_t t = tid; t < half; t += 256) cb[t] = sv[t];
+            if (tid == 0) a.c_B[mr] = st->cq_save;
+        }
+        if (tid == 0) {
+            const int new_cur = apply ? (src_sel ^ 1) : src_sel;
+            if (st->tiny_p) {  // raised by k_price2's bookkeeping (a tiny pivot): now it may stop the next launch
+                st->tiny_p = 0;
+                st->tiny = 1;
+            }
+            st->mv_pending = 0;
+            st->cur = new_cur;
+            st->usel = st->usel_next;
+            st->s_cur = new_cur;
+            st->iters += 1;  // a loop body is entered (primal…:163-168); its ratio test is folded by the next kernel
+            st->open = q < 0 ? 0 : 1;
+            if (q < 0) {  // primal…:289-292; the status itself is written by the next kernel's leader
+                st->fin = ELLP_OPTIMAL + 1;
+            } else {
+                const int64_t jq = a.N_index[q];
+                ELLP_CHECK(st, q < a.nN, 9111);
+                st->s_q = q;
+                st->s_at_lower = at_lower;
+                st->s_nbq = a.Nb[q];
+                st->s_jq = jq;
+                st->s_rq = a.xc.r(q);
+                const int kk = a.kind[jq];  // primal…:305-311
+                st->s_lambda0 = (kk == ELLP_BOUND_TWOSIDED) ? a.ub[jq] - a.lb[jq] : (kk == ELLP_BOUND_FIXED ? 0.0 : INFINITY);
+            }
+        }
+        return;
+    }
+    if (wave == 0) eta_store();  // fold -> column -> publish -> its own stores
+    if (!have_col) return;       // all four waves together
+
+    // ---- d_i = +-(row . a_q), a_q from LDS: wave sums, then the four waves in a fixed order
+    double acc0[UPD_ROWS], acc1[UPD_ROWS];
+#pragma unroll
+    for (int k = 0; k < UPD_ROWS; ++k) acc0[k] = acc1[k] = 0.0;
+    double2 cq[NR];
+#pragma unroll
+    for (int u = 0; u < NR; ++u) {
+        const int64_t t = tid + 256 * u;
+        const double2 cv = s_col[t < half ? t : 0];
+        cq[u] = t < half ? cv : make_double2(0.0, 0.0);
+    }
+#pragma unroll
+    for (int k = 0; k < UPD_ROWS; ++k) {
+        const int64_t i = row0 + k;
+        if (!(k < R && i < m)) continue;
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            const bool in = tid + 256 * u < half;
+            acc0[k] = fma(in ? wreg[k][u].x : 0.0, cq[u].x, acc0[k]);
+            acc1[k] = fma(in ? wreg[k][u].y : 0.0, cq[u].y, acc1[k]);
+        }
+    }
+    double s[UPD_ROWS];
+#pragma unroll
+    for (int k = 0; k < UPD_ROWS; ++k) s[k] = acc0[k] + acc1[k];
+    // only the R rows the block has (1, 2 or 4), step by step together
+    if (R >= 3) wave_sum_rows<4>(s);
+    else if (R == 2) wave_sum_rows<2>(s);
+    else wave_sum_rows<1>(s);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < UPD_ROWS; ++k) s_dot[wave][k] = s[k];
+    }
+    lds_barrier();  // reached by all four waves or by none: have_col and row_block are block-uniform
+    STAMP(1, 3);
+    if (wave != 0) return;  // no barrier follows: the rest is wave 0's own
+    const double sgn = at_lower ? -1.0 : 1.0;
+    double li = INFINITY;
+    int dp = 0;
+    if (own) {
+        const int k = tid;
+        const double di = sgn * (((s_dot[0][k] + s_dot[1][k]) + s_dot[2][k]) + s_dot[3][k]);
+        a.d[myrow] = di;
+        li = primal_lambda(di, xi0, lbi0, ubi0, k0, a.eps);  // primal…:320-367
+        if (li != li) st->nan_flag = 1;
+        dp = di > 0.0 ? 1 : 0;
+        a.lam[myrow] = li;
+        a.bidx[myrow] = (int32_t)bi0;
+        a.dpos[myrow] = (uint8_t)dp;
+    }
+    if (tid < UPD_ROWS) {
+        s_lam[tid] = li;
+        s_dp[tid] = dp;
+    }
+    wave_lds_sync();
+    if (tid == 0) {  // smallest and second smallest lambda of the block, and whose the smallest is
+        double m1 = INFINITY, m2 = INFINITY;
+        int info = -1;
+        for (int k = 0; k < R; ++k) {
+            const double v = s_lam[k];
+            if (v < m1) {
+                m2 = m1;
+                m1 = v;
+                info = (int)(2 * (row0 + k)) + s_dp[k];
+            } else if (v < m2) {
+                m2 = v;
+            }
+        }
+        a.bmin[blockIdx.x - NBK] = m1;
+        a.bsec[blockIdx.x - NBK] = m2;
+        a.binfo[blockIdx.x - NBK] = info;
+    }
+    STAMP(1, 4);
+}
+
+constexpr bool ftran_eta_hands_off(int NR, bool SH) { return !SH && NR >= 1 && NR <= 4; }
+
+template <int NR, bool SH = false>
+__global__ __launch_bounds__(256) void k_ftran_eta(FtranEtaArgs a) {
+    if constexpr (ftran_eta_hands_off(NR, SH)) ftran_eta_handoff<NR>(a);
+    else ftran_eta_whole<NR, SH>(a);
 }
