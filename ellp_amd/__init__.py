@@ -83,6 +83,12 @@ class _Result(C.Structure):
                 ("iters_phase1", C.c_uint64), ("iters_phase2", C.c_uint64), ("err", C.c_char * 512)]
 
 
+class _ResultEx(C.Structure):
+    """ellp_result_ex (include/ellp_host.h)"""
+    _fields_ = [("result", _Result), ("has_postsolve", C.c_int), ("n_duals", C.c_int64), ("duals", C.POINTER(C.c_double)),
+                ("n_reduced_costs", C.c_int64), ("reduced_costs", C.POINTER(C.c_double)), ("kkt", _engine.Kkt)]
+
+
 class _FlatPhase(C.Structure):
     _fields_ = ([(k, C.c_int64) for k in ("m", "n", "n_c", "n_B", "n_N")] +
                 [(k, C.POINTER(C.c_double)) for k in ("A", "c", "b", "lb", "ub", "x", "y", "d")] +
@@ -126,6 +132,9 @@ def host_lib():
     L.ellp_solve.restype = C.c_int
     L.ellp_solve.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Opts), C.POINTER(_Result)]
     L.ellp_result_free.argtypes = [C.POINTER(_Result)]
+    L.ellp_solve_ex.restype = C.c_int
+    L.ellp_solve_ex.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_int, C.POINTER(_ResultEx)]
+    L.ellp_result_ex_free.argtypes = [C.POINTER(_ResultEx)]
     L.ellp_solve_batch.restype = C.c_int
     L.ellp_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_void_p]
     L.ellp_debug_phase1.restype = C.c_int
@@ -223,16 +232,37 @@ class Problem:
 
 
 class Solution:
-    """src/solver.rs:35-54"""
+    """src/solver.rs:35-54; with solve(prob, postsolve=True) also duals(), reduced_costs() and kkt().
 
-    def __init__(self, obj, x):
-        self._obj, self._x = obj, x
+    Sign convention: the problem is a minimisation, d = c - A^T y, and duals()[i] is the derivative of the optimal objective
+    with respect to the right-hand side of constraint i: <= 0 for a binding `<=` row, >= 0 for a binding `>=` row, and 0.0
+    for a row the rank check dropped as redundant."""
+
+    def __init__(self, obj, x, post=None):
+        self._obj, self._x, self._post = obj, x, post
 
     def obj(self):
         return self._obj
 
     def x(self):
         return self._x
+
+    def _postsolve(self):
+        if self._post is None:
+            raise EllPError("solve(..., postsolve=True) was not asked for")
+        return self._post
+
+    def duals(self):
+        """one per constraint of the Problem, in order"""
+        return self._postsolve()[0]
+
+    def reduced_costs(self):
+        """one per variable of the Problem, in order"""
+        return self._postsolve()[1]
+
+    def kkt(self):
+        """the report of ellp_kkt (include/ellp_hip.h) as a dict, for the final point in standard form"""
+        return self._postsolve()[2]
 
 
 class SolverResult:
@@ -266,7 +296,23 @@ class _Solver:
     def default(cls):
         return cls()
 
-    def solve(self, prob):
+    def solve(self, prob, postsolve=False):
+        """postsolve=True: an Optimal result's Solution also has duals(), reduced_costs() and kkt() (one more pass on the
+        device after the solve; off by default, and off means not one extra device call)."""
+        if postsolve:
+            rx = _ResultEx()
+            host_lib().ellp_solve_ex(prob._h, self._KIND, self.max_iter,
+                                     C.byref(self._opts) if self._opts is not None else None, 1, C.byref(rx))
+            try:
+                res = _to_result(rx.result)
+                if res.kind == SolverResult.Optimal and rx.has_postsolve:
+                    y = np.ctypeslib.as_array(rx.duals, shape=(rx.n_duals,)).copy() if rx.n_duals else np.zeros(0)
+                    d = (np.ctypeslib.as_array(rx.reduced_costs, shape=(rx.n_reduced_costs,)).copy()
+                         if rx.n_reduced_costs else np.zeros(0))
+                    res.solution._post = (y, d, rx.kkt.as_dict())
+                return res
+            finally:
+                host_lib().ellp_result_ex_free(C.byref(rx))
         r = _Result()
         host_lib().ellp_solve(prob._h, self._KIND, self.max_iter,
                               C.byref(self._opts) if self._opts is not None else None, C.byref(r))

@@ -49,6 +49,17 @@ class Stats(C.Structure):
         return d
 
 
+class Kkt(C.Structure):
+    """ellp_kkt (include/ellp_hip.h): the report of a postsolve"""
+    _fields_ = [("primal_residual", C.c_double), ("bound_violation", C.c_double), ("dual_infeasibility", C.c_double),
+                ("basic_reduced_cost", C.c_double), ("y_backward_error", C.c_double), ("primal_obj", C.c_double),
+                ("dual_obj", C.c_double), ("worst_row", C.c_int64), ("worst_bound_var", C.c_int64),
+                ("worst_dual_var", C.c_int64), ("refinement_steps", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 # int fn(void *user, void *host_buffer, int64_t segment_bytes, int world)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
 
@@ -176,6 +187,11 @@ def lib():
     L.ellp_hip_lu_rows_last_ms.argtypes = []
     L.ellp_engine_shard_info.restype = C.c_int
     L.ellp_engine_shard_info.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.ellp_engine_postsolve.restype = C.c_int
+    L.ellp_engine_postsolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Kkt), C.c_char_p, C.c_size_t]
+    L.ellp_postsolve.restype = C.c_int
+    L.ellp_postsolve.argtypes = _PROBLEM_ARGS + [C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Kkt),
+                                                 C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -335,6 +351,18 @@ def dual_solve_with_initial(fp, opts=None):
     s = lib().ellp_dual_solve_with_initial(*fp._args(), _p(fp.y), _p(fp.d), C.byref(o), C.byref(st),
                                            err, 512)
     return s, st, err.value.decode()
+
+
+def postsolve(fp, opts=None):
+    """ellp_postsolve: duals, reduced costs, the row residual and the KKT report of the point a FlatProblem holds (the arrays
+    a solve_with_initial call left).  Returns (y, d, r, kkt_dict); raises EllpHipError on any status but OPTIMAL."""
+    o = opts or default_opts()
+    y, d, r, k = np.zeros(max(fp.m, 0)), np.zeros(max(fp.n_c, 0)), np.zeros(max(fp.m, 0)), Kkt()
+    err = C.create_string_buffer(512)
+    s = lib().ellp_postsolve(*fp._args(), C.byref(o), _p(y), _p(d), _p(r), C.byref(k), err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    return y, d, r, k.as_dict()
 
 
 class BatchItem(C.Structure):
@@ -527,6 +555,19 @@ class Engine:
         if s not in (OPTIMAL, UNBOUNDED, MAXITER):
             raise EllpHipError(s, err.value.decode())
         return fp
+
+    def postsolve(self):
+        """ellp_engine_postsolve on the basis and point the engine stands on: (y, d, r, kkt_dict) — y = B^-T c_B from a fresh
+        LU, refined; d = c - A^T y by variable; r = b - A x; the report of include/ellp_hip.h.  The engine's state is not
+        touched.  closing_status as for read_point (an open iteration of the two-launch pipeline is completed first)."""
+        fp = self.fp
+        y, d, r, k = np.zeros(fp.m), np.zeros(fp.n_c), np.zeros(fp.m), Kkt()
+        err = C.create_string_buffer(512)
+        s = lib().ellp_engine_postsolve(self._h, _p(y), _p(d), _p(r), C.byref(k), err, 512)
+        self.closing_status = s
+        if s not in (OPTIMAL, UNBOUNDED, MAXITER):
+            raise EllpHipError(s, err.value.decode())
+        return y, d, r, k.as_dict()
 
     def tap(self, what, count):
         out = np.zeros(int(count), dtype=np.float64)

@@ -3076,6 +3076,17 @@ struct ellp_engine : EnginePlan {  // the fields creation decides are the plan's
     double *ex_rhs = nullptr, *ex_sol = nullptr, *ex_rho = nullptr;
     int *ex_fail = nullptr;
     const double *price_rho_ovr = nullptr;  // launch_price<1>: PriceArgs::rho_ovr for the next launch
+    // postsolve (ellp_post.inc): a workspace of its own, made at the first call; nothing the loop reads lives here
+    bool post_ready = false;      // the whole workspace is there
+    bool post_luw_ready = false;  // its LU work is (released by ellp_engine_destroy)
+    EllpLuWork post_luw{};
+    double *post_y = nullptr, *post_dy = nullptr, *post_rho = nullptr, *post_den = nullptr, *post_r = nullptr, *post_d = nullptr;
+    double *post_dpart = nullptr, *post_rpart = nullptr, *post_omega = nullptr;
+    ellp_kkt *post_kkt = nullptr;
+    int *post_fail = nullptr;
+    int64_t *post_srow = nullptr;  // the basic columns with one nonzero: its row (or -1) and value
+    double *post_sval = nullptr;
+    double *c_tail = nullptr;  // n_c > n: the costs without a column (primal phase 1 with free variables), for the postsolve
     uint64_t hy_uncertified = 0;
     // the LP is a "box problem" — every bound TwoSided or Fixed and b = 0: the shape of DualPhase1's LP (dual_problem.rs:89-131),
     // whose dual objective is minus the dual infeasibility of the original problem, i.e. <= 0 and = 0 at a feasible end
@@ -3994,6 +4005,10 @@ void ellp_engine_destroy(ellp_engine *e) {
         ellp_lu_rows_free(&e->luw);
         e->luw_ready = false;
     }
+    if (e->post_luw_ready) {
+        ellp_lu_rows_free(&e->post_luw);
+        e->post_luw_ready = e->post_ready = false;
+    }
 #ifdef ELLP_DBG_STAMPS
     if (e->h_st && hipMemcpy(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost) == hipSuccess) {
         long long t0 = e->h_st->dbg[0][0][0] ? e->h_st->dbg[0][0][0] : e->h_st->dbg[1][0][0];
@@ -4290,6 +4305,10 @@ static ellp_status create_upload(ellp_engine *e, const double *A, const double *
     HIPCHK(hipMemcpyAsync(e->lb, lb, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->ub, ub, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->kindv, bound_kind, (size_t)n_c, hipMemcpyHostToDevice, e->stream));
+    if (n_c > n) {  // the costs no stored column carries: kept for the postsolve's d and c . x
+        HIPCHK(dmalloc(e, &e->c_tail, (size_t)(n_c - n)));
+        HIPCHK(hipMemcpyAsync(e->c_tail, t.c_full + n, sizeof(double) * (size_t)(n_c - n), hipMemcpyDeviceToDevice, e->stream));
+    }
     hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)m), dim3(256), 0, e->stream, t.A_full, m, e->B_index, e->A_B, ld);
     hipLaunchKernelGGL(k_gather_vec, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, t.c_full, e->B_index, e->c_B, m);
     if (n_N > 0) {
@@ -5800,6 +5819,8 @@ ellp_status ellp_engine_rephase(ellp_engine *e, const double *c, const uint8_t *
     const int64_t cnt = e->m > e->nN ? e->m : e->nN;
     hipLaunchKernelGGL(k_rephase, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, e->stream, c_dev, e->kindv,
                        e->B_index, e->N_index, e->c_B, e->c_N, e->Nb, e->m, e->nN);
+    if (e->c_tail && (rc = hipMemcpyAsync(e->c_tail, c_dev + e->n, sizeof(double) * (size_t)(e->n_c - e->n), hipMemcpyDeviceToDevice, e->stream)) != hipSuccess)
+        return bail(rc);
     hipLaunchKernelGGL(k_primal_obj, dim3(1), dim3(1024), 0, e->stream, e->c_B, e->c_N, e->x, e->B_index, e->N_index, e->m,
                        e->nN, e->st);  // c.x with the new costs (the objective trace continues from it)
     if (e->trace_len > 0) (void)hipMemsetAsync(e->trace_it, 0, sizeof(unsigned long long) * (size_t)e->trace_len, e->stream);
@@ -5963,6 +5984,7 @@ ellp_status ellp_engine_dual_rephase(ellp_engine *e, const double *c, const doub
     const int64_t cnt = m > nN ? m : nN;
     hipLaunchKernelGGL(k_rephase, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, e->stream, c_dev, e->kindv, e->B_index,
                        e->N_index, e->c_B, e->c_N, e->Nb, m, nN);
+    if (e->c_tail) DCHK(hipMemcpyAsync(e->c_tail, c_dev + e->n, sizeof(double) * (size_t)(n_c - e->n), hipMemcpyDeviceToDevice, e->stream));
     // a new solve_with_initial: status and counters afresh (the maintenance kernels need a RUNNING engine)
     DCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
     DCHK(hipStreamSynchronize(e->stream));
@@ -6630,3 +6652,4 @@ ellp_status ellp_dual_solve_with_initial(int64_t m, int64_t n, int64_t n_c, cons
 
 #include "ellp_batch.inc"
 #include "ellp_dstart.inc"
+#include "ellp_post.inc"

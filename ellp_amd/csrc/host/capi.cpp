@@ -103,7 +103,7 @@ ellp::EngineOptions engine_options(const ellp_opts *opts) {
 }
 // *out from what `run` returns or throws
 template <class F>
-int fill_result(ellp_result *out, F &&run) {
+int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr) {
     std::memset(out, 0, sizeof(*out));
     try {
         ellp::SolverResult r = run();
@@ -117,6 +117,20 @@ int fill_result(ellp_result *out, F &&run) {
             out->nx = static_cast<int64_t>(x.size());
             out->x = new double[x.size() ? x.size() : 1];
             std::memcpy(out->x, x.data(), sizeof(double) * x.size());
+            if (ex && r.solution->post) {
+                const ellp::Postsolve &ps = *r.solution->post;
+                auto dup = [](const std::vector<double> &v) {
+                    double *q = new double[v.size() ? v.size() : 1];
+                    std::memcpy(q, v.data(), sizeof(double) * v.size());
+                    return q;
+                };
+                ex->has_postsolve = 1;
+                ex->n_duals = static_cast<int64_t>(ps.duals.size());
+                ex->duals = dup(ps.duals);
+                ex->n_reduced_costs = static_cast<int64_t>(ps.reduced_costs.size());
+                ex->reduced_costs = dup(ps.reduced_costs);
+                ex->kkt = ps.kkt;
+            }
             break;
         }
         case ellp::SolverResult::Infeasible: out->status = ELLP_INFEASIBLE; break;
@@ -150,6 +164,34 @@ int ellp_solve(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_
         return solver == ELLP_SOLVER_PRIMAL ? ellp::PrimalSimplexSolver(mi).with_engine(eo).solve(p->prob)
                                             : ellp::DualSimplexSolver(mi).with_engine(eo).solve(p->prob);
     });
+}
+
+int ellp_solve_ex(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, int postsolve, ellp_result_ex *out) {
+    if (!out) return ELLP_ERR_ARG;
+    std::memset(out, 0, sizeof(*out));
+    if (!p || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL)) {
+        out->result.status = ELLP_ERR_ARG;
+        put(out->result.err, sizeof(out->result.err), "ellp_solve_ex: no problem, or an unknown solver");
+        return ELLP_ERR_ARG;
+    }
+    const ellp::EngineOptions eo = engine_options(opts);
+    const std::optional<std::uint64_t> mi =
+        max_iter == ELLP_MAX_ITER_NONE ? std::nullopt : std::optional<std::uint64_t>(max_iter);
+    ellp_result base;
+    const int s = fill_result(&base, [&] {
+        return solver == ELLP_SOLVER_PRIMAL ? ellp::PrimalSimplexSolver(mi).with_engine(eo).with_postsolve(postsolve != 0).solve(p->prob)
+                                            : ellp::DualSimplexSolver(mi).with_engine(eo).with_postsolve(postsolve != 0).solve(p->prob);
+    }, out);
+    out->result = base;
+    return s;
+}
+
+void ellp_result_ex_free(ellp_result_ex *r) {
+    if (!r) return;
+    ellp_result_free(&r->result);
+    delete[] r->duals;
+    delete[] r->reduced_costs;
+    r->duals = r->reduced_costs = nullptr;
 }
 
 int ellp_solve_batch(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,

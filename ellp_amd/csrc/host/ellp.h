@@ -102,6 +102,9 @@ struct StandardForm {  // src/standard_form.rs:27-75
     std::vector<double> b;
     std::vector<Bound> bounds;
     Problem prob;
+    // extension: row k of A came from prob.constraints[row_origin[k]] (the rows the rank check kept, standard_form.rs:142-181);
+    // what maps the duals of a postsolve back to the user's constraints
+    std::vector<std::size_t> row_origin;
 
     std::size_t rows() const { return static_cast<std::size_t>(A.rows); }
     std::size_t cols() const { return static_cast<std::size_t>(A.cols); }
@@ -162,11 +165,29 @@ struct DualPhase2 {  // :69-73
 
 enum class SolutionStatus { Optimal, Infeasible, Unbounded, MaxIter };  // src/solver.rs:27-33
 
+// extension (with_postsolve(true)): the duals, reduced costs and KKT report of an Optimal solution (ellp_engine_postsolve /
+// ellp_postsolve, include/ellp_hip.h).  The problem is a minimisation, d = c - A^T y, and duals[i] is the derivative of the
+// optimal objective with respect to the right-hand side of constraint i of the user's Problem: <= 0 for a binding `<=` row,
+// >= 0 for a binding `>=` row, 0.0 for a row the rank check dropped as redundant.
+struct Postsolve {
+    std::vector<double> duals;          // one per constraint of the Problem, in order
+    std::vector<double> reduced_costs;  // one per variable of the Problem, in order
+    ellp_kkt kkt{};
+};
+
 struct Solution {  // src/solver.rs:35-54
     StandardForm std_form;
     Point point;
+    std::optional<Postsolve> post;  // set by a solver made with_postsolve(true)
     double obj() const { return std_form.obj(point.x); }
     std::vector<double> x() const { return std_form.extract_solution(point); }
+    const Postsolve &postsolve() const {
+        if (!post) throw EllPError("solve(..., postsolve=True) was not asked for");
+        return *post;
+    }
+    const std::vector<double> &duals() const { return postsolve().duals; }
+    const std::vector<double> &reduced_costs() const { return postsolve().reduced_costs; }
+    const ellp_kkt &kkt() const { return postsolve().kkt; }
 };
 
 struct SolverResult {  // src/solver.rs:6-12
@@ -198,6 +219,9 @@ public:
     explicit PrimalSimplexSolver(std::optional<std::uint64_t> max_iter)  // new(), :26-30
         : max_iter_(max_iter.value_or(std::numeric_limits<std::uint64_t>::max())) {}
     PrimalSimplexSolver &with_engine(const EngineOptions &o) { engine_ = o; return *this; }
+    // extension, off by default (off: not one extra device call): an Optimal Solution carries duals(), reduced_costs(), kkt()
+    // (from the resident engine that ran phase 2 where there is one and it takes the call, else from phase 2's arrays)
+    PrimalSimplexSolver &with_postsolve(bool on) { postsolve_ = on; return *this; }
 
     SolverResult solve(Problem prob) const;  // :32-93
     // :95-236 — the loop itself runs on the GPU (ellp_primal_solve_with_initial)
@@ -206,6 +230,7 @@ public:
 private:
     std::uint64_t max_iter_;
     EngineOptions engine_;
+    bool postsolve_ = false;
 };
 
 class DualSimplexSolver {  // src/solvers/dual/dual_simplex_solver.rs:16-108
@@ -214,6 +239,7 @@ public:
     explicit DualSimplexSolver(std::optional<std::uint64_t> max_iter)
         : max_iter_(max_iter.value_or(std::numeric_limits<std::uint64_t>::max())) {}
     DualSimplexSolver &with_engine(const EngineOptions &o) { engine_ = o; return *this; }
+    DualSimplexSolver &with_postsolve(bool on) { postsolve_ = on; return *this; }
 
     SolverResult solve(Problem prob) const;
     SolutionStatus solve_with_initial(const StandardForm &std_form, DualFeasiblePoint &pt,
@@ -222,6 +248,7 @@ public:
 private:
     std::uint64_t max_iter_;
     EngineOptions engine_;
+    bool postsolve_ = false;
 };
 
 // Many problems solved by one solver (solver: ELLP_SOLVER_PRIMAL / ELLP_SOLVER_DUAL) in lock step, the device loops of a

@@ -212,6 +212,7 @@ std::optional<StandardForm> StandardForm::from_problem(Problem prob) {
     sf.c = std::move(c);
     sf.bounds = std::move(bounds);
     sf.prob = std::move(prob);
+    for (Index src : indep_rows) sf.row_origin.push_back(static_cast<size_t>(src));
     return sf;
 }
 

@@ -4,6 +4,7 @@
 //                           does before its loop (m == 0 -> trivial solver); everything else is
 //                           one call through the C ABI into the HIP engine.  No CPU loop exists
 //                           here: if the engine cannot run, the error is raised.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <exception>
@@ -124,6 +125,71 @@ SolutionStatus run_resident(ellp_engine *e, std::uint64_t max_iter, Flat &f, Poi
     return out;
 }
 
+// with_postsolve(true): duals, reduced costs and the KKT report of an Optimal solution.  `e`: the resident engine that ran
+// phase 2 (examined where it stands, ellp_engine_postsolve); null, or an engine that call refuses (a sharded one): the
+// phase-2 arrays go up once more (ellp_postsolve).
+// Without rows it is answered here: y is empty and d = c.
+void attach_postsolve(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
+    const StandardForm &sf = sol.std_form;
+    const size_t m = sf.rows(), nc = sf.bounds.size(), nv = sf.prob.variables.size();
+    Postsolve ps;
+    std::vector<double> y(m, 0.0), d(nc, 0.0);
+    if (m == 0) {
+        d = sf.c;
+        ellp_kkt &k = ps.kkt;
+        k.worst_row = k.worst_bound_var = k.worst_dual_var = -1;
+        k.primal_obj = sf.obj(sol.point.x);
+        k.dual_obj = sf.dual_obj(y, d);
+        for (size_t v = 0; v < nc; ++v) {
+            const Bound &bd = sf.bounds[v];
+            const double xv = sol.point.x[v];
+            double viol = 0.0;
+            switch (bd.kind) {
+            case Bound::Free: break;
+            case Bound::Lower: viol = bd.lb - xv; break;
+            case Bound::Upper: viol = xv - bd.ub; break;
+            case Bound::TwoSided: viol = std::max(bd.lb - xv, xv - bd.ub); break;
+            case Bound::Fixed: viol = std::fabs(xv - bd.lb); break;
+            }
+            if (viol > k.bound_violation) {
+                k.bound_violation = viol;
+                k.worst_bound_var = static_cast<std::int64_t>(v);
+            }
+        }
+        for (const Nonbasic &nb : sol.point.N) {
+            const double dv = d[nb.index];
+            double inf;
+            if (sf.bounds[nb.index].kind == Bound::Fixed) inf = 0.0;
+            else if (nb.bound == NonbasicBound::Lower) inf = -dv;
+            else if (nb.bound == NonbasicBound::Upper) inf = dv;
+            else inf = std::fabs(dv);
+            if (inf > k.dual_infeasibility) {
+                k.dual_infeasibility = inf;
+                k.worst_dual_var = static_cast<std::int64_t>(nb.index);
+            }
+        }
+    } else {
+        char err[512] = {0};
+        ellp_status s = ELLP_ERR_ARG;
+        if (e) s = ellp_engine_postsolve(e, y.data(), d.data(), nullptr, &ps.kkt, err, sizeof(err));
+        if (s == ELLP_ERR_ARG) {
+            // no resident engine, or one the postsolve refuses (a sharded engine): the phase-2 arrays go up once more
+            Flat f = flatten(sf, sol.point);
+            const ellp_opts o = make_opts(0, eng);
+            s = ellp_postsolve(static_cast<std::int64_t>(m), static_cast<std::int64_t>(sf.cols()), static_cast<std::int64_t>(nc),
+                               sf.A.a.data(), sf.c.data(), sf.b.data(), f.kind.data(), f.lb.data(), f.ub.data(), sol.point.x.data(),
+                               f.B.data(), static_cast<std::int64_t>(f.B.size()), f.N.data(), f.Nb.data(),
+                               static_cast<std::int64_t>(f.N.size()), &o, y.data(), d.data(), nullptr, &ps.kkt, err, sizeof(err));
+        }
+        if (s != ELLP_OPTIMAL) to_status(s, err);  // throws: a singular basis is an EllPError, a refusal of the arrays a panic
+    }
+    if (sf.row_origin.size() != m) throw EllPPanic("assertion failed: std_form.row_origin.len() == std_form.rows()");
+    ps.duals.assign(sf.prob.constraints.size(), 0.0);
+    for (size_t k = 0; k < m; ++k) ps.duals[sf.row_origin[k]] = y[k];
+    ps.reduced_costs.assign(d.begin(), d.begin() + static_cast<std::ptrdiff_t>(nv));
+    sol.post = std::move(ps);
+}
+
 }  // namespace
 
 // primal_simplex_solver.rs:32-93.  The two solve_with_initial calls of the reference become two
@@ -184,7 +250,8 @@ SolverResult PrimalSimplexSolver::solve(Problem prob) const {
     switch (s2) {
     case SolutionStatus::Optimal:
         res.kind = SolverResult::Optimal;
-        res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point)};
+        res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point), std::nullopt};
+        if (postsolve_) attach_postsolve(*res.solution, resident ? eng.e : nullptr, engine_);  // the engine that ran phase 2, before it goes
         return res;
     case SolutionStatus::Infeasible: throw EllPPanic("primal phase 2 should never be infeasible");
     case SolutionStatus::Unbounded: res.kind = SolverResult::Unbounded; return res;
@@ -342,7 +409,8 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
     switch (s2) {
     case SolutionStatus::Optimal:
         res.kind = SolverResult::Optimal;
-        res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point.point)};
+        res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point.point), std::nullopt};
+        if (postsolve_) attach_postsolve(*res.solution, eng.e, engine_);  // eng.e: set only where it ran phase 2
         return res;
     case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; return res;
     case SolutionStatus::Unbounded: throw EllPPanic("dual phase 2 should never return unbounded");
@@ -598,7 +666,7 @@ void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which,
             switch (s) {
             case SolutionStatus::Optimal:
                 res.kind = SolverResult::Optimal;
-                res.solution = Solution{std::move(p2.std_form), std::move(p2.point)};
+                res.solution = Solution{std::move(p2.std_form), std::move(p2.point), std::nullopt};
                 break;
             case SolutionStatus::Infeasible: throw EllPPanic("primal phase 2 should never be infeasible");
             case SolutionStatus::Unbounded: res.kind = SolverResult::Unbounded; break;
@@ -783,7 +851,7 @@ void dual_batch(std::vector<Problem> &probs, std::uint64_t max_iter, const Engin
             switch (s2) {
             case SolutionStatus::Optimal:
                 res.kind = SolverResult::Optimal;
-                res.solution = Solution{std::move(it.p2->std_form), std::move(it.p2->point.point)};
+                res.solution = Solution{std::move(it.p2->std_form), std::move(it.p2->point.point), std::nullopt};
                 break;
             case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; break;
             case SolutionStatus::Unbounded: throw EllPPanic("dual phase 2 should never return unbounded");

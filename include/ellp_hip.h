@@ -562,6 +562,51 @@ double ellp_engine_inverse_residual(ellp_engine *e);
 void ellp_engine_destroy(ellp_engine *e);
 
 /*
+ * Postsolve: duals, reduced costs, the row residual and a KKT report for the basis and the point an engine stands on
+ * (DESIGN.md §3.9).  The problem is a minimisation; y = B^-T c_B, d = c - A^T y, r = b - A x, so y_i is the derivative
+ * of the optimal objective with respect to b_i.  y comes from a fresh LU of the current A_B (never from the loop's carried
+ * vectors or explicit inverse) and is refined until its componentwise backward error omega = max_i |rho_i| /
+ * (|c_B| + |A_B|^T |y|)_i, rho = c_B - A_B^T y, is at most 2u (u = 2^-53; at most 4 steps, given up when a step does not
+ * halve omega; a component a basic column with a single nonzero a e_k fixes on its own is set to y_k = fl(c / a)); d and r are formed from one read of every stored column in compensated arithmetic (error per entry at most
+ * u |exact| + gamma_K^2 * sum of the absolute values of the terms) with a reduction order fixed by the launch geometry:
+ * two calls on the same state return the same bits.  The engine's state is not touched (a workspace of its own, made at
+ * the first call): running on afterwards gives the bits it would have given without the call.
+ *   y: m doubles; d: n_c doubles by variable (d_v = c_v for v >= n); r: m doubles; any of y, d, r, kkt may be NULL (not
+ *   wanted); all four NULL: ELLP_ERR_ARG.
+ * Works for primal and dual engines of every mode, between any two slices and after the run has ended.  An iteration the
+ * two-launch pipeline has left open is completed first, as ellp_engine_read_point does; if that produces a status it is
+ * returned, with the outputs of the completed point.  A singular basis: ELLP_ERR_SINGULAR, outputs untouched.  Refused
+ * with ELLP_ERR_ARG before any HIP call: e NULL, a sharded or column-sharded engine, an engine whose status is an error.
+ */
+typedef struct ellp_kkt {
+    double primal_residual;     /* max_i |r_i|, r = b - A x */
+    double bound_violation;     /* max_v violation of x_v's bound by kind (Fixed: |x_v - lb_v|; Free: 0) */
+    double dual_infeasibility;  /* max over nonbasic positions j, v = N_index[j]: kind Fixed: 0; label Lower: max(-d_v, 0);
+                                   Upper: max(d_v, 0); Free: |d_v| */
+    double basic_reduced_cost;  /* max over basic i of |d_{B[i]}| */
+    double y_backward_error;    /* omega of the returned y */
+    double primal_obj;          /* c.x, compensated */
+    double dual_obj;            /* b.y + the bound terms of StandardForm::dual_obj (standard_form.rs:52-68), compensated */
+    int64_t worst_row, worst_bound_var, worst_dual_var; /* where the three maxima sit (the smallest such index; of NaNs the
+                                   first); -1: the maximum is 0 */
+    int32_t refinement_steps;
+    int32_t reserved;
+} ellp_kkt;
+
+ellp_status ellp_engine_postsolve(ellp_engine *e, double *y /* m */, double *d /* n_c */, double *r /* m */,
+                                  ellp_kkt *kkt, char *errbuf, size_t errbuf_len);
+
+/* The same for a point in host memory (the arguments of ellp_primal_solve_with_initial after it returned): a minimal
+ * upload into the engine's layout, the same kernels, the same bits.  ELLP_ERR_ARG before any HIP call: a NULL input,
+ * m < 1, m > 8192 (the limit of ellp_engine_create), n_B != m, n_B + n_N != n, an index, label or kind out of range, or none
+ * of y, d, r, kkt wanted. */
+ellp_status ellp_postsolve(int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
+                           const uint8_t *bound_kind, const double *lb, const double *ub, const double *x,
+                           const int64_t *B_index, int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N,
+                           const ellp_opts *opts, double *y, double *d, double *r, ellp_kkt *kkt,
+                           char *errbuf, size_t errbuf_len);
+
+/*
  * SURVEY.md §8 f3 — the rank check of the standard form on the device: column-pivoted Householder
  * QR of A^T (src/standard_form.rs:142 `A.transpose().col_piv_qr()`), reduced to what :143-181
  * consume.  A: m x nv column-major (ld = m) in HOST memory, not modified.  pivot_out[i] = the

@@ -55,6 +55,24 @@ typedef struct ellp_result {
 int ellp_solve(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, ellp_result *out);
 void ellp_result_free(ellp_result *r);
 
+/* ellp_solve with the opt-in postsolve (ellp_engine_postsolve / ellp_postsolve, ellp_hip.h): with postsolve != 0 an Optimal
+ * result also carries the duals (one per constraint of the problem, in order: the derivative of the optimal objective with
+ * respect to that constraint's right-hand side — the problem is a minimisation, so <= 0 for a binding `<=` row, >= 0 for a
+ * binding `>=` row — and 0.0 for a row the rank check dropped as redundant), the reduced costs d = c - A^T y of the
+ * problem's variables, and the KKT report of the final point in standard form.  postsolve == 0: exactly ellp_solve, not one
+ * extra device call, has_postsolve = 0.  ellp_solve, ellp_result and ellp_solve_batch are unchanged. */
+typedef struct ellp_result_ex {
+    ellp_result result;
+    int has_postsolve;
+    int64_t n_duals;           /* the problem's constraints */
+    double *duals;             /* owned by the result (ellp_result_ex_free) */
+    int64_t n_reduced_costs;   /* the problem's variables */
+    double *reduced_costs;
+    ellp_kkt kkt;
+} ellp_result_ex;
+int ellp_solve_ex(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, int postsolve, ellp_result_ex *out);
+void ellp_result_ex_free(ellp_result_ex *r);
+
 /* solve() of many problems by one solver in lock step: every phase's device loops of the problems the small kernel
  * takes (1 to 128 rows, with nonbasic columns), and of the 129 to 1,024-row problems the single call runs on the exact
  * mid-size kernel (pipeline 3, ELLP_MID_AUTO_MAX, the dual's bound flipping), run in one batched
