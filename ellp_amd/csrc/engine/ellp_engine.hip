@@ -3686,11 +3686,16 @@ void launch_ftran_eta(ellp_engine *e) {
         else hipLaunchKernelGGL((k_ftran_eta<0, true>), g, b, e->ftran_lds, e->stream, a);
         return;
     }
-    // rows in registers up to 2,048 doubles: wave 0 hands the entering column to the other waves through LDS (+8 ld bytes)
+    // rows in registers up to 2,048 doubles: a fifth wave folds and hands the entering column to the four that stream the
+    // rows through LDS (+8 ld bytes)
     const size_t hand_lds = ftran_col_offset(e->nblocks) + sizeof(double) * (size_t)e->ld;
-    if (nr <= 1) hipLaunchKernelGGL((k_ftran_eta<1>), g, b, hand_lds, e->stream, a);
-    else if (nr <= 2) hipLaunchKernelGGL((k_ftran_eta<2>), g, b, hand_lds, e->stream, a);
-    else if (nr <= 4) hipLaunchKernelGGL((k_ftran_eta<4>), g, b, hand_lds, e->stream, a);
+    const dim3 bh(FTRAN_HAND_THREADS);
+    static_assert(ftran_eta_threads(1, false) == FTRAN_HAND_THREADS && ftran_eta_threads(4, false) == FTRAN_HAND_THREADS &&
+                      ftran_eta_threads(8, false) == 256 && ftran_eta_threads(4, true) == 256,
+                  "320 threads exactly where hand_lds is used");
+    if (nr <= 1) hipLaunchKernelGGL((k_ftran_eta<1>), g, bh, hand_lds, e->stream, a);
+    else if (nr <= 2) hipLaunchKernelGGL((k_ftran_eta<2>), g, bh, hand_lds, e->stream, a);
+    else if (nr <= 4) hipLaunchKernelGGL((k_ftran_eta<4>), g, bh, hand_lds, e->stream, a);
     else if (nr <= 8) hipLaunchKernelGGL((k_ftran_eta<8>), g, b, e->ftran_lds, e->stream, a);
     else hipLaunchKernelGGL((k_ftran_eta<0>), g, b, e->ftran_lds, e->stream, a);
 }

@@ -1191,16 +1191,19 @@ __device__ __forceinline__ void ftran_eta_whole(const FtranEtaArgs &a) {
     }
 }
 
-// ------------------------------------------------------------------ F, unsharded, rows in registers: one wave decides, three stream
+// ------------------------------------------------------------------ F, unsharded, rows in registers: one wave decides, four stream
 // A wave has ONE outstanding-memory counter for loads and stores.  A wave that has row stores in flight and then consumes a
-// global load therefore waits for its own store burst to be acknowledged.  So the work of a row block is divided:
-//   wave 0      folds alone (same functions, same values), reads Nb[q], fetches the entering column and leaves column, q and
-//               the sign in LDS; only then it updates and stores its own quarter of the block's columns;
-//   waves 1..3  load their quarter of the rows and the pivot row, store the updated rows as soon as those are there, and take
-//               q and the column from LDS at the hand-off barrier.
+// global load therefore waits for its own store burst to be acknowledged.  So the work of a row block is divided among the
+// five waves of a 320-thread block:
+//   wave 0      owns no row and stores none: it folds alone (same functions, same values), reads Nb[q], fetches the entering
+//               column and leaves column, q and the sign in LDS; after the last barrier it writes the block's tail;
+//   waves 1..4  load a quarter of the rows and of the pivot row each, store the updated rows as soon as those are there, and
+//               take q and the column from LDS at the hand-off barrier.
 // Rule for every wave: between its first row store and the end of the kernel it consumes no global load.
-// The arithmetic is that of ftran_eta_whole: the same fmas on the same operands in the same order, every thread owns the same
-// columns, every row keeps its butterfly order and the four waves their order ((s0 + s1) + s2) + s3.
+// The arithmetic is that of ftran_eta_whole: the same fmas on the same operands in the same order, thread 64 + s owns the
+// columns thread s owns there, every row keeps its butterfly order and the four streaming waves their order
+// ((s0 + s1) + s2) + s3.
+constexpr int FTRAN_HAND_THREADS = 320;
 
 // the lanes of one wave run in lockstep: what one lane wrote to LDS is there for the others once the wave's LDS traffic retired
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
@@ -1237,9 +1240,11 @@ __device__ __forceinline__ void ftran_eta_handoff(const FtranEtaArgs &a) {
     __shared__ int s_dp[UPD_ROWS];
     DevState *st = a.st;
     STAMP(1, 0);  // -DELLP_DBG_STAMPS builds (tools/stamps.py): 0 entry, 5 block maxima staged, 6 candidates chosen, 1 q known,
-                  // 7 column published, 2 first stores of a streaming wave issued (thread 64), 3 dot products reduced, 4 end
+                  // 7 column published (all wave 0), 2 stores of the first streaming wave issued (thread 64), 3 dot products
+                  // reduced, 4 end (wave 0)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int sid = tid - 64;  // streaming waves: thread 64 + s owns double2 columns s + 256 u of the block's rows
     // the ways out that do not depend on q, decided ONCE per block (another block of this launch may raise nan_flag meanwhile)
     if (tid == 0) s_leave = st->status != ST_RUNNING ? 1 : (st->nan_flag ? 2 : 0);
     const int src_sel = st->f_src;
@@ -1263,52 +1268,12 @@ __device__ __forceinline__ void ftran_eta_handoff(const FtranEtaArgs &a) {
     const int64_t myrow = row0 + tid;
     const bool own = row_block && tid < R && myrow < m;
     int64_t bi0 = 0;
-    if (wave == 0) {
-        const double *pb[FB];
-#pragma unroll
-        for (int u = 0; u < FB; ++u) {
-            const int b = lane + 64 * u;
-            pb[u] = &a.xc.bk(b < a.nblocks ? b : 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);  // all addresses, then all loads: one round trip
-#pragma unroll
-        for (int u = 0; u < FB; ++u) v0[u] = *pb[u];
-        bi0 = a.B_index[own ? myrow : 0];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    double dv[UPD_ROWS];
-#pragma unroll
-    for (int k = 0; k < UPD_ROWS; ++k) dv[k] = (row_block && k < R && row0 + k < m) ? a.d[row0 + k] : 0.0;
-    // rows and pivot row as loaded (clamped addresses): what lies outside the block's rows or beyond the row's end is
-    // never stored, and reaches the dot products as zero
-    double2 wreg[UPD_ROWS][NR], pr[NR];
-#pragma unroll
-    for (int k = 0; k < UPD_ROWS; ++k) {
-        const int64_t i = row0 + k;
-        const bool ok = row_block && k < R && i < m;
-        const double2 *srow = reinterpret_cast<const double2 *>(src + (ok ? i : 0) * a.ld);
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            const int64_t t = tid + 256 * u;
-            wreg[k][u] = srow[t < half ? t : 0];
-        }
-    }
-    {  // the pivot row of the eta update is known from the state: it comes with the rows
-        const double2 *rho2 = reinterpret_cast<const double2 *>(src + (apply ? r : 0) * a.ld);
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            const int64_t t = tid + 256 * u;
-            pr[u] = rho2[t < half ? t : 0];
-        }
-    }
     double xi0 = 0.0, lbi0 = 0.0, ubi0 = 0.0;
     int k0 = 0;
-    lds_barrier();  // every wave of the block arrives: nothing above leaves the kernel
-    const int leave = s_leave;
-    if (leave) {  // block-uniform (LDS).  Nothing of this launch has been stored
-        if (leave == 2 && blockIdx.x == 0 && tid == 0) st->status = ELLP_ERR_NAN;  // fatal: nothing of this engine is used afterwards
-        return;
-    }
+    // streaming waves: the previous d, rows and pivot row as loaded (clamped addresses): what lies outside the block's rows
+    // or beyond the row's end is never stored, and reaches the dot products as zero
+    double dv[UPD_ROWS];
+    double2 wreg[UPD_ROWS][NR], pr[NR];
 
     // eta update of this thread's columns of the block's rows: store them, keep the new values for the dot products
     auto eta_store = [&]() {
@@ -1321,7 +1286,7 @@ __device__ __forceinline__ void ftran_eta_handoff(const FtranEtaArgs &a) {
             double2 *drow = reinterpret_cast<double2 *>(dst + i * a.ld);
 #pragma unroll
             for (int u = 0; u < NR; ++u) {
-                const int64_t t = tid + 256 * u;
+                const int64_t t = sid + 256 * u;
                 if (t >= half) continue;
                 double2 o;
                 if (i == r) {
@@ -1356,7 +1321,36 @@ __device__ __forceinline__ void ftran_eta_handoff(const FtranEtaArgs &a) {
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), as an instruction the compiler's own wait insertion accounts for
     };
 
+    // block 0 behind the hand-off, all five waves: the deferred half of the column move
+    auto block0_move = [&]() {
+        if (!st->mv_pending) return;
+        const int64_t mr = st->mv_r;
+        double2 *cb = reinterpret_cast<double2 *>(a.A_B + mr * a.ld);
+        const double2 *sv = reinterpret_cast<const double2 *>(a.aq_save);
+        for (int64_t t = tid; t < half; t += FTRAN_HAND_THREADS) cb[t] = sv[t];
+        if (tid == 0) a.c_B[mr] = st->cq_save;
+    };
+
+    // The two roles are two branches from entry to the kernel's end, each with the block's three barriers in it, so that
+    // neither carries the other's registers (the rows are not live across the fold, the fold's staging not across the row
+    // loads) and neither inherits a wait for what the other has in flight.
     if (wave == 0) {
+        const double *pb[FB];
+#pragma unroll
+        for (int u = 0; u < FB; ++u) {
+            const int b = lane + 64 * u;
+            pb[u] = &a.xc.bk(b < a.nblocks ? b : 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);  // all addresses, then all loads: one round trip
+#pragma unroll
+        for (int u = 0; u < FB; ++u) v0[u] = *pb[u];
+        bi0 = a.B_index[own ? myrow : 0];
+        lds_barrier();  // the entry barrier: every wave of the block arrives at its own, nothing above leaves the kernel
+        const int leave = s_leave;
+        if (leave) {  // block-uniform (LDS): the streaming waves leave at theirs.  Nothing of this launch has been stored
+            if (leave == 2 && blockIdx.x == 0 && tid == 0) st->status = ELLP_ERR_NAN;  // fatal: nothing of this engine is used afterwards
+            return;
+        }
         // the gathers of the lambda owners (threads 0..R-1 are this wave's): issued here, in no other wave's path
         xi0 = a.x[bi0];
         lbi0 = a.lb[bi0];
@@ -1475,19 +1469,83 @@ __device__ __forceinline__ void ftran_eta_handoff(const FtranEtaArgs &a) {
             s_atl = hc ? (nbq == ELLP_NB_LOWER ? 1 : 0) : 0;
         }
         STAMP(1, 7);
+    } else {
+        // ---- streaming waves: every global value they will ever need, requested at entry
+#pragma unroll
+        for (int k = 0; k < UPD_ROWS; ++k) dv[k] = (row_block && k < R && row0 + k < m) ? a.d[row0 + k] : 0.0;
+#pragma unroll
+        for (int k = 0; k < UPD_ROWS; ++k) {
+            const int64_t i = row0 + k;
+            const bool ok = row_block && k < R && i < m;
+            const double2 *srow = reinterpret_cast<const double2 *>(src + (ok ? i : 0) * a.ld);
+#pragma unroll
+            for (int u = 0; u < NR; ++u) {
+                const int64_t t = sid + 256 * u;
+                wreg[k][u] = srow[t < half ? t : 0];
+            }
+        }
+        {  // the pivot row of the eta update is known from the state: it comes with the rows
+            const double2 *rho2 = reinterpret_cast<const double2 *>(src + (apply ? r : 0) * a.ld);
+#pragma unroll
+            for (int u = 0; u < NR; ++u) {
+                const int64_t t = sid + 256 * u;
+                pr[u] = rho2[t < half ? t : 0];
+            }
+        }
+        lds_barrier();  // the entry barrier
+        if (s_leave) return;  // block-uniform (LDS): wave 0 leaves at its own
+        // the update needs rows, rho and the previous d only, nothing the fold produces: retire them once, store at once
+        rows_retired();
+        if (row_block) {
+            eta_store();
+            STAMP_AT(1, 2, 64);
+        }
+        lds_barrier();  // the hand-off (below): LDS traffic only, the stores stay in flight across it
+        if (!row_block) {
+            block0_move();
+            return;
+        }
+        if (s_q < 0) return;  // block-uniform: LDS
+        // ---- d_i = +-(row . a_q), a_q from LDS: wave sums, then the four streaming waves in a fixed order
+        double acc0[UPD_ROWS], acc1[UPD_ROWS];
+#pragma unroll
+        for (int k = 0; k < UPD_ROWS; ++k) acc0[k] = acc1[k] = 0.0;
+        double2 cq[NR];
+#pragma unroll
+        for (int u = 0; u < NR; ++u) {
+            const int64_t t = sid + 256 * u;
+            const double2 cv = s_col[t < half ? t : 0];
+            cq[u] = t < half ? cv : make_double2(0.0, 0.0);
+        }
+#pragma unroll
+        for (int k = 0; k < UPD_ROWS; ++k) {
+            const int64_t i = row0 + k;
+            if (!(k < R && i < m)) continue;
+#pragma unroll
+            for (int u = 0; u < NR; ++u) {
+                const bool in = sid + 256 * u < half;
+                acc0[k] = fma(in ? wreg[k][u].x : 0.0, cq[u].x, acc0[k]);
+                acc1[k] = fma(in ? wreg[k][u].y : 0.0, cq[u].y, acc1[k]);
+            }
+        }
+        double s[UPD_ROWS];
+#pragma unroll
+        for (int k = 0; k < UPD_ROWS; ++k) s[k] = acc0[k] + acc1[k];
+        // only the R rows the block has (1, 2 or 4), step by step together
+        if (R >= 3) wave_sum_rows<4>(s);
+        else if (R == 2) wave_sum_rows<2>(s);
+        else wave_sum_rows<1>(s);
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < UPD_ROWS; ++k) s_dot[wave - 1][k] = s[k];
+        }
+        lds_barrier();  // the last barrier (below); nothing follows it here: the rest is wave 0's own
+        return;
     }
-    // Passed by every wave on every path, so that no load counts as pending behind it: wave 0 comes here with all its loads
-    // retired by the column's wait, the streaming waves come here straight from the barrier above
-    rows_retired();
-    if (wave != 0 && row_block) {
-        // ---- streaming waves: the update needs rows, rho and the previous d only, nothing the fold produces
-        eta_store();
-        STAMP_AT(1, 2, 64);
-    }
-    // The hand-off.  Every wave that passed the barrier above reaches this one: the only way out in between is `leave`, read
-    // from LDS after that barrier and therefore the same in all four waves, and nothing above returns, whatever the
-    // fold found (q < 0 included: the optimal end still applies the eta update in all waves).  It waits for LDS traffic only,
-    // so the streaming waves' stores stay in flight across it.
+    // ---- wave 0 from here on; each barrier below is the one the streaming waves meet at the same point of their branch.
+    // The hand-off.  Every wave that passed its entry barrier reaches it: the only way out in between is `leave`, read from
+    // LDS after that barrier and therefore the same in all five waves, and nothing above returns, whatever the fold found
+    // (q < 0 included: the optimal end still applies the eta update in the streaming waves).
     lds_barrier();
     const long long q = s_q;
     const bool have_col = q >= 0;  // block-uniform: LDS
@@ -1495,13 +1553,7 @@ __device__ __forceinline__ void ftran_eta_handoff(const FtranEtaArgs &a) {
 
     if (!row_block) {
         // ---------------- block 0: the deferred half of the column move, then the commit of this iteration
-        if (st->mv_pending) {
-            const int64_t mr = st->mv_r;
-            double2 *cb = reinterpret_cast<double2 *>(a.A_B + mr * a.ld);
-            const double2 *sv = reinterpret_cast<const double2 *>(a.aq_save);
-            for (int64_t t = tid; t < half; t += 256) cb[t] = sv[t];
-            if (tid == 0) a.c_B[mr] = st->cq_save;
-        }
+        block0_move();
         if (tid == 0) {
             const int new_cur = apply ? (src_sel ^ 1) : src_sel;
             if (st->tiny_p) {  // raised by k_price2's bookkeeping (a tiny pivot): now it may stop the next launch
@@ -1530,45 +1582,9 @@ __device__ __forceinline__ void ftran_eta_handoff(const FtranEtaArgs &a) {
         }
         return;
     }
-    if (wave == 0) eta_store();  // fold -> column -> publish -> its own stores
-    if (!have_col) return;       // all four waves together
-
-    // ---- d_i = +-(row . a_q), a_q from LDS: wave sums, then the four waves in a fixed order
-    double acc0[UPD_ROWS], acc1[UPD_ROWS];
-#pragma unroll
-    for (int k = 0; k < UPD_ROWS; ++k) acc0[k] = acc1[k] = 0.0;
-    double2 cq[NR];
-#pragma unroll
-    for (int u = 0; u < NR; ++u) {
-        const int64_t t = tid + 256 * u;
-        const double2 cv = s_col[t < half ? t : 0];
-        cq[u] = t < half ? cv : make_double2(0.0, 0.0);
-    }
-#pragma unroll
-    for (int k = 0; k < UPD_ROWS; ++k) {
-        const int64_t i = row0 + k;
-        if (!(k < R && i < m)) continue;
-#pragma unroll
-        for (int u = 0; u < NR; ++u) {
-            const bool in = tid + 256 * u < half;
-            acc0[k] = fma(in ? wreg[k][u].x : 0.0, cq[u].x, acc0[k]);
-            acc1[k] = fma(in ? wreg[k][u].y : 0.0, cq[u].y, acc1[k]);
-        }
-    }
-    double s[UPD_ROWS];
-#pragma unroll
-    for (int k = 0; k < UPD_ROWS; ++k) s[k] = acc0[k] + acc1[k];
-    // only the R rows the block has (1, 2 or 4), step by step together
-    if (R >= 3) wave_sum_rows<4>(s);
-    else if (R == 2) wave_sum_rows<2>(s);
-    else wave_sum_rows<1>(s);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < UPD_ROWS; ++k) s_dot[wave][k] = s[k];
-    }
-    lds_barrier();  // reached by all four waves or by none: have_col and row_block are block-uniform
+    if (!have_col) return;  // all five waves together
+    lds_barrier();          // the dot products of the four streaming waves are in s_dot: reached by all five waves or by none
     STAMP(1, 3);
-    if (wave != 0) return;  // no barrier follows: the rest is wave 0's own
     const double sgn = at_lower ? -1.0 : 1.0;
     double li = INFINITY;
     int dp = 0;
@@ -1609,9 +1625,11 @@ __device__ __forceinline__ void ftran_eta_handoff(const FtranEtaArgs &a) {
 }
 
 constexpr bool ftran_eta_hands_off(int NR, bool SH) { return !SH && NR >= 1 && NR <= 4; }
+// threads per block: the deciding wave comes on top of the four that own the rows' columns
+constexpr int ftran_eta_threads(int NR, bool SH) { return ftran_eta_hands_off(NR, SH) ? FTRAN_HAND_THREADS : 256; }
 
 template <int NR, bool SH = false>
-__global__ __launch_bounds__(256) void k_ftran_eta(FtranEtaArgs a) {
+__global__ __launch_bounds__(ftran_eta_threads(NR, SH)) void k_ftran_eta(FtranEtaArgs a) {
     if constexpr (ftran_eta_hands_off(NR, SH)) ftran_eta_handoff<NR>(a);
     else ftran_eta_whole<NR, SH>(a);
 }
