@@ -89,6 +89,16 @@ class _ResultEx(C.Structure):
                 ("n_reduced_costs", C.c_int64), ("reduced_costs", C.POINTER(C.c_double)), ("kkt", _engine.Kkt)]
 
 
+class _ResultRng(C.Structure):
+    """ellp_result_rng (include/ellp_host.h)"""
+    _PD, _PI = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    _fields_ = [("ex", _ResultEx), ("has_ranging", C.c_int), ("n_cost", C.c_int64), ("cost_down", _PD), ("cost_up", _PD),
+                ("cost_blocking_down", _PI), ("cost_blocking_up", _PI), ("n_rhs", C.c_int64), ("rhs_down", _PD), ("rhs_up", _PD),
+                ("rhs_blocking_down", _PI), ("rhs_blocking_up", _PI), ("inverse_residual", C.c_double), ("n_B", C.c_int64),
+                ("n_N", C.c_int64), ("n_x_std", C.c_int64), ("B_index", _PI), ("N_index", _PI), ("row_origin", _PI),
+                ("N_bound", C.POINTER(C.c_uint8)), ("x_std", _PD)]
+
+
 class _FlatPhase(C.Structure):
     _fields_ = ([(k, C.c_int64) for k in ("m", "n", "n_c", "n_B", "n_N")] +
                 [(k, C.POINTER(C.c_double)) for k in ("A", "c", "b", "lb", "ub", "x", "y", "d")] +
@@ -135,6 +145,9 @@ def host_lib():
     L.ellp_solve_ex.restype = C.c_int
     L.ellp_solve_ex.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_int, C.POINTER(_ResultEx)]
     L.ellp_result_ex_free.argtypes = [C.POINTER(_ResultEx)]
+    L.ellp_solve_flags.restype = C.c_int
+    L.ellp_solve_flags.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_uint, C.POINTER(_ResultRng)]
+    L.ellp_result_rng_free.argtypes = [C.POINTER(_ResultRng)]
     L.ellp_solve_batch.restype = C.c_int
     L.ellp_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_void_p]
     L.ellp_debug_phase1.restype = C.c_int
@@ -238,8 +251,8 @@ class Solution:
     with respect to the right-hand side of constraint i: <= 0 for a binding `<=` row, >= 0 for a binding `>=` row, and 0.0
     for a row the rank check dropped as redundant."""
 
-    def __init__(self, obj, x, post=None):
-        self._obj, self._x, self._post = obj, x, post
+    def __init__(self, obj, x, post=None, rng=None):
+        self._obj, self._x, self._post, self._rng = obj, x, post, rng
 
     def obj(self):
         return self._obj
@@ -263,6 +276,31 @@ class Solution:
     def kkt(self):
         """the report of ellp_kkt (include/ellp_hip.h) as a dict, for the final point in standard form"""
         return self._postsolve()[2]
+
+    def _ranging(self):
+        if getattr(self, "_rng", None) is None:
+            raise EllPError("solve(..., ranging=True) was not asked for")
+        return self._rng
+
+    def cost_ranging(self):
+        """(down, up, blocking): for every variable of the Problem, in order, the change of its cost coefficient over which the
+        final basis stays optimal: down <= 0 <= up, -+inf unlimited.  blocking: (n, 2) indices of the standard form (below
+        the number of variables: that variable, above: a slack), the variable whose reduced cost changes sign first below /
+        above, -1 for an unlimited side.  Definitions: include/ellp_hip.h."""
+        r = self._ranging()
+        return r["cost_down"], r["cost_up"], np.stack([r["cost_blocking_down"], r["cost_blocking_up"]], axis=1)
+
+    def rhs_ranging(self):
+        """(down, up, blocking): for every constraint of the Problem, in order, the change of its right-hand side over which the
+        final basis stays feasible; a row the rank check dropped: (0.0, 0.0, -1).  blocking as for cost_ranging: the basic
+        variable that reaches a bound first."""
+        r = self._ranging()
+        return r["rhs_down"], r["rhs_up"], np.stack([r["rhs_blocking_down"], r["rhs_blocking_up"]], axis=1)
+
+    def basis(self):
+        """the final basis in standard form, as the ranging saw it: dict(B, N, Nb, x, row_origin, inverse_residual)"""
+        r = self._ranging()
+        return {k: r[k] for k in ("B", "N", "Nb", "x", "row_origin", "inverse_residual")}
 
 
 class SolverResult:
@@ -296,9 +334,33 @@ class _Solver:
     def default(cls):
         return cls()
 
-    def solve(self, prob, postsolve=False):
+    def solve(self, prob, postsolve=False, ranging=False):
         """postsolve=True: an Optimal result's Solution also has duals(), reduced_costs() and kkt() (one more pass on the
-        device after the solve; off by default, and off means not one extra device call)."""
+        device after the solve; off by default, and off means not one extra device call).  ranging=True (implies the
+        postsolve): also cost_ranging(), rhs_ranging() and basis()."""
+        if ranging:
+            rr = _ResultRng()
+            host_lib().ellp_solve_flags(prob._h, self._KIND, self.max_iter,
+                                        C.byref(self._opts) if self._opts is not None else None, 3, C.byref(rr))
+            try:
+                res = _to_result(rr.ex.result)
+                if res.kind == SolverResult.Optimal:
+                    rx = rr.ex
+                    arr = lambda p, n: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=p._type_)
+                    if rx.has_postsolve:
+                        res.solution._post = (arr(rx.duals, rx.n_duals), arr(rx.reduced_costs, rx.n_reduced_costs), rx.kkt.as_dict())
+                    if rr.has_ranging:
+                        res.solution._rng = dict(
+                            cost_down=arr(rr.cost_down, rr.n_cost), cost_up=arr(rr.cost_up, rr.n_cost),
+                            cost_blocking_down=arr(rr.cost_blocking_down, rr.n_cost), cost_blocking_up=arr(rr.cost_blocking_up, rr.n_cost),
+                            rhs_down=arr(rr.rhs_down, rr.n_rhs), rhs_up=arr(rr.rhs_up, rr.n_rhs),
+                            rhs_blocking_down=arr(rr.rhs_blocking_down, rr.n_rhs), rhs_blocking_up=arr(rr.rhs_blocking_up, rr.n_rhs),
+                            B=arr(rr.B_index, rr.n_B), N=arr(rr.N_index, rr.n_N), Nb=arr(rr.N_bound, rr.n_N),
+                            x=arr(rr.x_std, rr.n_x_std), row_origin=arr(rr.row_origin, rr.n_B),
+                            inverse_residual=float(rr.inverse_residual))
+                return res
+            finally:
+                host_lib().ellp_result_rng_free(C.byref(rr))
         if postsolve:
             rx = _ResultEx()
             host_lib().ellp_solve_ex(prob._h, self._KIND, self.max_iter,

@@ -64,6 +64,48 @@ class Kkt(C.Structure):
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
 
 
+class RangingInfo(C.Structure):
+    """ellp_ranging_info (include/ellp_hip.h)"""
+    _fields_ = [("inverse_residual", C.c_double), ("reserved", C.c_int64), ("kkt", Kkt)]
+
+
+class RangingOut(C.Structure):
+    """ellp_ranging_out (include/ellp_hip.h): caller-owned arrays, any of which may be NULL"""
+    _fields_ = [("cost_down", C.c_void_p), ("cost_up", C.c_void_p), ("cost_blocking_down", C.c_void_p),
+                ("cost_blocking_up", C.c_void_p), ("rhs_down", C.c_void_p), ("rhs_up", C.c_void_p),
+                ("rhs_blocking_down", C.c_void_p), ("rhs_blocking_up", C.c_void_p), ("d", C.c_void_p),
+                ("y", C.c_void_p), ("info", C.POINTER(RangingInfo))]
+
+
+class Ranging:
+    """The arrays of one ranging call.  cost_*: n_c entries by variable; rhs_*: m entries by row; all limits are changes with
+    down <= 0 <= up, -+inf unlimited, blocking -1 then; d, y: the reduced costs the ratios were formed from and the duals behind
+    them; kkt: the report of the underlying postsolve."""
+
+    def __init__(self, m, n_c):
+        self.cost_down, self.cost_up = np.zeros(n_c), np.zeros(n_c)
+        self.cost_blocking_down, self.cost_blocking_up = np.zeros(n_c, dtype=np.int64), np.zeros(n_c, dtype=np.int64)
+        self.rhs_down, self.rhs_up = np.zeros(m), np.zeros(m)
+        self.rhs_blocking_down, self.rhs_blocking_up = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+        self.d, self.y = np.zeros(n_c), np.zeros(m)
+        self._info = RangingInfo()
+        self.inverse_residual, self.kkt = float("nan"), None
+
+    ARRAYS = ("cost_down", "cost_up", "cost_blocking_down", "cost_blocking_up", "rhs_down", "rhs_up", "rhs_blocking_down",
+              "rhs_blocking_up", "d", "y")
+
+    def _out(self):
+        o = RangingOut()
+        for name in self.ARRAYS:
+            setattr(o, name, getattr(self, name).ctypes.data)
+        o.info = C.pointer(self._info)
+        return o
+
+    def _done(self):
+        self.inverse_residual, self.kkt = float(self._info.inverse_residual), self._info.kkt.as_dict()
+        return self
+
+
 class EllpHipError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"{STATUS_NAME.get(status, status)}: {msg}")
@@ -189,6 +231,12 @@ def lib():
     L.ellp_engine_shard_info.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.ellp_engine_postsolve.restype = C.c_int
     L.ellp_engine_postsolve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Kkt), C.c_char_p, C.c_size_t]
+    L.ellp_engine_ranging.restype = C.c_int
+    L.ellp_engine_ranging.argtypes = [C.c_void_p, C.POINTER(RangingOut), C.c_char_p, C.c_size_t]
+    L.ellp_ranging.restype = C.c_int
+    L.ellp_ranging.argtypes = _PROBLEM_ARGS + [C.POINTER(Opts), C.POINTER(RangingOut), C.c_char_p, C.c_size_t]
+    L.ellp_engine_tableau_rows.restype = C.c_int
+    L.ellp_engine_tableau_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
     L.ellp_postsolve.restype = C.c_int
     L.ellp_postsolve.argtypes = _PROBLEM_ARGS + [C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Kkt),
                                                  C.c_char_p, C.c_size_t]
@@ -363,6 +411,19 @@ def postsolve(fp, opts=None):
     if s != OPTIMAL:
         raise EllpHipError(s, err.value.decode())
     return y, d, r, k.as_dict()
+
+
+def ranging(fp, opts=None):
+    """ellp_ranging: the cost and right-hand-side ranges of the point a FlatProblem holds (the arrays a solve_with_initial call
+    left), by the kernels and with the bits of Engine.ranging.  Returns a Ranging; raises EllpHipError on any status but
+    OPTIMAL."""
+    o = opts or default_opts()
+    rg = Ranging(max(fp.m, 0), max(fp.n_c, 0))
+    err = C.create_string_buffer(512)
+    s = lib().ellp_ranging(*fp._args(), C.byref(o), C.byref(rg._out()), err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    return rg._done()
 
 
 class BatchItem(C.Structure):
@@ -568,6 +629,32 @@ class Engine:
         if s not in (OPTIMAL, UNBOUNDED, MAXITER):
             raise EllpHipError(s, err.value.decode())
         return y, d, r, k.as_dict()
+
+    def ranging(self):
+        """ellp_engine_ranging on the basis and point the engine stands on: a Ranging (include/ellp_hip.h has the definitions).
+        The engine's state is not touched.  closing_status as for postsolve."""
+        fp = self.fp
+        rg = Ranging(fp.m, fp.n_c)
+        err = C.create_string_buffer(512)
+        s = lib().ellp_engine_ranging(self._h, C.byref(rg._out()), err, 512)
+        self.closing_status = s
+        if s not in (OPTIMAL, UNBOUNDED, MAXITER):
+            raise EllpHipError(s, err.value.decode())
+        return rg._done()
+
+    def tableau_rows(self, positions, want_rho=True):
+        """ellp_engine_tableau_rows: (alpha, rho) — alpha[p] = row positions[p] of the tableau B^-1 A_N by nonbasic position,
+        rho[p] = that row of the computed B^-1 (None unless want_rho) — with the bits the ranging forms them with."""
+        fp = self.fp
+        pos = np.ascontiguousarray(positions, dtype=np.int64).reshape(-1)
+        alpha = np.zeros((pos.size, fp.nN))
+        rho = np.zeros((pos.size, fp.m)) if want_rho else None
+        err = C.create_string_buffer(512)
+        s = lib().ellp_engine_tableau_rows(self._h, _p(pos), pos.size, _p(alpha), _p(rho), err, 512)
+        self.closing_status = s
+        if s not in (OPTIMAL, UNBOUNDED, MAXITER):
+            raise EllpHipError(s, err.value.decode())
+        return alpha, rho
 
     def tap(self, what, count):
         out = np.zeros(int(count), dtype=np.float64)

@@ -3086,6 +3086,15 @@ struct ellp_engine : EnginePlan {  // the fields creation decides are the plan's
     int *post_fail = nullptr;
     int64_t *post_srow = nullptr;  // the basic columns with one nonzero: its row (or -1) and value
     double *post_sval = nullptr;
+    // sensitivity ranging (ellp_range.inc): its workspace, made at the first call on top of the postsolve's
+    bool rng_ready = false;
+    double *rng_W = nullptr;                          // B^-1, m rows of ld doubles
+    double *rng_pu = nullptr, *rng_pd = nullptr;      // the tableau pass's records, [column block][row]
+    int32_t *rng_ppu = nullptr, *rng_ppd = nullptr;
+    double *rng_cost = nullptr, *rng_rhs = nullptr;   // down, up: 2 n_c and 2 m doubles
+    int64_t *rng_cblk = nullptr, *rng_rblk = nullptr;  // blocking down, up
+    double *rng_res = nullptr;                        // the tile maxima of |I - A_B W|, then the maximum
+    int *rng_fail = nullptr;
     double *c_tail = nullptr;  // n_c > n: the costs without a column (primal phase 1 with free variables), for the postsolve
     uint64_t hy_uncertified = 0;
     // the LP is a "box problem" — every bound TwoSided or Fixed and b = 0: the shape of DualPhase1's LP (dual_problem.rs:89-131),
@@ -6658,3 +6667,4 @@ ellp_status ellp_dual_solve_with_initial(int64_t m, int64_t n, int64_t n_c, cons
 #include "ellp_batch.inc"
 #include "ellp_dstart.inc"
 #include "ellp_post.inc"
+#include "ellp_range.inc"

@@ -590,73 +590,27 @@ ellp_status post_compute(ellp_engine *e, double *y, double *d, double *r, ellp_k
     return ELLP_OPTIMAL;
 }
 
-}  // namespace
-
-extern "C" {
-
-ellp_status ellp_engine_postsolve(ellp_engine *e, double *y, double *d, double *r, ellp_kkt *kkt, char *errbuf, size_t errlen) {
-    if (errbuf && errlen) errbuf[0] = 0;
-    if (!e) {
-        set_err(errbuf, errlen, "postsolve: no engine");
-        return ELLP_ERR_ARG;
-    }
-    if (!y && !d && !r && !kkt) {
-        set_err(errbuf, errlen, "postsolve: none of y, d, r, kkt is wanted");
-        return ELLP_ERR_ARG;
-    }
-    if (e->world > 1 || e->colshard) {
-        set_err(errbuf, errlen, "postsolve: not on a sharded engine (every rank holds a part of the columns or of the pricing)");
-        return ELLP_ERR_ARG;
-    }
-    if (e->h_st && e->h_st->status < 0) {
-        set_err(errbuf, errlen, "postsolve: the engine ended with an error (status %d): there is no point to examine", (int)e->h_st->status);
-        return ELLP_ERR_ARG;
-    }
-    e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
-    HIPCHK(hipSetDevice(e->device));
-    // an iteration the two-launch pipeline has left open is completed first, exactly as ellp_engine_read_point does
-    const bool was_open = e->lag_open;
-    launch_flush(e);
-    ellp_status closing = ELLP_OPTIMAL;
-    if (was_open) {
-        HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        adopt_fin(e);
-        const int32_t stt = e->h_st->status;
-        if (stt != ST_RUNNING && stt != ST_NEED_MAINT && stt != ELLP_OPTIMAL) closing = status_message(*e->h_st, errbuf, errlen);
-    }
-    char err2[256];
-    const ellp_status s = post_compute(e, y, d, r, kkt, closing == ELLP_OPTIMAL ? errbuf : err2, closing == ELLP_OPTIMAL ? errlen : sizeof(err2));
-    if (s != ELLP_OPTIMAL) {
-        if (closing != ELLP_OPTIMAL) set_err(errbuf, errlen, "%s", err2);
-        return s;
-    }
-    return closing;
-}
-
-ellp_status ellp_postsolve(int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
-                           const uint8_t *bound_kind, const double *lb, const double *ub, const double *x, const int64_t *B_index,
-                           int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N, const ellp_opts *opts_in,
-                           double *y, double *d, double *r, ellp_kkt *kkt, char *errbuf, size_t errlen) {
-    if (errbuf && errlen) errbuf[0] = 0;
-    if (!y && !d && !r && !kkt) {
-        set_err(errbuf, errlen, "postsolve: none of y, d, r, kkt is wanted");
-        return ELLP_ERR_ARG;
-    }
+// The host-memory forms (ellp_postsolve, ellp_ranging): the checks answered before any HIP call, then a minimal engine that
+// holds the point in the engine's layout.  who: the caller's name in the messages.
+typedef std::unique_ptr<ellp_engine, void (*)(ellp_engine *)> PostOwn;
+ellp_status post_host_engine(const char *who, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
+                             const uint8_t *bound_kind, const double *lb, const double *ub, const double *x, const int64_t *B_index,
+                             int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N, const ellp_opts *opts_in,
+                             PostOwn &own, char *errbuf, size_t errlen) {
     if (m < 1) {
-        set_err(errbuf, errlen, "postsolve: m < 1 (without rows y is empty and d = c: answered on the host)");
+        set_err(errbuf, errlen, "%s: m < 1 (without rows y is empty and d = c: answered on the host)", who);
         return ELLP_ERR_ARG;
     }
     if (m > PLAN_MAX_M) {  // the engines' own limit (plan_engine); k_lu_solve keeps 16 m bytes in LDS
-        set_err(errbuf, errlen, "postsolve: m = %lld rows, at most %lld (the limit of ellp_engine_create)", (long long)m, (long long)PLAN_MAX_M);
+        set_err(errbuf, errlen, "%s: m = %lld rows, at most %lld (the limit of ellp_engine_create)", who, (long long)m, (long long)PLAN_MAX_M);
         return ELLP_ERR_ARG;
     }
     if (n < 0 || n_c < n || !A || !c || !b || !bound_kind || !lb || !ub || !x || !B_index || (n_N > 0 && (!N_index || !N_bound))) {
-        set_err(errbuf, errlen, "postsolve: null pointer or inconsistent sizes");
+        set_err(errbuf, errlen, "%s: null pointer or inconsistent sizes", who);
         return ELLP_ERR_ARG;
     }
     if (n_B != m || n_N < 0 || n_B + n_N != n) {
-        set_err(errbuf, errlen, "postsolve: invalid B/N, %lld + %lld elements for %lld rows and %lld columns", (long long)n_B,
+        set_err(errbuf, errlen, "%s: invalid B/N, %lld + %lld elements for %lld rows and %lld columns", who, (long long)n_B,
                 (long long)n_N, (long long)m, (long long)n);
         return ELLP_ERR_ARG;
     }
@@ -673,7 +627,7 @@ ellp_status ellp_postsolve(int64_t m, int64_t n, int64_t n_c, const double *A, c
     }
     // a minimal upload into the engine's layout: the stored columns, the costs by position, the point, the bounds and b —
     // no inverse, no pricing buffers, no loop; then the steps of ellp_engine_postsolve on the same kernels
-    std::unique_ptr<ellp_engine, void (*)(ellp_engine *)> own(new ellp_engine(), ellp_engine_destroy);
+    own.reset(new ellp_engine());
     ellp_engine *e = own.get();
     e->opts = opts;
     e->opts.profile = 0;
@@ -701,9 +655,75 @@ ellp_status ellp_postsolve(int64_t m, int64_t n, int64_t n_c, const double *A, c
     HIPCHK(dmalloc(e, &e->Nb, (size_t)nNa));
     HIPCHK(dmalloc(e, &e->st, 1));
     HIPCHK(hipMemsetAsync(e->b_dev, 0, sizeof(double) * (size_t)ld, e->stream));
-    s = create_upload(e, A, c, b, bound_kind, lb, ub, x, B_index, N_index, N_bound, nullptr, nullptr, n, errbuf, errlen);
+    return create_upload(e, A, c, b, bound_kind, lb, ub, x, B_index, N_index, N_bound, nullptr, nullptr, n, errbuf, errlen);
+}
+
+// An iteration the two-launch pipeline has left open is completed first, exactly as ellp_engine_read_point does; *closing: the
+// status that produced (ELLP_OPTIMAL: none)
+ellp_status post_complete_open(ellp_engine *e, ellp_status *closing, char *errbuf, size_t errlen) {
+    e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
+    HIPCHK(hipSetDevice(e->device));
+    const bool was_open = e->lag_open;
+    launch_flush(e);
+    *closing = ELLP_OPTIMAL;
+    if (was_open) {
+        HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        adopt_fin(e);
+        const int32_t stt = e->h_st->status;
+        if (stt != ST_RUNNING && stt != ST_NEED_MAINT && stt != ELLP_OPTIMAL) *closing = status_message(*e->h_st, errbuf, errlen);
+    }
+    return ELLP_OPTIMAL;
+}
+
+}  // namespace
+
+extern "C" {
+
+ellp_status ellp_engine_postsolve(ellp_engine *e, double *y, double *d, double *r, ellp_kkt *kkt, char *errbuf, size_t errlen) {
+    if (errbuf && errlen) errbuf[0] = 0;
+    if (!e) {
+        set_err(errbuf, errlen, "postsolve: no engine");
+        return ELLP_ERR_ARG;
+    }
+    if (!y && !d && !r && !kkt) {
+        set_err(errbuf, errlen, "postsolve: none of y, d, r, kkt is wanted");
+        return ELLP_ERR_ARG;
+    }
+    if (e->world > 1 || e->colshard) {
+        set_err(errbuf, errlen, "postsolve: not on a sharded engine (every rank holds a part of the columns or of the pricing)");
+        return ELLP_ERR_ARG;
+    }
+    if (e->h_st && e->h_st->status < 0) {
+        set_err(errbuf, errlen, "postsolve: the engine ended with an error (status %d): there is no point to examine", (int)e->h_st->status);
+        return ELLP_ERR_ARG;
+    }
+    ellp_status closing = ELLP_OPTIMAL;
+    const ellp_status cs = post_complete_open(e, &closing, errbuf, errlen);
+    if (cs != ELLP_OPTIMAL) return cs;
+    char err2[256];
+    const ellp_status s = post_compute(e, y, d, r, kkt, closing == ELLP_OPTIMAL ? errbuf : err2, closing == ELLP_OPTIMAL ? errlen : sizeof(err2));
+    if (s != ELLP_OPTIMAL) {
+        if (closing != ELLP_OPTIMAL) set_err(errbuf, errlen, "%s", err2);
+        return s;
+    }
+    return closing;
+}
+
+ellp_status ellp_postsolve(int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
+                           const uint8_t *bound_kind, const double *lb, const double *ub, const double *x, const int64_t *B_index,
+                           int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N, const ellp_opts *opts_in,
+                           double *y, double *d, double *r, ellp_kkt *kkt, char *errbuf, size_t errlen) {
+    if (errbuf && errlen) errbuf[0] = 0;
+    if (!y && !d && !r && !kkt) {
+        set_err(errbuf, errlen, "postsolve: none of y, d, r, kkt is wanted");
+        return ELLP_ERR_ARG;
+    }
+    PostOwn own(nullptr, ellp_engine_destroy);
+    const ellp_status s = post_host_engine("postsolve", m, n, n_c, A, c, b, bound_kind, lb, ub, x, B_index, n_B, N_index, N_bound, n_N, opts_in,
+                                           own, errbuf, errlen);
     if (s != ELLP_OPTIMAL) return s;
-    return post_compute(e, y, d, r, kkt, errbuf, errlen);
+    return post_compute(own.get(), y, d, r, kkt, errbuf, errlen);
 }
 
 }  // extern "C"

@@ -3,6 +3,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include <type_traits>
+
 #include "ellp.h"
 #include "ellp_host.h"
 
@@ -103,7 +105,7 @@ ellp::EngineOptions engine_options(const ellp_opts *opts) {
 }
 // *out from what `run` returns or throws
 template <class F>
-int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr) {
+int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr, ellp_result_rng *rng = nullptr) {
     std::memset(out, 0, sizeof(*out));
     try {
         ellp::SolverResult r = run();
@@ -130,6 +132,35 @@ int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr) {
                 ex->n_reduced_costs = static_cast<int64_t>(ps.reduced_costs.size());
                 ex->reduced_costs = dup(ps.reduced_costs);
                 ex->kkt = ps.kkt;
+            }
+            if (rng && r.solution->rng) {
+                const ellp::Ranging &rg = *r.solution->rng;
+                auto dup = [](const auto &v) {
+                    using T = typename std::decay_t<decltype(v)>::value_type;
+                    T *q = new T[v.size() ? v.size() : 1];
+                    std::memcpy(q, v.data(), sizeof(T) * v.size());
+                    return q;
+                };
+                rng->has_ranging = 1;
+                rng->n_cost = static_cast<int64_t>(rg.cost_down.size());
+                rng->cost_down = dup(rg.cost_down); rng->cost_up = dup(rg.cost_up);
+                rng->cost_blocking_down = dup(rg.cost_blocking_down); rng->cost_blocking_up = dup(rg.cost_blocking_up);
+                rng->n_rhs = static_cast<int64_t>(rg.rhs_down.size());
+                rng->rhs_down = dup(rg.rhs_down); rng->rhs_up = dup(rg.rhs_up);
+                rng->rhs_blocking_down = dup(rg.rhs_blocking_down); rng->rhs_blocking_up = dup(rg.rhs_blocking_up);
+                rng->inverse_residual = rg.inverse_residual;
+                const ellp::Point &pt = r.solution->point;
+                std::vector<int64_t> B, N, ro;
+                std::vector<uint8_t> Nb;
+                for (const auto &bv : pt.B) B.push_back(static_cast<int64_t>(bv.index));
+                for (const auto &nb : pt.N) {
+                    N.push_back(static_cast<int64_t>(nb.index));
+                    Nb.push_back(static_cast<uint8_t>(nb.bound));
+                }
+                for (size_t o : r.solution->std_form.row_origin) ro.push_back(static_cast<int64_t>(o));
+                rng->n_B = static_cast<int64_t>(B.size()); rng->n_N = static_cast<int64_t>(N.size());
+                rng->n_x_std = static_cast<int64_t>(pt.x.size());
+                rng->B_index = dup(B); rng->N_index = dup(N); rng->N_bound = dup(Nb); rng->row_origin = dup(ro); rng->x_std = dup(pt.x);
             }
             break;
         }
@@ -184,6 +215,38 @@ int ellp_solve_ex(const ellp_problem *p, int solver, uint64_t max_iter, const el
     }, out);
     out->result = base;
     return s;
+}
+
+int ellp_solve_flags(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, unsigned flags, ellp_result_rng *out) {
+    if (!out) return ELLP_ERR_ARG;
+    std::memset(out, 0, sizeof(*out));
+    if (!p || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL) || (flags & ~(ELLP_SOLVE_POSTSOLVE | ELLP_SOLVE_RANGING))) {
+        out->ex.result.status = ELLP_ERR_ARG;
+        put(out->ex.result.err, sizeof(out->ex.result.err), "ellp_solve_flags: no problem, an unknown solver or an unknown flag");
+        return ELLP_ERR_ARG;
+    }
+    const ellp::EngineOptions eo = engine_options(opts);
+    const std::optional<std::uint64_t> mi =
+        max_iter == ELLP_MAX_ITER_NONE ? std::nullopt : std::optional<std::uint64_t>(max_iter);
+    const bool post = (flags & ELLP_SOLVE_POSTSOLVE) != 0, rng = (flags & ELLP_SOLVE_RANGING) != 0;
+    ellp_result base;
+    const int s = fill_result(&base, [&] {
+        return solver == ELLP_SOLVER_PRIMAL ? ellp::PrimalSimplexSolver(mi).with_engine(eo).with_postsolve(post).with_ranging(rng).solve(p->prob)
+                                            : ellp::DualSimplexSolver(mi).with_engine(eo).with_postsolve(post).with_ranging(rng).solve(p->prob);
+    }, &out->ex, out);
+    out->ex.result = base;
+    return s;
+}
+
+void ellp_result_rng_free(ellp_result_rng *r) {
+    if (!r) return;
+    ellp_result_ex_free(&r->ex);
+    delete[] r->cost_down; delete[] r->cost_up; delete[] r->cost_blocking_down; delete[] r->cost_blocking_up;
+    delete[] r->rhs_down; delete[] r->rhs_up; delete[] r->rhs_blocking_down; delete[] r->rhs_blocking_up;
+    delete[] r->B_index; delete[] r->N_index; delete[] r->row_origin; delete[] r->N_bound; delete[] r->x_std;
+    r->cost_down = r->cost_up = r->rhs_down = r->rhs_up = r->x_std = nullptr;
+    r->cost_blocking_down = r->cost_blocking_up = r->rhs_blocking_down = r->rhs_blocking_up = r->B_index = r->N_index = r->row_origin = nullptr;
+    r->N_bound = nullptr;
 }
 
 void ellp_result_ex_free(ellp_result_ex *r) {

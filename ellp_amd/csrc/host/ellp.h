@@ -175,10 +175,27 @@ struct Postsolve {
     ellp_kkt kkt{};
 };
 
+// extension (with_ranging(true)): over what change of one cost coefficient the final basis stays optimal and over what change
+// of one right-hand side it stays feasible (ellp_engine_ranging / ellp_ranging, include/ellp_hip.h has the definitions).  All
+// limits are changes, down <= 0 <= up, -+infinity: unlimited.  A blocking entry is an index of the standard form (below the
+// number of the Problem's variables: that variable; above: a slack or phase-1 column) or -1 for an unlimited side.
+struct Ranging {
+    std::vector<double> cost_down, cost_up;                          // one per variable of the Problem, in order
+    std::vector<std::int64_t> cost_blocking_down, cost_blocking_up;
+    std::vector<double> rhs_down, rhs_up;                            // one per constraint of the Problem, in order; a row the rank
+    std::vector<std::int64_t> rhs_blocking_down, rhs_blocking_up;    // check dropped: (0.0, 0.0, -1)
+    double inverse_residual = 0.0;                                   // max |I - A_B W| of the computed inverse (0 without rows)
+};
+
 struct Solution {  // src/solver.rs:35-54
     StandardForm std_form;
     Point point;
     std::optional<Postsolve> post;  // set by a solver made with_postsolve(true)
+    std::optional<Ranging> rng;     // set by a solver made with_ranging(true)
+    const Ranging &ranging() const {
+        if (!rng) throw EllPError("solve(..., ranging=True) was not asked for");
+        return *rng;
+    }
     double obj() const { return std_form.obj(point.x); }
     std::vector<double> x() const { return std_form.extract_solution(point); }
     const Postsolve &postsolve() const {
@@ -222,6 +239,9 @@ public:
     // extension, off by default (off: not one extra device call): an Optimal Solution carries duals(), reduced_costs(), kkt()
     // (from the resident engine that ran phase 2 where there is one and it takes the call, else from phase 2's arrays)
     PrimalSimplexSolver &with_postsolve(bool on) { postsolve_ = on; return *this; }
+    // extension, off by default (off: not one extra device call): an Optimal Solution carries ranging(); implies the postsolve, which
+    // comes out of the same device call (one LU, not two)
+    PrimalSimplexSolver &with_ranging(bool on) { ranging_ = on; if (on) postsolve_ = true; return *this; }
 
     SolverResult solve(Problem prob) const;  // :32-93
     // :95-236 — the loop itself runs on the GPU (ellp_primal_solve_with_initial)
@@ -231,6 +251,7 @@ private:
     std::uint64_t max_iter_;
     EngineOptions engine_;
     bool postsolve_ = false;
+    bool ranging_ = false;
 };
 
 class DualSimplexSolver {  // src/solvers/dual/dual_simplex_solver.rs:16-108
@@ -240,6 +261,7 @@ public:
         : max_iter_(max_iter.value_or(std::numeric_limits<std::uint64_t>::max())) {}
     DualSimplexSolver &with_engine(const EngineOptions &o) { engine_ = o; return *this; }
     DualSimplexSolver &with_postsolve(bool on) { postsolve_ = on; return *this; }
+    DualSimplexSolver &with_ranging(bool on) { ranging_ = on; if (on) postsolve_ = true; return *this; }
 
     SolverResult solve(Problem prob) const;
     SolutionStatus solve_with_initial(const StandardForm &std_form, DualFeasiblePoint &pt,
@@ -249,6 +271,7 @@ private:
     std::uint64_t max_iter_;
     EngineOptions engine_;
     bool postsolve_ = false;
+    bool ranging_ = false;
 };
 
 // Many problems solved by one solver (solver: ELLP_SOLVER_PRIMAL / ELLP_SOLVER_DUAL) in lock step, the device loops of a

@@ -8,6 +8,8 @@
 #include <cmath>
 #include <cstring>
 #include <exception>
+#include <limits>
+#include <type_traits>
 
 #include "ellp.h"
 
@@ -190,6 +192,73 @@ void attach_postsolve(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
     sol.post = std::move(ps);
 }
 
+// with_ranging(true): the cost and right-hand-side ranges of an Optimal solution, from the engine that ran phase 2 where there
+// is one and it takes the call (ellp_engine_ranging), else from phase 2's arrays (ellp_ranging).  The ranging runs the
+// postsolve itself, so its y, d and report are taken from the same call and become the Solution's postsolve (no second LU).
+// Without rows both are answered here: every variable is nonbasic with d = c, and there is no right-hand side.
+void attach_ranging(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
+    const StandardForm &sf = sol.std_form;
+    const size_t m = sf.rows(), nc = sf.bounds.size(), nv = sf.prob.variables.size();
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> cd(nc, -inf), cu(nc, inf), rd(m, 0.0), ru(m, 0.0);
+    std::vector<std::int64_t> cbd(nc, -1), cbu(nc, -1), rbd(m, -1), rbu(m, -1);
+    Ranging rg;
+    if (m == 0) {
+        attach_postsolve(sol, e, eng);
+        for (const Nonbasic &nb : sol.point.N) {
+            const size_t v = nb.index;
+            const double dv = sf.c[v];
+            if (sf.bounds[v].kind == Bound::Fixed) continue;
+            if (nb.bound == NonbasicBound::Lower) cd[v] = 0.0 - std::max(dv, 0.0);
+            else if (nb.bound == NonbasicBound::Upper) cu[v] = 0.0 - std::min(dv, 0.0);
+            else {
+                cu[v] = std::max(-dv, 0.0) + 0.0;
+                cd[v] = std::min(-dv, 0.0) + 0.0;
+            }
+            if (cd[v] != -inf) cbd[v] = static_cast<std::int64_t>(v);
+            if (cu[v] != inf) cbu[v] = static_cast<std::int64_t>(v);
+        }
+    } else {
+        char err[512] = {0};
+        ellp_ranging_info info{};
+        ellp_ranging_out out{};
+        out.cost_down = cd.data(); out.cost_up = cu.data(); out.cost_blocking_down = cbd.data(); out.cost_blocking_up = cbu.data();
+        out.rhs_down = rd.data(); out.rhs_up = ru.data(); out.rhs_blocking_down = rbd.data(); out.rhs_blocking_up = rbu.data();
+        out.info = &info;
+        std::vector<double> y(m, 0.0), d(nc, 0.0);
+        out.y = y.data(); out.d = d.data();
+        ellp_status s = ELLP_ERR_ARG;
+        if (e) s = ellp_engine_ranging(e, &out, err, sizeof(err));
+        if (s == ELLP_ERR_ARG) {
+            Flat f = flatten(sf, sol.point);
+            const ellp_opts o = make_opts(0, eng);
+            s = ellp_ranging(static_cast<std::int64_t>(m), static_cast<std::int64_t>(sf.cols()), static_cast<std::int64_t>(nc), sf.A.a.data(),
+                             sf.c.data(), sf.b.data(), f.kind.data(), f.lb.data(), f.ub.data(), sol.point.x.data(), f.B.data(),
+                             static_cast<std::int64_t>(f.B.size()), f.N.data(), f.Nb.data(), static_cast<std::int64_t>(f.N.size()), &o, &out,
+                             err, sizeof(err));
+        }
+        if (s != ELLP_OPTIMAL) to_status(s, err);  // throws, as attach_postsolve
+        rg.inverse_residual = info.inverse_residual;
+        if (sf.row_origin.size() != m) throw EllPPanic("assertion failed: std_form.row_origin.len() == std_form.rows()");
+        Postsolve ps;
+        ps.kkt = info.kkt;
+        ps.duals.assign(sf.prob.constraints.size(), 0.0);
+        for (size_t k = 0; k < m; ++k) ps.duals[sf.row_origin[k]] = y[k];
+        ps.reduced_costs.assign(d.begin(), d.begin() + static_cast<std::ptrdiff_t>(nv));
+        sol.post = std::move(ps);
+    }
+    if (sf.row_origin.size() != m) throw EllPPanic("assertion failed: std_form.row_origin.len() == std_form.rows()");
+    const auto head = [nv](const auto &v) { return std::decay_t<decltype(v)>(v.begin(), v.begin() + static_cast<std::ptrdiff_t>(nv)); };
+    rg.cost_down = head(cd); rg.cost_up = head(cu); rg.cost_blocking_down = head(cbd); rg.cost_blocking_up = head(cbu);
+    const size_t ncon = sf.prob.constraints.size();
+    rg.rhs_down.assign(ncon, 0.0); rg.rhs_up.assign(ncon, 0.0); rg.rhs_blocking_down.assign(ncon, -1); rg.rhs_blocking_up.assign(ncon, -1);
+    for (size_t k = 0; k < m; ++k) {
+        const size_t o = sf.row_origin[k];
+        rg.rhs_down[o] = rd[k]; rg.rhs_up[o] = ru[k]; rg.rhs_blocking_down[o] = rbd[k]; rg.rhs_blocking_up[o] = rbu[k];
+    }
+    sol.rng = std::move(rg);
+}
+
 }  // namespace
 
 // primal_simplex_solver.rs:32-93.  The two solve_with_initial calls of the reference become two
@@ -250,8 +319,9 @@ SolverResult PrimalSimplexSolver::solve(Problem prob) const {
     switch (s2) {
     case SolutionStatus::Optimal:
         res.kind = SolverResult::Optimal;
-        res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point), std::nullopt};
-        if (postsolve_) attach_postsolve(*res.solution, resident ? eng.e : nullptr, engine_);  // the engine that ran phase 2, before it goes
+        res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point), std::nullopt, std::nullopt};
+        if (ranging_) attach_ranging(*res.solution, resident ? eng.e : nullptr, engine_);  // the engine that ran phase 2, before it goes
+        else if (postsolve_) attach_postsolve(*res.solution, resident ? eng.e : nullptr, engine_);
         return res;
     case SolutionStatus::Infeasible: throw EllPPanic("primal phase 2 should never be infeasible");
     case SolutionStatus::Unbounded: res.kind = SolverResult::Unbounded; return res;
@@ -409,8 +479,9 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
     switch (s2) {
     case SolutionStatus::Optimal:
         res.kind = SolverResult::Optimal;
-        res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point.point), std::nullopt};
-        if (postsolve_) attach_postsolve(*res.solution, eng.e, engine_);  // eng.e: set only where it ran phase 2
+        res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point.point), std::nullopt, std::nullopt};
+        if (ranging_) attach_ranging(*res.solution, eng.e, engine_);  // eng.e: set only where it ran phase 2
+        else if (postsolve_) attach_postsolve(*res.solution, eng.e, engine_);
         return res;
     case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; return res;
     case SolutionStatus::Unbounded: throw EllPPanic("dual phase 2 should never return unbounded");
@@ -666,7 +737,7 @@ void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which,
             switch (s) {
             case SolutionStatus::Optimal:
                 res.kind = SolverResult::Optimal;
-                res.solution = Solution{std::move(p2.std_form), std::move(p2.point), std::nullopt};
+                res.solution = Solution{std::move(p2.std_form), std::move(p2.point), std::nullopt, std::nullopt};
                 break;
             case SolutionStatus::Infeasible: throw EllPPanic("primal phase 2 should never be infeasible");
             case SolutionStatus::Unbounded: res.kind = SolverResult::Unbounded; break;
@@ -851,7 +922,7 @@ void dual_batch(std::vector<Problem> &probs, std::uint64_t max_iter, const Engin
             switch (s2) {
             case SolutionStatus::Optimal:
                 res.kind = SolverResult::Optimal;
-                res.solution = Solution{std::move(it.p2->std_form), std::move(it.p2->point.point), std::nullopt};
+                res.solution = Solution{std::move(it.p2->std_form), std::move(it.p2->point.point), std::nullopt, std::nullopt};
                 break;
             case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; break;
             case SolutionStatus::Unbounded: throw EllPPanic("dual phase 2 should never return unbounded");

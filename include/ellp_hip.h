@@ -607,6 +607,73 @@ ellp_status ellp_postsolve(int64_t m, int64_t n, int64_t n_c, const double *A, c
                            char *errbuf, size_t errbuf_len);
 
 /*
+ * Sensitivity ranging: over what change of one cost coefficient the basis stays optimal, and over what change of one
+ * right-hand side it stays feasible.  Standard form, minimisation, at the basis and point the engine stands
+ * on.  The call runs the postsolve above (with the completion of an open iteration, the fresh LU and the refined y) and uses
+ * its factors and its d; then W = B^-1 row by row from that LU (A_B^T rho_i = e_i, many right-hand sides per workgroup, the
+ * arithmetic of the postsolve's own transposed solve), every row of the tableau alpha = W A_N on the matrix cores with the
+ * ratio test in the epilogue (the tableau is never stored), and one pass over W for the right-hand sides.
+ *
+ * All results are CHANGES delta with down <= 0 <= up; -+Inf: unlimited, the blocking variable is then -1.  eps is the
+ * engine's eps option.  Zeros are +0.0.
+ *   cost of a nonbasic v (label Lower / Upper / Free; kind Fixed: unlimited both ways):
+ *       Lower (up, down) = (+Inf, -max(d_v, 0));  Upper (-min(d_v, 0), -Inf);  Free (max(-d_v, 0), min(-d_v, 0)); blocking v.
+ *   cost of the basic variable at position i: over the non-Fixed nonbasic positions j, v = N_index[j], alpha = alpha_ij:
+ *       Lower: alpha > eps limits up, alpha < -eps limits down, by fl(max(d_v, 0) / alpha);
+ *       Upper: alpha < -eps limits up, alpha > eps limits down, by fl(min(d_v, 0) / alpha);
+ *       Free:  |alpha| > eps limits both, d_v clamped so that up >= 0 >= down;
+ *       up = the smallest, down = the largest such quotient; blocking = N_index of the first extremal position.
+ *   a cost without a column (v >= n): (-Inf, +Inf, -1).
+ *   right-hand side of row k: over the basic positions i with w = W[i][k], |w| > eps, x = x_{B[i]} and its bounds:
+ *       up:   w > 0 and an upper bound (kind Upper, TwoSided, Fixed): fl(max(ub - x, 0) / w);
+ *             w < 0 and a lower bound (kind Lower, TwoSided, Fixed): fl(max(x - lb, 0) / -w);
+ *       down: w > 0 and a lower bound: fl(max(x - lb, 0) / -w);  w < 0 and an upper bound: fl(max(ub - x, 0) / w);
+ *       up = the smallest, down = the largest; blocking = B_index of the first extremal position.
+ *   NaN: a NaN alpha_ij (j not Fixed) or w_ik, or a NaN d_v or x in a quotient the definition forms, makes BOTH limits of that
+ *   row NaN (blocking: the first position that holds one); a NaN never yields a finite limit.
+ * min and max are exact and ties go to the smallest position, so no result depends on the order of the reduction: two calls
+ * on one state return the same bits.  The engine's state is not touched (a workspace of its own, m x ld doubles for W and
+ * four words per row and block of 128 columns, made at the first call).
+ *
+ * Every pointer of ellp_ranging_out may be NULL (not wanted); all NULL: ELLP_ERR_ARG.  Status and refusals as for
+ * ellp_engine_postsolve (a status produced by completing an open iteration is returned with the outputs; ELLP_ERR_SINGULAR
+ * leaves them untouched; ELLP_ERR_ARG before any HIP call: e NULL, out NULL or empty, a sharded engine, an engine in error).
+ */
+typedef struct ellp_ranging_info {
+    double inverse_residual; /* max_ij |(I - A_B W)_ij| of the computed W, each entry summed in ascending k without fma; NaN
+                                if any entry is.  Reported, never used to refuse a result */
+    int64_t reserved;
+    ellp_kkt kkt;            /* the report of the underlying postsolve */
+} ellp_ranging_info;
+
+typedef struct ellp_ranging_out {
+    double *cost_down, *cost_up;                     /* n_c, by variable */
+    int64_t *cost_blocking_down, *cost_blocking_up;  /* n_c */
+    double *rhs_down, *rhs_up;                       /* m, by row */
+    int64_t *rhs_blocking_down, *rhs_blocking_up;    /* m */
+    double *d;                                       /* n_c: the postsolve's reduced costs the ratios were formed from */
+    double *y;                                       /* m: the postsolve's duals (with d and info->kkt: one call gives both) */
+    ellp_ranging_info *info;
+} ellp_ranging_out;
+
+ellp_status ellp_engine_ranging(ellp_engine *e, const ellp_ranging_out *out, char *errbuf, size_t errbuf_len);
+
+/* The same for a point in host memory, with the argument list and the refusals of ellp_postsolve: the same kernels, the
+ * same bits. */
+ellp_status ellp_ranging(int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
+                         const uint8_t *bound_kind, const double *lb, const double *ub, const double *x,
+                         const int64_t *B_index, int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N,
+                         const ellp_opts *opts, const ellp_ranging_out *out, char *errbuf, size_t errbuf_len);
+
+/* Chosen rows of the tableau and of W behind them, as the ranging forms them (the same kernel with a storing epilogue: the
+ * same bits): alpha[p * n_N + j] = rho_i . a_{N[j]} and rho[p * m + k] = W[i][k] for i = positions[p], p < k.  rho may be
+ * NULL.  Refusals as above, and a position outside [0, m), k < 1 or positions / alpha NULL: ELLP_ERR_ARG before any HIP call.
+ * Every call pays the whole postsolve and the whole of W again (the state may have moved between two calls), whatever k
+ * is: 30 ms at 2000 rows, 160 ms at 4000; ask for all the rows wanted in one call. */
+ellp_status ellp_engine_tableau_rows(ellp_engine *e, const int64_t *positions, int64_t k, double *alpha /* k x n_N */,
+                                     double *rho /* k x m */, char *errbuf, size_t errbuf_len);
+
+/*
  * SURVEY.md §8 f3 — the rank check of the standard form on the device: column-pivoted Householder
  * QR of A^T (src/standard_form.rs:142 `A.transpose().col_piv_qr()`), reduced to what :143-181
  * consume.  A: m x nv column-major (ld = m) in HOST memory, not modified.  pivot_out[i] = the

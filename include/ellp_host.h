@@ -73,6 +73,35 @@ typedef struct ellp_result_ex {
 int ellp_solve_ex(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, int postsolve, ellp_result_ex *out);
 void ellp_result_ex_free(ellp_result_ex *r);
 
+/* ellp_solve with a flags word: ELLP_SOLVE_POSTSOLVE as ellp_solve_ex's postsolve, ELLP_SOLVE_RANGING (implies the postsolve)
+ * adds the sensitivity ranging of an Optimal result (ellp_engine_ranging / ellp_ranging, ellp_hip.h has the definitions): for
+ * every variable of the problem the change of its cost over which the final basis stays optimal, for every constraint the
+ * change of its right-hand side over which the basis stays feasible (down <= 0 <= up, -+Inf: unlimited; a row the rank check
+ * dropped: 0, 0, -1).  Blocking entries are indices of the standard form: below the problem's variable count that variable,
+ * above a slack or phase-1 column, -1 for an unlimited side.  The final basis is reported in the same indices: B_index
+ * (one per row of the standard form), N_index / N_bound (ELLP_NB_*), x_std (the point by standard-form index) and
+ * row_origin (the constraint each row of the standard form came from).  flags == 0: exactly ellp_solve, not one extra device
+ * call.  ellp_solve_ex and ellp_result_ex are unchanged. */
+#define ELLP_SOLVE_POSTSOLVE 1u
+#define ELLP_SOLVE_RANGING 2u
+typedef struct ellp_result_rng {
+    ellp_result_ex ex;
+    int has_ranging;
+    int64_t n_cost;            /* the problem's variables */
+    double *cost_down, *cost_up;
+    int64_t *cost_blocking_down, *cost_blocking_up;
+    int64_t n_rhs;             /* the problem's constraints */
+    double *rhs_down, *rhs_up;
+    int64_t *rhs_blocking_down, *rhs_blocking_up;
+    double inverse_residual;
+    int64_t n_B, n_N, n_x_std; /* the final basis in standard form */
+    int64_t *B_index, *N_index, *row_origin;
+    uint8_t *N_bound;
+    double *x_std;
+} ellp_result_rng;
+int ellp_solve_flags(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, unsigned flags, ellp_result_rng *out);
+void ellp_result_rng_free(ellp_result_rng *r);
+
 /* solve() of many problems by one solver in lock step: every phase's device loops of the problems the small kernel
  * takes (1 to 128 rows, with nonbasic columns), and of the 129 to 1,024-row problems the single call runs on the exact
  * mid-size kernel (pipeline 3, ELLP_MID_AUTO_MAX, the dual's bound flipping), run in one batched
