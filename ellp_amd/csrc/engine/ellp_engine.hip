@@ -3180,694 +3180,7 @@ inline void replace_alloc(ellp_engine *e, void *old, void *neu) {
     e->allocs.push_back(neu);  // `old` lives in the slab
 }
 
-struct Prof {
-    ellp_engine *e;
-    int id;
-    bool on;
-    hipEvent_t a{}, b{};
-    Prof(ellp_engine *e_, int id_) : e(e_), id(id_), on(e_->opts.profile != 0) {
-        if (!on) return;
-        if (e->ev_next + 2 > e->ev_pool.size()) {
-            for (int k = 0; k < 64; ++k) {
-                hipEvent_t ev;
-                if (hipEventCreate(&ev) != hipSuccess) { on = false; return; }
-                e->ev_pool.push_back(ev);
-            }
-        }
-        a = e->ev_pool[e->ev_next++];
-        b = e->ev_pool[e->ev_next++];
-        (void)hipEventRecord(a, e->stream);
-    }
-    ~Prof() {
-        if (!on) return;
-        (void)hipEventRecord(b, e->stream);
-        e->pending.push_back({id, a, b});
-    }
-};
-
-// What an event bracket adds to the one kernel inside it, relative to rocprofv3's duration of
-// that kernel.  Measured on MI355X / ROCm 7.2 with tools/event_cal.hip and with bench.py run
-// under rocprofv3: 2.4 us around a 23.6 us kernel, 2.45 us around a null kernel, 2.2-2.5 us
-// around k_price / k_ftran2 / k_update2.  It is a property of the event markers, not of the
-// kernel, and it cannot be measured live without the profiler: an EMPTY pair reads 4.4 us, and
-// differences between one launch and N back-to-back launches include a dispatch gap that varies
-// from 0.35 to 2 us with the kernel.  So the constant below is subtracted (2.3 us errs on the
-// side of longer kernels); ELLP_EVENT_BRACKET_US overrides it, ELLP_PROF_RAW=1 reports raw
-// brackets.  profiles/ holds the rocprofv3 summaries the bench's figures are checked against.
-constexpr double EVENT_BRACKET_US = 2.3;
-
-void prof_calibrate(ellp_engine *e) {
-    if (e->ev_overhead_ms >= 0.0 || !e->opts.profile) return;
-    e->ev_overhead_ms = EVENT_BRACKET_US * 1e-3;
-    if (const char *v = getenv("ELLP_PROF_RAW"); v && v[0] == '1') e->ev_overhead_ms = 0.0;
-    if (const char *v = getenv("ELLP_EVENT_BRACKET_US"); v && v[0]) {
-        const double us = atof(v);
-        if (us >= 0.0 && us < 20.0) e->ev_overhead_ms = us * 1e-3;
-    }
-}
-
-void prof_collect(ellp_engine *e) {
-    prof_calibrate(e);
-    for (auto &p : e->pending) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-            double v = (double)ms - (p.id == ELLP_K_REFACTOR ? 0.0 : e->ev_overhead_ms);
-            e->kernel_ms[p.id] += v > 0.0 ? v : 0.0;
-            e->kernel_calls[p.id] += 1;
-        }
-    }
-    e->pending.clear();
-    e->ev_next = 0;
-}
-
-// ---- launches -----------------------------------------------------------------------------
-template <int MODE>
-void launch_price(ellp_engine *e) {
-    PriceArgs a{};
-    a.A_N = e->A_N;
-    a.W0 = e->W;
-    a.W1 = e->W2;
-    a.u = e->u;
-    a.c_N = e->c_N;
-    a.Nb = e->Nb;
-    a.N_index = e->N_index;
-    a.dd = e->dd;
-    a.xc = Xchg{e->X, e->seg, e->nbs, e->cpb};
-    a.st = e->st;
-    a.ld = e->ld;
-    a.nN = e->nN;
-    a.cpb = e->cpb;
-    a.block0 = e->rank * e->nbs;
-    a.eps = e->eps;
-    a.pp_on = e->pp_P > 1 ? 1 : 0;
-    a.vs_row = !(e->opts.flags & ELLP_FLAG_DENSE_PRICING) ? e->vs_row : nullptr;
-    a.vs_val = a.vs_row ? e->vs_val : nullptr;
-    a.rho_ovr = MODE == 1 ? e->price_rho_ovr : nullptr;
-    if (MODE == 1 && e->dual_fold) {
-        a.dp_seq = e->dual_seq;
-        a.dp_lrow = e->binfo; a.dp_ldelta = e->bmin; a.dp_lside = e->bmin + e->m; a.dp_d = e->d;
-        a.dp_nrb = (int)((e->m + UPD_ROWS - 1) / UPD_ROWS);
-        a.dp_maxviol = e->dual_maxviol;
-        a.dp_A_N = e->A_N; a.dp_A_B = e->A_B; a.dp_c_B = e->c_B; a.dp_c_N = e->c_N; a.dp_x = e->x; a.dp_dd = e->dd;
-        a.dp_B_index = e->B_index; a.dp_N_index = e->N_index; a.dp_Nb = e->Nb;
-        a.dp_trace = Trace{e->trace_obj, e->trace_it, e->trace_len};
-    }
-    int mine = e->nblocks - a.block0;
-    if (mine > e->nbs) mine = e->nbs;
-    if (mine <= 0) mine = 1;  // empty shard (more ranks than pricing blocks): the block only serves DevState::tiny
-    dim3 g(mine), b(256);
-    if (e->price_wave) {
-        hipLaunchKernelGGL((k_price_wave<MODE>), g, b, 0, e->stream, a);
-        return;
-    }
-    if (e->price_nt) {
-        switch (e->priceT) {
-        case 1: hipLaunchKernelGGL((k_price<1, MODE, true>), g, b, 0, e->stream, a); break;
-        case 2: hipLaunchKernelGGL((k_price<2, MODE, true>), g, b, 0, e->stream, a); break;
-        case 4: hipLaunchKernelGGL((k_price<4, MODE, true>), g, b, 0, e->stream, a); break;
-        case 8: hipLaunchKernelGGL((k_price<8, MODE, true>), g, b, 0, e->stream, a); break;
-        default: hipLaunchKernelGGL((k_price<16, MODE, true>), g, b, 0, e->stream, a); break;
-        }
-    } else {
-        switch (e->priceT) {
-        case 1: hipLaunchKernelGGL((k_price<1, MODE, false>), g, b, 0, e->stream, a); break;
-        case 2: hipLaunchKernelGGL((k_price<2, MODE, false>), g, b, 0, e->stream, a); break;
-        case 4: hipLaunchKernelGGL((k_price<4, MODE, false>), g, b, 0, e->stream, a); break;
-        case 8: hipLaunchKernelGGL((k_price<8, MODE, false>), g, b, 0, e->stream, a); break;
-        default: hipLaunchKernelGGL((k_price<16, MODE, false>), g, b, 0, e->stream, a); break;
-        }
-    }
-}
-
-template <int MODE>
-void launch_ftran2(ellp_engine *e) {
-    Ftran2Args a{};
-    a.W0 = e->W; a.W1 = e->W2; a.A_N = e->A_N;
-    a.xc = Xchg{e->X, e->seg, e->nbs, e->cpb};
-    a.N_index = e->N_index; a.B_index = e->B_index; a.Nb = e->Nb; a.kind = e->kindv;
-    a.x = e->x; a.lb = e->lb; a.ub = e->ub;
-    a.d = e->d; a.lam = e->lam; a.bidx = e->bidx; a.dpos = e->dpos;
-    a.st = e->st; a.m = e->m; a.ld = e->ld; a.nN = e->nN; a.nblocks = e->nblocks; a.cpb = e->cpb; a.eps = e->eps;
-    a.aq_cur = (MODE == 0 && e->colshard) ? e->aq_cur : nullptr;
-    if (MODE == 0 && e->colshard && e->sel_in_ftran) {
-        a.sel_packs = e->packs; a.aq_out = e->aq_cur; a.sel_world = e->world; a.mbox_commit = e->sel_commit ? 1 : 0;
-    }
-    a.pp_on = (MODE == 0 && e->pp_P > 1) ? 1 : 0;
-    const dim3 g(e->ftran_blocks), b(256);
-    const int64_t nt = ((e->ld >> 1) + 63) / 64;  // double2 per lane for one row
-    if (nt <= 4) hipLaunchKernelGGL((k_ftran2<MODE, 4>), g, b, e->ftran_lds, e->stream, a);
-    else if (nt <= 8) hipLaunchKernelGGL((k_ftran2<MODE, 8>), g, b, e->ftran_lds, e->stream, a);
-    else if (nt <= 16) hipLaunchKernelGGL((k_ftran2<MODE, 16>), g, b, e->ftran_lds, e->stream, a);
-    else hipLaunchKernelGGL((k_ftran2<MODE, 0>), g, b, e->ftran_lds, e->stream, a);
-}
-
-template <int MODE>
-void launch_update2(ellp_engine *e, int update_u) {
-    Update2Args a{};
-    a.W0 = e->W; a.W1 = e->W2; a.d = e->d; a.lam = e->lam; a.bidx = e->bidx; a.dpos = e->dpos; a.xc = Xchg{e->X, e->seg, e->nbs, e->cpb};
-    a.u = e->u; a.u_alt = e->u + e->ld; a.A_N = e->A_N; a.A_B = e->A_B; a.c_B = e->c_B; a.c_N = e->c_N; a.x = e->x; a.y = e->y; a.dd = e->dd;
-    a.lb = e->lb; a.ub = e->ub; a.kind = e->kindv; a.B_index = e->B_index; a.N_index = e->N_index; a.Nb = e->Nb;
-    a.st = e->st; a.m = e->m; a.ld = e->ld; a.nN = e->nN; a.rows_per_block = e->upd2_rows; a.update_u = update_u;
-    a.stage_lds = e->upd_stage; a.eps = e->eps;
-    a.ill_tol = e->ill_tol;
-    a.guard_abs = ((e->hybrid || e->cert_large) && !e->guard_off) ? e->guard_abs : 0.0;
-    a.aq_cur = (MODE == 0 && e->colshard) ? e->aq_cur : nullptr; a.own0 = e->own0; a.own1 = e->own1;
-    a.count_iter = (MODE == 0 && e->lagged) ? 0 : 1;
-    a.maxviol = e->dual_maxviol;
-    a.se_gamma = (MODE == 0 && e->se) ? e->se_gamma : nullptr;
-    a.se_rho = (MODE == 0 && e->se) ? e->se_rho : nullptr;
-    a.se_vpart = (MODE == 0 && e->se) ? e->se_vpart : nullptr;
-    a.trace = Trace{e->trace_obj, e->trace_it, e->trace_len};
-    const dim3 g(e->upd2_blocks + (MODE == 0 ? 2 : 3)), b(256);
-    const size_t lds = MODE == 0 ? e->upd_lds : 0;
-    const int64_t nr = ((e->ld >> 1) + 255) / 256;  // double2 per thread per row
-    if (nr <= 1) hipLaunchKernelGGL((k_update2<MODE, 1>), g, b, lds, e->stream, a);
-    else if (nr <= 2) hipLaunchKernelGGL((k_update2<MODE, 2>), g, b, lds, e->stream, a);
-    else if (nr <= 4) hipLaunchKernelGGL((k_update2<MODE, 4>), g, b, lds, e->stream, a);
-    else if (nr <= 8) hipLaunchKernelGGL((k_update2<MODE, 8>), g, b, lds, e->stream, a);
-    else hipLaunchKernelGGL((k_update2<MODE, 0>), g, b, lds, e->stream, a);
-}
-
-// out = B^-T v (two buffers of out: DevState::usel; the same one twice where there is no other)
-void launch_btran(ellp_engine *e, const double *v, double *out0, double *out1) {
-    BtranArgs a{e->W, e->W2, v, e->upart, out0, out1, e->st, e->m, e->ld, e->btran_rows, e->btran_tiles};
-    const int64_t half = e->ld >> 1;
-    dim3 g((unsigned)((half + 255) / 256), (unsigned)e->btran_tiles);
-    hipLaunchKernelGGL(k_btran_part, g, dim3(256), 0, e->stream, a);
-    hipLaunchKernelGGL(k_btran_reduce, dim3((unsigned)((e->ld + 255) / 256)), dim3(256), 0, e->stream, a);
-}
-void launch_btran(ellp_engine *e) { launch_btran(e, e->c_B, e->u, e->u + e->ld); }  // u = B^-T c_B
-
-void launch_refactor_columnwise(ellp_engine *e) {
-    Prof p(e, ELLP_K_REFACTOR);
-    RefArgs a{e->W, e->W2, e->d, e->A_B, e->used, e->perm, e->st, e->m, e->ld, e->upd_rows,
-              e->kind == ELLP_ENGINE_PRIMAL ? e->eps : 0.0};
-    hipLaunchKernelGGL(k_ref_begin, dim3(1), dim3(1), 0, e->stream, a);
-    hipLaunchKernelGGL(k_ref_init, dim3(1024), dim3(256), 0, e->stream, a);
-    for (int64_t k = 0; k < e->m; ++k) {
-        hipLaunchKernelGGL(k_ref_ftran, dim3(e->ftran_blocks), dim3(256), 0, e->stream, a);
-        hipLaunchKernelGGL(k_ref_pick, dim3(1), dim3(1024), 0, e->stream, a);
-        hipLaunchKernelGGL(k_ref_update, dim3(e->upd_blocks), dim3(256), 0, e->stream, a);
-    }
-    hipLaunchKernelGGL(k_ref_permute, dim3((unsigned)e->m), dim3(256), 0, e->stream, a);
-    hipLaunchKernelGGL(k_ref_finish, dim3(1), dim3(1), 0, e->stream, a);
-    e->refactors += 1;
-    e->since_refactor = 0;
-    e->u_valid = false;
-}
-
-// the k_bl_factor variant of a rebuild of m rows: workgroup size and sub-panel width (read per rebuild)
-struct BlFactorVariant {
-    int bl_nt, nbw_max;
-};
-BlFactorVariant bl_factor_variant(int64_t m) {
-    BlFactorVariant v;
-    v.bl_nt = (getenv("ELLP_BL_NT") && atoi(getenv("ELLP_BL_NT")) == 1024) ? 1024 : 512;
-    v.nbw_max = m <= 2048 ? 16 : (m <= 4096 ? 8 : 4);
-    if (const char *s = getenv("ELLP_BL_NBW"); s && s[0]) {  // tests: a narrower sub-panel than the size needs
-        const int w = atoi(s);
-        if ((w == 8 || w == 4) && w < v.nbw_max) v.nbw_max = w;
-    }
-    return v;
-}
-
-// Blocked rebuild (ellp_rebuild.inc).  One host synchronisation: after the probe for a generalised
-// permutation matrix (the artificial / slack bases every phase 1 starts from), to know whether the
-// general elimination has to be enqueued at all.  Rebuilds are rare (engine creation, a refused refresh).
-void launch_refactor(ellp_engine *e) {
-    const bool legacy = e->bl_Cpart == nullptr || (getenv("ELLP_REBUILD") && !strcmp(getenv("ELLP_REBUILD"), "columnwise"));
-    if (legacy) {
-        launch_refactor_columnwise(e);
-        return;
-    }
-    Prof p(e, ELLP_K_REFACTOR);
-    const int64_t m = e->m;
-    BlArgs a{};
-    a.W0 = e->W; a.W1 = e->W2; a.A_B = e->A_B; a.Cpart = e->bl_Cpart; a.C0 = e->bl_C; a.C1 = e->bl_C + m * BL_NB;
-    a.V0 = e->bl_V; a.V1 = e->bl_V + m * BL_NB; a.Vs = e->bl_Vs; a.Wp = e->bl_Wp; a.used = e->used; a.perm = e->perm;
-    a.Pm = e->bl_Pm; a.st = e->st; a.m = m; a.ld = e->ld; a.splits = e->bl_splits;
-    a.ksplit = (int)round_up((m + e->bl_splits - 1) / e->bl_splits, 16);
-    a.eps = e->kind == ELLP_ENGINE_PRIMAL ? e->eps : 0.0;
-    e->refactors += 1;
-    e->since_refactor = 0;
-    e->u_valid = false;
-    // ---- shortcut: one nonzero per column, distinct rows
-    hipLaunchKernelGGL(k_bl_probe, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, e->stream, a, e->bl_nzval, e->bl_nzrow, e->bl_nzcnt);
-    hipLaunchKernelGGL(k_bl_perm_check, dim3(1), dim3(1024), 0, e->stream, a, e->bl_nzval, e->bl_nzrow, e->bl_nzcnt);
-    hipLaunchKernelGGL(k_bl_perm_fill, dim3((unsigned)m), dim3(256), 0, e->stream, a, e->bl_nzval, e->bl_nzrow);
-    DevState probe;
-    if (hipMemcpyAsync(&probe, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-        hipStreamSynchronize(e->stream) != hipSuccess)
-        return;
-    static const int32_t zero = 0;  // static: the copy may still be in flight when this function returns
-    (void)hipMemcpyAsync(&e->st->do_update, &zero, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    if (probe.status != ST_RUNNING) return;  // singular (or the engine is not running: the kernels did nothing)
-    if (probe.do_update) {
-        e->rebuild_shortcuts += 1;
-        return;
-    }
-    // ---- general case
-    RefArgs ra{e->W, e->W2, e->d, e->A_B, e->used, e->perm, e->st, e->m, e->ld, e->upd_rows, a.eps};
-    hipLaunchKernelGGL(k_ref_init, dim3(1024), dim3(256), 0, e->stream, ra);
-    const auto [bl_nt, nbw_max] = bl_factor_variant(m);
-    for (int64_t k0 = 0; k0 < m; k0 += BL_NB) {
-        a.k0 = (int)k0;
-        a.nbc = (int)((m - k0) < BL_NB ? (m - k0) : BL_NB);
-        a.sel = 0;
-        hipLaunchKernelGGL(k_bl_gemm1, dim3((unsigned)((m + 63) / 64), (unsigned)a.splits), dim3(256), 0, e->stream, a);
-        hipLaunchKernelGGL(k_bl_sum, dim3(256), dim3(256), 0, e->stream, a);
-        for (int j0 = 0; j0 < a.nbc; j0 += nbw_max) {
-            a.j0 = j0;
-            a.nbw = (a.nbc - j0) < nbw_max ? (a.nbc - j0) : nbw_max;
-            a.nacc = j0;
-            if (bl_nt == 512) {  // two waves per SIMD, 256 VGPRs each: 4 / 8 / 16 rows per thread
-                if (nbw_max == 16) hipLaunchKernelGGL((k_bl_factor<16, 4, 512>), dim3(1), dim3(512), 0, e->stream, a);
-                else if (nbw_max == 8) hipLaunchKernelGGL((k_bl_factor<8, 8, 512>), dim3(1), dim3(512), 0, e->stream, a);
-                else hipLaunchKernelGGL((k_bl_factor<4, 16, 512>), dim3(1), dim3(512), 0, e->stream, a);
-            } else {
-                if (nbw_max == 16) hipLaunchKernelGGL((k_bl_factor<16, 2, 1024>), dim3(1), dim3(1024), 0, e->stream, a);
-                else if (nbw_max == 8) hipLaunchKernelGGL((k_bl_factor<8, 4, 1024>), dim3(1), dim3(1024), 0, e->stream, a);
-                else hipLaunchKernelGGL((k_bl_factor<4, 8, 1024>), dim3(1), dim3(1024), 0, e->stream, a);
-            }
-            hipLaunchKernelGGL(k_bl_apply, dim3((unsigned)((m + 7) / 8)), dim3(256), 0, e->stream, a);
-            a.sel ^= 1;
-        }
-        hipLaunchKernelGGL(k_bl_gather, dim3((unsigned)a.nbc), dim3(256), 0, e->stream, a);
-        hipLaunchKernelGGL(k_bl_gemm2, dim3((unsigned)((e->ld + 127) / 128), (unsigned)((m + 63) / 64)), dim3(256), 0, e->stream, a);
-    }
-    hipLaunchKernelGGL(k_ref_permute, dim3((unsigned)e->m), dim3(256), 0, e->stream, ra);
-    hipLaunchKernelGGL(k_ref_finish, dim3(1), dim3(1), 0, e->stream, ra);
-}
-
-// One Newton-Schulz step on the current inverse, enqueued without any host synchronisation: the
-// residual max|I - A_B W| of the first GEMM is folded on the device (k_resid_reduce), which also
-// decides whether the step is safe; if it is not, the step is skipped, DevState::need_rebuild is set
-// and the loop stops with a maintenance request that the host services by rebuilding from A_B.
-void launch_refresh(ellp_engine *e) {
-    Prof p(e, ELLP_K_REFACTOR);
-    GemmArgs a{e->W, e->W2, e->A_B, e->T, e->resid, e->st, e->m, e->ld};
-    const unsigned nt = (unsigned)((e->m + 127) / 128);
-    static const bool valu = [] {  // measurement: ELLP_GEMM=valu runs round 1's vector-ALU GEMM
-        const char *v = getenv("ELLP_GEMM");
-        return v && strcmp(v, "valu") == 0;
-    }();
-    if (valu) hipLaunchKernelGGL(k_gemm128<0>, dim3(nt, nt), dim3(256), 0, e->stream, a);
-    else hipLaunchKernelGGL(k_gemm_mfma<0>, dim3(nt, nt), dim3(512), 0, e->stream, a);
-    hipLaunchKernelGGL(k_resid_reduce, dim3(1), dim3(256), 0, e->stream, a, (int)(nt * nt));
-    if (valu) hipLaunchKernelGGL(k_gemm128<1>, dim3(nt, nt), dim3(256), 0, e->stream, a);
-    else hipLaunchKernelGGL(k_gemm_mfma<1>, dim3(nt, nt), dim3(512), 0, e->stream, a);
-    hipLaunchKernelGGL(k_copy_to_other, dim3(1024), dim3(256), 0, e->stream, a);
-    hipLaunchKernelGGL(k_refresh_finish, dim3(1), dim3(1), 0, e->stream, a);
-    e->refreshes += 1;
-    e->since_refactor = 0;
-    e->u_valid = false;
-}
-
-// periodic maintenance of B^-1: Newton-Schulz refresh, full rebuild only if that is not safe
-void launch_dleave(ellp_engine *e);
-void launch_resync(ellp_engine *e, int force);
-
-// tvec = b - A_N x_N: the front of the resync, and of the primal phase-1 start (its b~)
-ResyncArgs launch_resync_rhs(ellp_engine *e, int force) {
-    ResyncArgs a{e->A_N, e->W, e->W2, e->b_dev, e->x, e->xg, e->tvec, e->upart, e->cand, e->maxbits, e->B_index,
-                 e->N_index, e->st, e->m, e->ld, e->nN, 0, e->btran_tiles, force};
-    a.cols_per_tile = (int)((e->nN + e->btran_tiles - 1) / e->btran_tiles);
-    const int64_t half = e->ld >> 1;
-    hipLaunchKernelGGL(k_resync_gather, dim3((unsigned)((e->nN + 255) / 256)), dim3(256), 0, e->stream, a);
-    hipLaunchKernelGGL(k_resync_part, dim3((unsigned)((half + 255) / 256), (unsigned)e->btran_tiles), dim3(256), 0,
-                       e->stream, a);
-    hipLaunchKernelGGL(k_resync_rhs, dim3((unsigned)((e->ld + 255) / 256)), dim3(256), 0, e->stream, a);
-    return a;
-}
-
-// x_B from the freshly maintained B^-1 (see k_resync_part)
-void launch_resync(ellp_engine *e, int force) {
-    if (e->nN <= 0) return;
-    if (e->colshard) return;  // b - A_N x_N would need every rank's columns (a reduction over the ranks): not done
-    const ResyncArgs a = launch_resync_rhs(e, force);  // k_resync_rhs also zeroes maxbits
-    hipLaunchKernelGGL(k_resync_xb, dim3((unsigned)((e->m + 3) / 4)), dim3(256), 0, e->stream, a);
-    hipLaunchKernelGGL(k_resync_apply, dim3((unsigned)((e->m + 255) / 256)), dim3(256), 0, e->stream, a);
-    if (e->kind == ELLP_ENGINE_DUAL) launch_dleave(e);  // the leaving row is chosen from x (dual…:200-236)
-    e->resyncs += 1;
-    if (getenv("ELLP_RESYNC_DEBUG")) {  // diagnostics: what the resync found
-        unsigned long long hb[2] = {0, 0};
-        (void)hipMemcpyAsync(hb, e->maxbits, sizeof(hb), hipMemcpyDeviceToHost, e->stream);
-        (void)hipStreamSynchronize(e->stream);
-        double dv[2];
-        memcpy(dv, hb, sizeof(dv));
-        fprintf(stderr, "ellp resync %llu: max|cand - x_B| %.3e, max|x_B| %.3e\n", (unsigned long long)e->resyncs, dv[0], dv[1]);
-    }
-}
-
-// Maintenance of B^-1: Newton-Schulz refresh, full rebuild if that is not safe, then x_B is checked
-// against the fresh inverse (launch_resync).  `reactive` (asked for by the device, or the follow-up of
-// such a request) is kept for diagnostics: resynchronising only then was tried and is worse (netlib
-// ADLITTLE / BLEND in 60 variable orders, dual: 4 wrong outcomes instead of 1).
-void launch_dual_close(ellp_engine *e);
-void maintain_inverse(ellp_engine *e, bool reactive = false, bool rebuild = false) {
-    // two-launch pipeline: an open iteration (priced, FTRAN done, ratio test not folded) was decided with
-    // the inverse that is about to be replaced — drop it; the next k_price2 starts afresh (use_pend = 0) and
-    // the iteration is priced again from the maintained inverse.  Its eta-update half is already in B^-1.
-    launch_dual_close(e);  // a fused dual iteration is completed, not dropped: its pivot is in B^-1 already
-    if (e->lagged) hipLaunchKernelGGL(k_drop_open, dim3(1), dim3(1), 0, e->stream, e->st);
-    e->lag_open = false;
-    if (rebuild) launch_refactor(e);
-    else launch_refresh(e);
-    const char *mode = getenv("ELLP_RESYNC");  // diagnostics: "0" never, "1" only on reactive maintenance
-    const bool want = mode && mode[0] == '0' ? false : (mode && mode[0] == '1' ? reactive : true);
-    if (want) launch_resync(e, 0);
-}
-
-// After a read-back with the stream drained: iterations that were enqueued behind a stop (a final
-// status or a maintenance request) returned at entry and did not happen, but the host counted them
-// when it enqueued them.  Take them back, so that the maintenance schedule follows the iterations
-// that really ran (DevState::iters counts every loop body entered).
-void reconcile_counters(ellp_engine *e) {
-    const uint64_t ran = e->h_st->iters >= e->iters_seen ? e->h_st->iters - e->iters_seen : 0;
-    const uint64_t lost = e->enqueued > ran ? e->enqueued - ran : 0;
-    if (lost) {
-        e->since_refactor = e->since_refactor > lost ? e->since_refactor - lost : 0;
-        e->since_btran = e->since_btran > lost ? e->since_btran - lost : 0;
-        e->since_drift = e->since_drift > lost ? e->since_drift - lost : 0;
-    }
-    e->enqueued = 0;
-    e->iters_seen = e->h_st->iters;
-}
-
-// two-launch pipeline: k_ftran_eta reports the end of the solve in DevState::fin and leaves it to the next
-// kernel's leader to make it the status; after a drained read-back the host can do that itself
-void adopt_fin(ellp_engine *e) {
-    if (e->h_st->status != ST_RUNNING || !e->h_st->fin) return;
-    static int32_t fin_status;  // static: asynchronous copy
-    fin_status = e->h_st->fin - 1;
-    (void)hipMemcpyAsync(&e->st->status, &fin_status, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    (void)hipStreamSynchronize(e->stream);
-    e->h_st->status = fin_status;
-}
-
-// After a status read-back: if a kernel asked for maintenance, do it, re-arm the loop and report
-// true (the caller keeps going).  The pivot that raised the request is committed (k_update2 raises the
-// flag after its bookkeeping); what is void is the rest of the batch behind it.  The device is
-// re-armed (status = RUNNING, tiny = 0) BEFORE the maintenance kernels are enqueued: all of them
-// (k_gemm128, k_copy_to_other, k_ref_*, k_dleave) return at entry on any other status, so servicing
-// the request under ST_NEED_MAINT would refresh nothing and re-select the dual's leaving row from
-// nothing.
-bool service_maintenance_request(ellp_engine *e) {
-    // the request is the status (a later pricing launch of the batch saw the flag) or still the flag
-    // (the batch ended with the k_update2 that raised it)
-    if (e->h_st->status != ST_NEED_MAINT && !(e->h_st->status == ST_RUNNING && e->h_st->tiny)) return false;
-    const int32_t running = ST_RUNNING, zero = 0;
-    const bool rebuild = e->h_st->need_rebuild != 0;  // a refresh found B^-1 too far off for Newton-Schulz
-    (void)hipMemcpyAsync(&e->st->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    (void)hipMemcpyAsync(&e->st->tiny, &zero, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    (void)hipMemcpyAsync(&e->st->need_rebuild, &zero, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-    e->h_st->status = ST_RUNNING;
-    e->h_st->tiny = 0;
-    e->h_st->need_rebuild = 0;
-    maintain_inverse(e, true, rebuild);
-    e->maint_chain = 1;
-    (void)hipStreamSynchronize(e->stream);
-    e->maint_requests += 1;
-    return true;
-}
-
-// between k_ftran2 and k_update2 of an iteration: see k_drift_part
-void launch_drift_check(ellp_engine *e) {
-    if (e->drift_every <= 0) return;
-    if (++e->since_drift < (uint64_t)e->drift_every) return;
-    e->since_drift = 0;
-    e->drift_checks += 1;
-    DriftArgs a{e->A_B, e->A_N, e->d, e->colshard ? e->aq_cur : nullptr, e->upart, e->st, e->m, e->ld, e->btran_rows, e->btran_tiles, e->drift_tol};
-    const int64_t half = e->ld >> 1;
-    hipLaunchKernelGGL(k_drift_part, dim3((unsigned)((half + 255) / 256), (unsigned)e->btran_tiles), dim3(256), 0,
-                       e->stream, a);
-    hipLaunchKernelGGL(k_drift_reduce, dim3((unsigned)((e->m + WAVE - 1) / WAVE)), dim3(WAVE), 0, e->stream, a);
-}
-
-// ---- two-launch pipeline (ellp_lagged.inc) -------------------------------------------------------
-void launch_price2(ellp_engine *e, int use_pend) {
-    Price2Args a{};
-    a.p.A_N = e->A_N; a.p.W0 = e->W; a.p.W1 = e->W2; a.p.u = nullptr; a.p.c_N = e->c_N; a.p.Nb = e->Nb;
-    a.p.N_index = e->N_index; a.p.dd = nullptr; a.p.xc = Xchg{e->X, e->seg, e->nbs, e->cpb}; a.p.st = e->st;
-    a.p.ld = e->ld; a.p.nN = e->nN; a.p.cpb = e->cpb; a.p.block0 = e->rank * e->nbs; a.p.eps = e->eps;
-    a.p.vs_row = e->vs_row; a.p.vs_val = e->vs_val; a.pos_hint = e->pos_hint;
-    a.u0 = e->u; a.u1 = e->u + e->ld; a.W0 = e->W; a.W1 = e->W2;
-    a.d = e->d; a.lam = e->lam; a.bmin = e->bmin; a.bsec = e->bmin + e->m; a.bidx = e->bidx; a.binfo = e->binfo; a.dpos = e->dpos;
-    a.A_N = e->A_N; a.A_B = e->A_B; a.aq_save = e->aq_save; a.c_B = e->c_B; a.c_N = e->c_N; a.x = e->x;
-    a.lb = e->lb; a.ub = e->ub; a.kind = e->kindv; a.B_index = e->B_index; a.N_index = e->N_index; a.Nb = e->Nb;
-    a.m = e->m; a.rpb = e->upd2_rows; a.use_pend = use_pend; a.ill_tol = e->ill_tol;
-    a.guard_abs = (e->cert_large && !e->guard_off) ? e->guard_abs : 0.0;
-    a.aq_cur = e->colshard ? e->aq_cur : nullptr; a.own0 = e->own0; a.own1 = e->own1;
-    a.trace = Trace{e->trace_obj, e->trace_it, e->trace_len};
-    int mine = e->nblocks - a.p.block0;
-    if (mine > e->nbs) mine = e->nbs;
-    if (mine < 0) mine = 0;
-    const dim3 g(mine + P2_BOOK), b(256);
-    const size_t lds = e->price2_lds;
-    if (e->colshard) {  // the sharded instantiations (ellp_lagged.inc, SH)
-        if (e->price_wave) {
-            hipLaunchKernelGGL((k_price2_wave<true>), g, b, lds + sizeof(double) * (size_t)e->ld, e->stream, a);
-            return;
-        }
-        if (e->price_nt) {
-            switch (e->priceT) {
-            case 1: hipLaunchKernelGGL((k_price2<1, true, true>), g, b, lds, e->stream, a); break;
-            case 2: hipLaunchKernelGGL((k_price2<2, true, true>), g, b, lds, e->stream, a); break;
-            case 4: hipLaunchKernelGGL((k_price2<4, true, true>), g, b, lds, e->stream, a); break;
-            case 8: hipLaunchKernelGGL((k_price2<8, true, true>), g, b, lds, e->stream, a); break;
-            default: hipLaunchKernelGGL((k_price2<16, true, true>), g, b, lds, e->stream, a); break;
-            }
-        } else {
-            switch (e->priceT) {
-            case 1: hipLaunchKernelGGL((k_price2<1, false, true>), g, b, lds, e->stream, a); break;
-            case 2: hipLaunchKernelGGL((k_price2<2, false, true>), g, b, lds, e->stream, a); break;
-            case 4: hipLaunchKernelGGL((k_price2<4, false, true>), g, b, lds, e->stream, a); break;
-            case 8: hipLaunchKernelGGL((k_price2<8, false, true>), g, b, lds, e->stream, a); break;
-            default: hipLaunchKernelGGL((k_price2<16, false, true>), g, b, lds, e->stream, a); break;
-            }
-        }
-        return;
-    }
-    if (e->price_wave) {
-        hipLaunchKernelGGL((k_price2_wave<false>), g, b, lds + sizeof(double) * (size_t)e->ld, e->stream, a);
-        return;
-    }
-    if (e->price_nt) {
-        switch (e->priceT) {
-        case 1: hipLaunchKernelGGL((k_price2<1, true>), g, b, lds, e->stream, a); break;
-        case 2: hipLaunchKernelGGL((k_price2<2, true>), g, b, lds, e->stream, a); break;
-        case 4: hipLaunchKernelGGL((k_price2<4, true>), g, b, lds, e->stream, a); break;
-        case 8: hipLaunchKernelGGL((k_price2<8, true>), g, b, lds, e->stream, a); break;
-        default: hipLaunchKernelGGL((k_price2<16, true>), g, b, lds, e->stream, a); break;
-        }
-    } else {
-        switch (e->priceT) {
-        case 1: hipLaunchKernelGGL((k_price2<1, false>), g, b, lds, e->stream, a); break;
-        case 2: hipLaunchKernelGGL((k_price2<2, false>), g, b, lds, e->stream, a); break;
-        case 4: hipLaunchKernelGGL((k_price2<4, false>), g, b, lds, e->stream, a); break;
-        case 8: hipLaunchKernelGGL((k_price2<8, false>), g, b, lds, e->stream, a); break;
-        default: hipLaunchKernelGGL((k_price2<16, false>), g, b, lds, e->stream, a); break;
-        }
-    }
-}
-
-void launch_ftran_eta(ellp_engine *e) {
-    FtranEtaArgs a{};
-    a.W0 = e->W; a.W1 = e->W2; a.A_N = e->A_N; a.xc = Xchg{e->X, e->seg, e->nbs, e->cpb};
-    a.N_index = e->N_index; a.B_index = e->B_index; a.Nb = e->Nb; a.kind = e->kindv;
-    a.x = e->x; a.lb = e->lb; a.ub = e->ub; a.d = e->d; a.lam = e->lam; a.bmin = e->bmin; a.bsec = e->bmin + e->m; a.bidx = e->bidx;
-    a.binfo = e->binfo; a.dpos = e->dpos;
-    a.A_B = e->A_B; a.c_B = e->c_B; a.aq_save = e->aq_save; a.st = e->st; a.m = e->m; a.ld = e->ld; a.nN = e->nN;
-    a.nblocks = e->nblocks; a.cpb = e->cpb; a.rows_per_block = e->upd2_rows; a.eps = e->eps;
-    if (e->colshard) {
-        a.aq_cur = e->aq_cur; a.aq_out = e->aq_cur;
-        if (e->sel_in_ftran) {
-            a.sel_packs = e->packs; a.sel_world = e->world; a.mbox_commit = e->sel_commit ? 1 : 0;
-        }
-    }
-    const dim3 g(e->upd2_blocks + 1), b(256);
-    const int64_t nr = ((e->ld >> 1) + 255) / 256;  // double2 per thread per row
-    if (e->colshard) {  // the sharded instantiations (selection in the prologue instead of the entering fold)
-        if (nr <= 1) hipLaunchKernelGGL((k_ftran_eta<1, true>), g, b, e->ftran_lds, e->stream, a);
-        else if (nr <= 2) hipLaunchKernelGGL((k_ftran_eta<2, true>), g, b, e->ftran_lds, e->stream, a);
-        else if (nr <= 4) hipLaunchKernelGGL((k_ftran_eta<4, true>), g, b, e->ftran_lds, e->stream, a);
-        else if (nr <= 8) hipLaunchKernelGGL((k_ftran_eta<8, true>), g, b, e->ftran_lds, e->stream, a);
-        else hipLaunchKernelGGL((k_ftran_eta<0, true>), g, b, e->ftran_lds, e->stream, a);
-        return;
-    }
-    // rows in registers up to 2,048 doubles: a fifth wave folds and hands the entering column to the four that stream the
-    // rows through LDS (+8 ld bytes)
-    const size_t hand_lds = ftran_col_offset(e->nblocks) + sizeof(double) * (size_t)e->ld;
-    const dim3 bh(FTRAN_HAND_THREADS);
-    static_assert(ftran_eta_threads(1, false) == FTRAN_HAND_THREADS && ftran_eta_threads(4, false) == FTRAN_HAND_THREADS &&
-                      ftran_eta_threads(8, false) == 256 && ftran_eta_threads(4, true) == 256,
-                  "320 threads exactly where hand_lds is used");
-    if (nr <= 1) hipLaunchKernelGGL((k_ftran_eta<1>), g, bh, hand_lds, e->stream, a);
-    else if (nr <= 2) hipLaunchKernelGGL((k_ftran_eta<2>), g, bh, hand_lds, e->stream, a);
-    else if (nr <= 4) hipLaunchKernelGGL((k_ftran_eta<4>), g, bh, hand_lds, e->stream, a);
-    else if (nr <= 8) hipLaunchKernelGGL((k_ftran_eta<8>), g, b, e->ftran_lds, e->stream, a);
-    else hipLaunchKernelGGL((k_ftran_eta<0>), g, b, e->ftran_lds, e->stream, a);
-}
-
-// iteration k of the two-launch pipeline: P_k folds and books iteration k-1 (if one is open), prices k;
-// F_k applies the eta of k-1 and forms d_k.  Iteration k itself stays open until the next P or the flush.
-void launch_primal_iteration_lagged(ellp_engine *e) {
-    const bool full_btran = !e->u_valid || e->since_btran >= (uint64_t)e->btran_refresh;
-    if (full_btran) {
-        // u = B^-T c_B from the materialised inverse: W and c_B both stand at "all pivots but the open one",
-        // exactly the u_{k-1} that P_k advances by the open pivot's rank-1 term
-        Prof p(e, ELLP_K_BTRAN);
-        launch_btran(e);
-        e->since_btran = 0;
-        e->u_valid = true;
-    }
-    {
-        Prof p(e, ELLP_K_PRICE);
-        launch_price2(e, e->lag_open ? 1 : 0);
-    }
-    {
-        Prof p(e, ELLP_K_FTRAN);
-        launch_ftran_eta(e);
-    }
-    launch_drift_check(e);
-    e->lag_open = true;
-    e->since_btran += 1;
-    e->since_refactor += 1;
-    e->enqueued += 1;
-}
-
-// closing kernel of a slice: k_update2 folds the open iteration's ratio test, applies its eta update and
-// does its bookkeeping (the three-launch path's third kernel, unchanged)
-void launch_dual_close(ellp_engine *e);
-void launch_flush(ellp_engine *e) {
-    launch_dual_close(e);
-    if (!e->lag_open) return;
-    {
-        Prof p(e, ELLP_K_UPDATE);
-        launch_update2<0>(e, 1);
-    }
-    e->lag_open = false;
-}
-
-void launch_price_se(ellp_engine *e) {
-    SeArgs a{};
-    a.A_N = e->A_N; a.u = e->u; a.rho = e->se_rho; a.v = e->se_v; a.c_N = e->c_N; a.Nb = e->Nb; a.N_index = e->N_index;
-    a.gamma = e->se_gamma;
-    const bool unit_ok = !(e->opts.flags & ELLP_FLAG_DENSE_PRICING);
-    a.vs_row = unit_ok ? e->vs_row : nullptr; a.vs_val = unit_ok ? e->vs_val : nullptr;
-    a.xc = Xchg{e->X, e->seg, e->nbs, e->cpb}; a.st = e->st; a.ld = e->ld; a.nN = e->nN; a.cpb = e->cpb; a.eps = e->eps;
-    hipLaunchKernelGGL(k_price_se, dim3((unsigned)e->nblocks), dim3(256), 0, e->stream, a);
-}
-
-void launch_primal_iteration(ellp_engine *e) {
-    if (e->lagged) {
-        launch_primal_iteration_lagged(e);
-        return;
-    }
-    const bool full_btran = (e->opts.btran_mode == 1) || !e->u_valid || e->since_btran >= (uint64_t)e->btran_refresh;
-    if (full_btran) {
-        Prof p(e, ELLP_K_BTRAN);
-        launch_btran(e);
-        e->since_btran = 0;
-        e->u_valid = true;
-    }
-    {
-        Prof p(e, ELLP_K_PRICE);
-        if (e->se) launch_price_se(e);
-        else launch_price<0>(e);
-    }
-    {
-        Prof p(e, ELLP_K_FTRAN);
-        launch_ftran2<0>(e);
-    }
-    if (e->se && !e->se_vpart) {  // v = B^-T d from the inverse this iteration's FTRAN used: the weight update of the NEXT pricing launch
-        Prof p(e, ELLP_K_BTRAN);
-        launch_btran(e, e->d, e->se_v, e->se_v);
-    }
-    launch_drift_check(e);
-    {
-        Prof p(e, ELLP_K_UPDATE);
-        launch_update2<0>(e, e->opts.btran_mode == 1 ? 0 : 1);
-    }
-    if (e->se && e->se_vpart) {  // v = the row blocks' partial sums of k_update2, added in block order
-        Prof p(e, ELLP_K_BTRAN);
-        hipLaunchKernelGGL(k_se_vreduce, dim3((unsigned)((e->ld + 15) / 16)), dim3(256), 0, e->stream, e->se_vpart, e->se_v, e->st, e->ld,
-                           e->upd2_blocks);
-    }
-    e->since_btran += 1;
-    e->since_refactor += 1;
-    e->enqueued += 1;
-}
-
-// the closing block of the fused dual iteration in front (a no-op on the device if that has been closed already)
-void launch_dual_close(ellp_engine *e) {
-    if (!e->dual_open) return;
-    Prof p(e, ELLP_K_DUPDATE);
-    DualCloseArgs c{e->d, e->A_N, e->A_B, e->c_B, e->c_N, e->x, e->dd, e->B_index, e->N_index, e->Nb, e->binfo, e->bmin,
-                    e->bmin + e->m, (int)((e->m + UPD_ROWS - 1) / UPD_ROWS), e->st, e->m, e->ld, e->ill_tol,
-                    Trace{e->trace_obj, e->trace_it, e->trace_len}, e->dual_maxviol};
-    hipLaunchKernelGGL(k_dual_close, dim3(1), dim3(256), 0, e->stream, c);
-    e->dual_open = false;
-}
-
-// FTRAN + eta update + x_B / d_N / y updates in one pass (ellp_dualfu.inc); the iteration stays open
-void launch_dual_fu(ellp_engine *e) {
-    Prof p(e, ELLP_K_FTRAN);
-    DualFuArgs a{};
-    a.W0 = e->W; a.W1 = e->W2; a.A_N = e->A_N; a.xc = Xchg{e->X, e->seg, e->nbs, e->cpb};
-    a.N_index = e->N_index; a.B_index = e->B_index; a.x = e->x; a.d = e->d; a.y = e->y; a.dd = e->dd;
-    a.lb = e->lb; a.ub = e->ub; a.kind = e->kindv; a.lrow = e->binfo; a.ldelta = e->bmin; a.lside = e->bmin + e->m;
-    a.st = e->st; a.m = e->m; a.ld = e->ld; a.nN = e->nN; a.nblocks = e->nblocks; a.eps = e->eps;
-    a.seq = e->dual_seq;
-    a.maxviol = e->dual_maxviol;
-    a.guard_abs = (e->cert_large && !e->guard_off) ? e->guard_abs : 0.0;
-    const dim3 g((unsigned)((e->m + UPD_ROWS - 1) / UPD_ROWS) + DFU_BOOK), b(256);
-    const int64_t nr = ((e->ld >> 1) + 255) / 256;  // double2 per thread per row
-    if (nr <= 1) hipLaunchKernelGGL((k_dual_fu<1>), g, b, 0, e->stream, a);
-    else if (nr <= 2) hipLaunchKernelGGL((k_dual_fu<2>), g, b, 0, e->stream, a);
-    else if (nr <= 4) hipLaunchKernelGGL((k_dual_fu<4>), g, b, 0, e->stream, a);
-    else hipLaunchKernelGGL((k_dual_fu<8>), g, b, 0, e->stream, a);
-    e->dual_open = true;
-}
-
-void launch_dual_iteration(ellp_engine *e) {
-    e->dual_seq += 1;
-    {
-        Prof p(e, ELLP_K_DPRICE);
-        // closes the fused iteration in front of it if this engine folds the closing work (dual_fold) — unless it
-        // returns at entry on a stop, so the host keeps dual_open until a k_dual_close has been enqueued (which does
-        // nothing on the device when the iteration is closed already)
-        launch_price<1>(e);
-    }
-    // the drift monitor compares A_B alpha_q with a_q between FTRAN and the update: those iterations keep the
-    // three-launch form (both forms leave the same state behind)
-    const bool drift_now = e->drift_every > 0 && e->since_drift + 1 >= (uint64_t)e->drift_every;
-    if (e->dual_fused && !drift_now) {
-        if (e->drift_every > 0) e->since_drift += 1;
-        launch_dual_fu(e);
-        if (!e->dual_fold) launch_dual_close(e);
-        e->since_refactor += 1;
-        e->enqueued += 1;
-        return;
-    }
-    {
-        Prof p(e, ELLP_K_FTRAN);
-        launch_ftran2<1>(e);
-    }
-    launch_drift_check(e);
-    {
-        Prof p(e, ELLP_K_DUPDATE);
-        launch_update2<1>(e, 0);
-    }
-    e->since_refactor += 1;
-    e->enqueued += 1;
-}
-
-void launch_dleave(ellp_engine *e) {
-    Prof p(e, ELLP_K_DLEAVE);
-    DLeaveArgs a{e->x, e->lb, e->ub, e->kindv, e->B_index, e->st, e->m, e->eps, e->dual_maxviol};
-    hipLaunchKernelGGL(k_dleave, dim3(1), dim3(256), 0, e->stream, a);
-}
+#include "ellp_launch.inc"
 
 ellp_status status_message(const DevState &s, char *errbuf, size_t errlen) {
     switch (s.status) {
@@ -3919,8 +3232,7 @@ void fill_stats(ellp_engine *e, ellp_stats *stats) {
     if (e->obj_fresh) {
         e->obj_fresh = false;  // ellp_engine_run computed c . x in front of the read-back this state came from
     } else if (e->kind == ELLP_ENGINE_PRIMAL && e->st) {
-        hipLaunchKernelGGL(k_primal_obj, dim3(1), dim3(1024), 0, e->stream, e->c_B, e->c_N, e->x, e->B_index,
-                           e->N_index, e->m, e->nN, e->st);
+        launch_primal_obj(e);
         double v = 0.0;
         if (hipMemcpyAsync(&v, &e->st->obj, sizeof(double), hipMemcpyDeviceToHost, e->stream) == hipSuccess &&
             hipStreamSynchronize(e->stream) == hipSuccess)
@@ -4355,8 +3667,7 @@ static ellp_status create_phase1_start(ellp_engine *e) {
     hipLaunchKernelGGL(k_phase1_art, dim3((unsigned)((e->m + 255) / 256)), dim3(256), 0, e->stream, e->tvec, e->A_B, e->x, e->B_index,
                        e->m, e->ld);
     // the carried objective (and the trace) start from c . x WITH the artificials at |b~_i|, not from the host's value
-    hipLaunchKernelGGL(k_primal_obj, dim3(1), dim3(1024), 0, e->stream, e->c_B, e->c_N, e->x, e->B_index, e->N_index, e->m, e->nN,
-                       e->st);
+    launch_primal_obj(e);
     return ELLP_OPTIMAL;
 }
 
@@ -4458,8 +3769,7 @@ static ellp_status create_initial_inverse(ellp_engine *e, char *errbuf, size_t e
             (void)hipGetLastError();  // no scratch memory: the weights stay at 1 (a reference-framework start)
         }
     }
-    HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(read_state(e));
     HIPCHK(hipGetLastError());
     prof_collect(e);
     if (e->h_st->status == ST_RUNNING) return ELLP_OPTIMAL;
@@ -4602,818 +3912,7 @@ ellp_status ellp_engine_create_primal_phase1(int64_t m, int64_t n, const double 
                               n, true);
 }
 
-// The explicit-inverse engine is about to be used on an engine that has been running k_small: build
-// B^-1 from the current A_B and leave the small path for good.
-static ellp_status ensure_inverse(ellp_engine *e, char *errbuf, size_t errlen) {
-    if (e->dual_bflip) {  // the caller must be able to tell which rule runs: the explicit-inverse engine has no long-step ratio test
-        set_err(errbuf, errlen, "ELLP_FLAG_DUAL_BOUND_FLIPPING: this call needs the explicit-inverse engine, which has no long-step ratio test");
-        return ELLP_ERR_ARG;
-    }
-    launch_flush(e);  // two-launch pipeline: B^-1 is complete only once the open iteration has been booked
-    if (e->w_valid) {
-        e->small = false;
-        return ELLP_OPTIMAL;
-    }
-    HIPCHK(hipSetDevice(e->device));
-    launch_refactor(e);
-    HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    prof_collect(e);
-    e->w_valid = true;
-    e->small = false;
-    e->need_dleave = true;
-    e->u_valid = false;
-    if (e->h_st->status != ST_RUNNING) return status_message(*e->h_st, errbuf, errlen);
-    return ELLP_OPTIMAL;
-}
-
-// one launch of the LU-per-iteration kernel of ellp_mid.inc for up to `iters` loop bodies (run_small; exact_takeover)
-static hipError_t launch_mid(ellp_engine *e, uint64_t iters, int resync) {
-    const int64_t per = (int64_t)e->nbs * e->cpb;  // layout of the pricing buffer (Xchg, one segment)
-    MidArgs a{};
-    a.A_B = e->A_B; a.A_N = e->A_N; a.A_Nt = e->A_Nt; a.c_B = e->c_B; a.c_N = e->c_N; a.x = e->x; a.y = e->y; a.dd = e->dd;
-    a.lb = e->lb; a.ub = e->ub; a.kind = e->kindv; a.B_index = e->B_index; a.N_index = e->N_index; a.Nb = e->Nb;
-    a.kbuf = e->X + 2 * e->nbs;
-    a.rbuf = e->X + 2 * e->nbs + per;
-    a.LUa = e->LUa; a.Ut = e->Ut;
-    a.st = e->st; a.m = e->m; a.ld = e->ld; a.nN = e->nN; a.ldn = e->ldn;
-    a.max_iters = iters;
-    a.nch = (int)((e->nN + 63) / 64);
-    a.eps = e->eps;
-    a.trace = Trace{e->trace_obj, e->trace_it, e->trace_len};
-    a.stamps = e->small_stamps;
-    a.maxviol = e->dual_maxviol;
-    a.bflip = e->dual_bflip;
-    a.flist = e->bf_list;
-    a.resync = resync;
-    a.b = e->b_dev;
-    // the row-major copy of A_N the pricing pass reads: made afresh at every launch (anything may have
-    // touched A_N in between: a hand-off, a sharding call, the other engine)
-    hipLaunchKernelGGL(k_mid_transpose, dim3((unsigned)((e->m + 31) / 32), (unsigned)((e->nN + 31) / 32)), dim3(256), 0,
-                       e->stream, e->A_N, e->A_Nt, e->m, e->ld, e->nN, e->ldn);
-    void *kargs[] = {&a};
-    return hipLaunchKernel(mid_kernel(e->kind, e->mid_nt), dim3(1), dim3((unsigned)e->mid_nt), kargs, e->mid_lds, e->stream);
-}
-
-// ellp_engine_run for the small path: launches of k_small, each good for up to 16384 iterations
-static ellp_status run_small(ellp_engine *e, uint64_t max_iters, char *errbuf, size_t errlen) {
-    HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->h_st->status != ST_RUNNING) return status_message(*e->h_st, errbuf, errlen);
-    const uint64_t iters0 = e->h_st->iters;
-    uint64_t remaining = max_iters;
-    const int64_t per = (int64_t)e->nbs * e->cpb;  // layout of the pricing buffer (Xchg, one segment)
-    while (remaining > 0) {
-        if (e->mid) {
-            HIPCHK(launch_mid(e, remaining < 4096 ? remaining : 4096, 0));
-        } else {
-            SmallArgs a{};
-            a.A_B = e->A_B; a.A_N = e->A_N; a.c_B = e->c_B; a.c_N = e->c_N; a.x = e->x; a.y = e->y; a.dd = e->dd;
-            a.lb = e->lb; a.ub = e->ub; a.kind = e->kindv; a.B_index = e->B_index; a.N_index = e->N_index; a.Nb = e->Nb;
-            a.kbuf = e->X + 2 * e->nbs;
-            a.rbuf = e->X + 2 * e->nbs + per;
-            a.st = e->st; a.m = e->m; a.ld = e->ld; a.nN = e->nN;
-            a.max_iters = remaining < 16384 ? remaining : 16384;
-            a.nch = (int)((e->nN + 63) / 64);
-            a.eps = e->eps;
-            a.trace = Trace{e->trace_obj, e->trace_it, e->trace_len};
-            a.stamps = e->small_stamps;
-            a.maxviol = e->dual_maxviol;
-            a.bflip = e->dual_bflip;
-            a.flist = e->bf_list;
-            void *kargs[] = {&a};
-            HIPCHK(hipLaunchKernel(small_kernel(e->kind, e->small_nt), dim3(1), dim3((unsigned)e->small_nt), kargs,
-                                   e->small_lds, e->stream));
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        e->refactors = e->h_st->iters;  // one LU per loop body, as the reference
-        if (e->h_st->status != ST_RUNNING) return status_message(*e->h_st, errbuf, errlen);
-        const uint64_t done = e->h_st->iters - iters0;
-        remaining = done < max_iters ? max_iters - done : 0;
-    }
-    return ELLP_MAXITER;
-}
-
-double ellp_engine_refresh(ellp_engine *e) {
-    if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
-    if (!e) return NAN;
-    if (hipSetDevice(e->device) != hipSuccess) return NAN;
-    if (ensure_inverse(e, nullptr, 0) != ELLP_OPTIMAL) return NAN;
-    launch_refresh(e);
-    if (hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream) != hipSuccess) return NAN;
-    if (hipStreamSynchronize(e->stream) != hipSuccess) return NAN;
-    prof_collect(e);
-    const double res = e->h_st->resid;
-    e->last_residual = res;
-    if (e->h_st->need_rebuild) {  // an explicit refresh that was refused changes nothing and stops nothing
-        const int32_t zero = 0;
-        (void)hipMemcpyAsync(&e->st->need_rebuild, &zero, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-        (void)hipMemcpyAsync(&e->st->tiny, &zero, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-        (void)hipStreamSynchronize(e->stream);
-        e->h_st->need_rebuild = 0;
-        e->h_st->tiny = 0;
-    }
-    return res;
-}
-
-ellp_status ellp_engine_refactor(ellp_engine *e, char *errbuf, size_t errlen) {
-    if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
-    if (!e) return ELLP_ERR_ARG;
-    HIPCHK(hipSetDevice(e->device));
-    e->w_valid = true;  // about to be
-    e->small = false;
-    e->need_dleave = true;
-    launch_flush(e);
-    launch_refactor(e);
-    HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    prof_collect(e);
-    if (e->h_st->status != ST_RUNNING) return status_message(*e->h_st, errbuf, errlen);
-    return ELLP_OPTIMAL;
-}
-
-static ellp_status run_colsharded(ellp_engine *e, uint64_t max_iters, ellp_stats *stats, char *errbuf, size_t errlen);
-
-// ---- "certify or redo" (certified hybrid): the start of a phase is kept on the host; a solve that ends Optimal on a point
-// that violates an invariant of the reference's loop (see k_invariants) is repeated from that start by the exact kernel
-static hipError_t take_snapshot(ellp_engine *e) {
-    auto &sn = e->snap;
-    const size_t m = (size_t)e->m, nN = (size_t)e->nN, n_c = (size_t)e->n_c;
-    sn.x.resize(n_c); sn.B.resize(m); sn.N.resize(nN); sn.Nb.resize(nN); sn.c_B.resize(m); sn.c_N.resize(nN);
-    hipError_t rc;
-#define SNAP(dst, src, bytes) if ((rc = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream)) != hipSuccess) return rc
-    SNAP(sn.x.data(), e->x, 8 * n_c);
-    SNAP(sn.B.data(), e->B_index, 8 * m);
-    SNAP(sn.N.data(), e->N_index, 8 * nN);
-    SNAP(sn.Nb.data(), e->Nb, nN);
-    SNAP(sn.c_B.data(), e->c_B, 8 * m);
-    SNAP(sn.c_N.data(), e->c_N, 8 * nN);
-    if (e->kind == ELLP_ENGINE_DUAL) {
-        sn.y.resize(m); sn.d.resize(n_c);
-        SNAP(sn.y.data(), e->y, 8 * m);
-        SNAP(sn.d.data(), e->dd, 8 * n_c);
-    }
-    SNAP(&sn.obj, &e->st->obj, sizeof(double));
-#undef SNAP
-    if ((rc = hipStreamSynchronize(e->stream)) != hipSuccess) return rc;
-    sn.valid = true;
-    return hipSuccess;
-}
-
-// true if the end point keeps the invariants of the reference's loop to within EPS (or cannot be examined)
-static bool end_point_ok(ellp_engine *e, double *detail3) {
-    if (!e->inv_out && dmalloc(e, &e->inv_out, 4) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;
-    }
-    InvArgs a{e->x, e->lb, e->ub, e->b_dev, e->y, e->dd, e->kindv, e->Nb, e->N_index, e->m, e->n_c, e->nN,
-              e->kind == ELLP_ENGINE_DUAL ? 1 : 0, e->inv_out};
-    hipLaunchKernelGGL(k_invariants, dim3(1), dim3(1024), 0, e->stream, a);
-    double out[3] = {0.0, 0.0, 0.0};
-    if (hipMemcpyAsync(out, e->inv_out, sizeof(out), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-        hipStreamSynchronize(e->stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return true;
-    }
-    if (detail3) { detail3[0] = out[0]; detail3[1] = out[1]; detail3[2] = out[2]; }
-    if (e->kind == ELLP_ENGINE_PRIMAL) return out[0] <= e->eps;
-    if (!(out[1] <= e->eps)) return false;
-    // a box problem's dual objective (= minus the original problem's dual infeasibility, the number the caller tests against
-    // EPS, dual…:45-50) that lies BELOW -EPS but within what the drift of the carried d can produce: the exact loop decides
-    if (e->box_problem && out[2] <= -e->eps && out[2] > -1e-6) return false;
-    return true;
-}
-
-// back to the start of the phase, and from now on the LU-per-iteration kernel alone (ellp_mid.inc; `large`: run_exact_large)
-static ellp_status redo_from_snapshot(ellp_engine *e, bool large, char *errbuf, size_t errlen) {
-    const auto &sn = e->snap;
-    const int64_t m = e->m, nN = e->nN, ld = e->ld;
-    std::vector<int64_t> B((size_t)m), N((size_t)nN), where((size_t)e->n, INT64_MIN), src((size_t)(m + nN));
-    HIPCHK(hipMemcpy(B.data(), e->B_index, 8 * (size_t)m, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(N.data(), e->N_index, 8 * (size_t)nN, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < m; ++i) where[(size_t)B[(size_t)i]] = i;
-    for (int64_t j = 0; j < nN; ++j) where[(size_t)N[(size_t)j]] = -1 - j;
-    for (int64_t i = 0; i < m; ++i) src[(size_t)i] = where[(size_t)sn.B[(size_t)i]];
-    for (int64_t j = 0; j < nN; ++j) src[(size_t)(m + j)] = where[(size_t)sn.N[(size_t)j]];
-    for (int64_t k = 0; k < m + nN; ++k)
-        if (src[(size_t)k] == INT64_MIN) {
-            set_err(errbuf, errlen, "redo: the index sets of the snapshot and of the engine differ");
-            return ELLP_ERR_PANIC;
-        }
-    double *A2 = nullptr;
-    int64_t *src_dev = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&A2), sizeof(double) * (size_t)(ld * (m + nN))));
-    hipError_t rc = hipMalloc(reinterpret_cast<void **>(&src_dev), 8 * (size_t)(m + nN));
-    if (rc != hipSuccess) { (void)hipFree(A2); HIPCHK(rc); }
-    auto done = [&](hipError_t err) {
-        (void)hipStreamSynchronize(e->stream);
-        (void)hipFree(A2);
-        (void)hipFree(src_dev);
-        return err;
-    };
-#define RCHK(expr) do { hipError_t _r = (expr); if (_r != hipSuccess) { HIPCHK(done(_r)); } } while (0)
-    RCHK(hipMemcpyAsync(src_dev, src.data(), 8 * (size_t)(m + nN), hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_restore_cols, dim3((unsigned)(m + nN)), dim3(256), 0, e->stream, e->A_B, e->A_N, src_dev, A2, ld);
-    RCHK(hipMemcpyAsync(e->A_B, A2, sizeof(double) * (size_t)(ld * m), hipMemcpyDeviceToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->A_N, A2 + ld * m, sizeof(double) * (size_t)(ld * nN), hipMemcpyDeviceToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->x, sn.x.data(), 8 * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->B_index, sn.B.data(), 8 * (size_t)m, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->N_index, sn.N.data(), 8 * (size_t)nN, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->Nb, sn.Nb.data(), (size_t)nN, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->c_B, sn.c_B.data(), 8 * (size_t)m, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->c_N, sn.c_N.data(), 8 * (size_t)nN, hipMemcpyHostToDevice, e->stream));
-    if (e->kind == ELLP_ENGINE_DUAL) {
-        RCHK(hipMemcpyAsync(e->y, sn.y.data(), 8 * (size_t)m, hipMemcpyHostToDevice, e->stream));
-        RCHK(hipMemcpyAsync(e->dd, sn.d.data(), 8 * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream));
-    }
-    DevState ns = *e->h_st;
-    ns.status = ST_RUNNING;
-    ns.nan_flag = 0; ns.tiny = 0; ns.tiny_p = 0; ns.fin = 0; ns.need_rebuild = 0; ns.panic_code = 0; ns.open = 0;
-    ns.pe_valid = 0; ns.mv_pending = 0; ns.se_valid = 0;
-    ns.iters = ns.pivots = ns.flips = 0;
-    ns.lambda = 0.0;
-    ns.obj = sn.obj;
-    ns.lr = -1;
-    *e->h_st = ns;
-    RCHK(hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream));
-    if (e->trace_len > 0) RCHK(hipMemsetAsync(e->trace_it, 0, sizeof(unsigned long long) * (size_t)e->trace_len, e->stream));
-    RCHK(done(hipSuccess));
-#undef RCHK
-    if (large) {
-        // above 1,024 rows the exact loop is run_exact_large; the explicit inverse follows the restored basis (the exact
-        // iterations keep updating it, and the next phase's fast loop starts from it)
-        e->exact_large_only = true;
-        launch_refactor(e);
-        HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        prof_collect(e);
-        e->hy_rebuilds += 1;
-        if (e->h_st->status != ST_RUNNING) return status_message(*e->h_st, errbuf, errlen);
-    } else {
-        e->hybrid = false;
-        e->small = true;
-        e->mid = true;
-        e->w_valid = false;
-        e->lagged = false;
-        e->dual_fused = e->dual_fold = false;
-    }
-    e->lag_open = e->dual_open = false;
-    e->u_valid = false;
-    e->need_dleave = true;
-    e->maint_chain = 0;
-    e->enqueued = 0;
-    e->iters_seen = 0;
-    e->since_refactor = e->since_btran = e->since_drift = 0;
-    e->hy_redos += 1;
-    return ELLP_OPTIMAL;
-}
-
-// One iteration with u / rho and B^-1 a_q from a fresh LU of the CURRENT basis (ellp_exact.inc), enqueued; the state is complete
-// afterwards.  The workspace must be there (exact_workspace) and the caller has switched the pivot guard off (guard_off).
-static void enqueue_exact_iteration(ellp_engine *e) {
-    const int64_t m = e->m, ld = e->ld;
-    const unsigned gm = (unsigned)((m + 255) / 256), gld = (unsigned)((ld + 255) / 256);
-    const size_t lds0 = sizeof(double) * (size_t)m, lds1 = 2 * sizeof(double) * (size_t)m;
-    const bool was_lagged = e->lagged, was_fused = e->dual_fused, was_fold = e->dual_fold;
-        hipLaunchKernelGGL(k_rows_from_cols, dim3((unsigned)((m + 31) / 32), (unsigned)((m + 31) / 32)), dim3(256), 0, e->stream, e->A_B, e->luw.M, m, ld);
-        ellp_lu_rows_factor(&e->luw, e->stream);
-        if (e->kind == ELLP_ENGINE_PRIMAL) {
-            hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds1, e->stream, e->luw.M, e->luw.piv, m, e->c_B, e->ex_sol, 1, e->ex_fail);
-            hipLaunchKernelGGL(k_exact_put_u, dim3(gld), dim3(256), 0, e->stream, e->ex_sol, e->u, m, ld, e->ex_fail);
-            e->lagged = false;
-            launch_price<0>(e);
-            launch_ftran2<0>(e);
-            hipLaunchKernelGGL(k_exact_gather_aq, dim3(gm), dim3(256), 0, e->stream, e->A_N, e->st, m, ld, e->ex_rhs);
-            hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds0, e->stream, e->luw.M, e->luw.piv, m, e->ex_rhs, e->ex_sol, 0, e->ex_fail);
-            ExactLamArgs la{e->ex_sol, e->d, e->lam, e->bidx, e->dpos, e->B_index, e->x, e->lb, e->ub, e->kindv, e->st, m, e->eps, e->ex_fail};
-            hipLaunchKernelGGL(k_exact_relam, dim3(gm), dim3(256), 0, e->stream, la);
-            launch_update2<0>(e, 1);
-            e->lagged = was_lagged;
-        } else {
-            // x_B = A_B^-1 (b - A_N x_N) from the LU (the kernels of launch_resync form the right-hand side)
-            ResyncArgs ra{e->A_N, e->W, e->W2, e->b_dev, e->x, e->xg, e->tvec, e->upart, e->cand, e->maxbits, e->B_index,
-                          e->N_index, e->st, e->m, e->ld, e->nN, 0, e->btran_tiles, 1};
-            ra.cols_per_tile = (int)((e->nN + e->btran_tiles - 1) / e->btran_tiles);
-            const int64_t half = ld >> 1;
-            hipLaunchKernelGGL(k_resync_gather, dim3((unsigned)((e->nN + 255) / 256)), dim3(256), 0, e->stream, ra);
-            hipLaunchKernelGGL(k_resync_part, dim3((unsigned)((half + 255) / 256), (unsigned)e->btran_tiles), dim3(256), 0, e->stream, ra);
-            hipLaunchKernelGGL(k_resync_rhs, dim3(gld), dim3(256), 0, e->stream, ra);
-            hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds0, e->stream, e->luw.M, e->luw.piv, m, e->tvec, e->cand, 0, e->ex_fail);
-            hipLaunchKernelGGL(k_resync_apply, dim3(gm), dim3(256), 0, e->stream, ra);
-            launch_dleave(e);
-            hipLaunchKernelGGL(k_exact_unit, dim3(gm), dim3(256), 0, e->stream, e->ex_rhs, m, e->st);
-            hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds1, e->stream, e->luw.M, e->luw.piv, m, e->ex_rhs, e->ex_rho, 1, e->ex_fail);
-            e->dual_fused = e->dual_fold = false;
-            e->price_rho_ovr = e->ex_rho;
-            e->dual_seq += 1;
-            launch_price<1>(e);
-            launch_ftran2<1>(e);
-            hipLaunchKernelGGL(k_exact_gather_aq, dim3(gm), dim3(256), 0, e->stream, e->A_N, e->st, m, ld, e->ex_rhs);
-            hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds0, e->stream, e->luw.M, e->luw.piv, m, e->ex_rhs, e->ex_sol, 0, e->ex_fail);
-            hipLaunchKernelGGL(k_exact_copy, dim3(gm), dim3(256), 0, e->stream, e->ex_sol, e->d, m, e->st, e->ex_fail);
-            launch_update2<1>(e, 0);
-            e->price_rho_ovr = nullptr;
-            e->dual_fused = was_fused;
-            e->dual_fold = was_fold;
-        }
-}
-
-// the LU workspace and the vectors of the exact iteration (allocated at the first use)
-static hipError_t exact_workspace(ellp_engine *e) {
-    if (e->luw_ready) return hipSuccess;
-    const int64_t m = e->m, ld = e->ld;
-    hipError_t rc;
-    if ((rc = ellp_lu_rows_alloc(&e->luw, m)) != hipSuccess) {
-        ellp_lu_rows_free(&e->luw);
-        (void)hipGetLastError();
-        return rc;
-    }
-    e->luw_ready = true;
-    if ((rc = dmalloc(e, &e->ex_rhs, (size_t)ld)) != hipSuccess) return rc;
-    if ((rc = dmalloc(e, &e->ex_sol, (size_t)ld)) != hipSuccess) return rc;
-    if ((rc = dmalloc(e, &e->ex_rho, (size_t)ld)) != hipSuccess) return rc;
-    if ((rc = dmalloc(e, &e->ex_fail, 4)) != hipSuccess) return rc;
-    (void)hipMemsetAsync(e->ex_rho, 0, sizeof(double) * (size_t)ld, e->stream);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lu_solve), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16 * m));
-    return hipSuccess;
-}
-
-// "certify or redo" above 1,024 rows: after a redo every loop body runs on a fresh LU (ellp_engine::exact_large_only) — the
-// reference's LU-per-iteration loop on all CUs instead of in one workgroup: a blocked LU (2 ceil(m / 16) launches, ellp_lu.hip) and
-// two (primal) / three (dual) solves per iteration; the explicit inverse is still updated along (a later phase goes back to
-// the fast loop).  With pipeline 3 (ellp_engine::exact_large_always) this loop is the engine, from the first slice on.
-static ellp_status run_exact_large(ellp_engine *e, uint64_t max_iters, char *errbuf, size_t errlen) {
-    HIPCHK(exact_workspace(e));
-    HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->h_st->status != ST_RUNNING) return status_message(*e->h_st, errbuf, errlen);
-    const uint64_t iters0 = e->h_st->iters;
-    e->lag_open = e->dual_open = false;
-    e->guard_off = true;
-    ellp_status result = ELLP_MAXITER;
-    while (e->h_st->iters - iters0 < max_iters) {
-        HIPCHK(hipMemsetAsync(e->ex_fail, 0, sizeof(int), e->stream));
-        enqueue_exact_iteration(e);
-        int failed = 0;
-        HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipMemcpyAsync(&failed, e->ex_fail, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        HIPCHK(hipGetLastError());
-        prof_collect(e);
-        if (failed) {  // a zero on U's diagonal: the reference's unwrap() on None in BTRAN / FTRAN
-            set_err(errbuf, errlen, "unwrap() on None: the basis is exactly singular");
-            result = ELLP_ERR_PANIC;
-            break;
-        }
-        if (e->h_st->tiny) {  // raised by the update kernel for the explicit inverse's sake: nothing to maintain here
-            static const int32_t zero = 0;
-            (void)hipMemcpyAsync(&e->st->tiny, &zero, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-            e->h_st->tiny = 0;
-        }
-        if (e->h_st->status != ST_RUNNING) {
-            result = status_message(*e->h_st, errbuf, errlen);
-            break;
-        }
-    }
-    e->guard_off = false;
-    e->u_valid = false;
-    e->enqueued = 0;
-    e->iters_seen = e->h_st->iters;
-    e->hy_exact_iters += e->h_st->iters - iters0;
-    e->need_dleave = true;
-    if (result != ELLP_MAXITER && e->h_st->status != ST_RUNNING) {
-        // the solve has ended: the explicit inverse, updated along through pivots no guard has looked at, is rebuilt from
-        // the final basis (a phase hand-off and the dual point of read_point read it)
-        static const int32_t running = ST_RUNNING;
-        static int32_t keep;
-        keep = e->h_st->status;
-        (void)hipMemcpyAsync(&e->st->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-        launch_refactor(e);
-        e->hy_rebuilds += 1;
-        DevState after;
-        HIPCHK(hipMemcpyAsync(&after, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        prof_collect(e);
-        if (after.status != ST_RUNNING) e->w_valid = false;
-        e->h_st->cur = after.cur;
-        (void)hipMemcpyAsync(&e->st->status, &keep, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-        (void)hipMemcpyAsync(&e->st->panic_code, &e->h_st->panic_code, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-        (void)hipStreamSynchronize(e->stream);
-    }
-    return result;
-}
-
-// The certificate above 1,024 rows (ellp_exact.inc): the explicit-inverse loop has reported a terminal status; one iteration
-// is run with u / rho and d = B^-1 a_q from a fresh LU of the basis (dual: x_B recomputed from it first).  Returns as
-// exact_takeover does.
-static int exact_certify_large(ellp_engine *e, uint64_t remaining, ellp_status *result, char *errbuf, size_t errlen) {
-    const int s = e->h_st->status;
-    const bool guard = s == ST_NEED_EXACT;  // a refused pivot: nothing of that iteration is committed or counted
-    if (!(guard || s == ELLP_OPTIMAL || s == ELLP_INFEASIBLE || s == ELLP_UNBOUNDED)) return 0;
-    if (guard && remaining == 0) return 0;  // the slice is used up: the next one starts here
-    if (!guard) remaining += 1;  // the loop body that found the status is examined again, not counted twice
-    auto fail = [&](hipError_t rc) {
-        set_err(errbuf, errlen, "HIP error %s in the certificate of the terminal status", hipGetErrorString(rc));
-        *result = ELLP_ERR_DEVICE;
-        return 2;
-    };
-    hipError_t rc;
-    if ((rc = exact_workspace(e)) != hipSuccess) {
-        e->cert_large = false;  // no memory for the factors: the status goes out uncertified
-        e->hy_uncertified += 1;
-        return 0;
-    }
-    // re-arm: the state is complete (a status found by k_ftran_eta comes with that pass's eta update done; one found by a
-    // ratio-test fold comes before anything of its iteration is committed); the loop body that found it is not counted twice
-    DevState ns = *e->h_st;
-    ns.status = ST_RUNNING;
-    ns.nan_flag = 0; ns.tiny = 0; ns.tiny_p = 0; ns.fin = 0; ns.need_rebuild = 0; ns.panic_code = 0;
-    ns.open = 0; ns.pe_valid = 0; ns.mv_pending = 0; ns.usel = 0; ns.usel_next = 0;
-    if (!guard && ns.iters > 0) ns.iters -= 1;
-    *e->h_st = ns;
-    if ((rc = hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream)) != hipSuccess) return fail(rc);
-    if ((rc = hipMemsetAsync(e->ex_fail, 0, sizeof(int), e->stream)) != hipSuccess) return fail(rc);
-    e->guard_off = true;
-    e->lag_open = false;
-    e->dual_open = false;
-    // the first iteration examines the status; if it does NOT confirm it (it pivots), up to exact_K - 1 more follow before the
-    // explicit-inverse loop takes over again — the policy of the certified hybrid (oracle/ellp_oracle.c, hybrid_run)
-    int failed = 0;
-    uint64_t ran = 0;
-    int s_first = ST_RUNNING;
-    for (int k = 0; k < e->exact_K; ++k) {
-        enqueue_exact_iteration(e);
-        if ((rc = hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream)) != hipSuccess) return fail(rc);
-        if ((rc = hipMemcpyAsync(&failed, e->ex_fail, sizeof(int), hipMemcpyDeviceToHost, e->stream)) != hipSuccess) return fail(rc);
-        if ((rc = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(rc);
-        if ((rc = hipGetLastError()) != hipSuccess) return fail(rc);
-        ran += 1;
-        if (k == 0) s_first = e->h_st->status;
-        if (e->h_st->status != ST_RUNNING || e->h_st->tiny || failed) break;
-        if (ran >= remaining) break;  // the caller's budget
-    }
-    e->guard_off = false;
-    prof_collect(e);
-    const int s2 = e->h_st->status;
-    e->hy_exact_iters += ran;
-    if (failed) e->hy_uncertified += 1;  // an exactly singular basis: the iteration ran on the explicit inverse's numbers
-    if (guard) e->hy_guards += 1;
-    else {
-        e->hy_certs += 1;
-        if (s_first != s) e->hy_disagree += 1;
-    }
-    if (getenv("ELLP_HYBRID_DEBUG"))
-        fprintf(stderr, "ellp hybrid: fast status %d at iteration %llu -> exact-LU iteration, status %d%s\n", s,
-                (unsigned long long)ns.iters, s2, failed ? " (LU singular: not certified)" : "");
-    e->u_valid = false;
-    e->since_btran = 0;
-    e->maint_chain = 0;
-    e->enqueued = 0;
-    e->iters_seen = e->h_st->iters;
-    e->need_dleave = false;
-    if (s2 == ST_RUNNING && !e->h_st->tiny) return 1;
-    if (s2 == ST_RUNNING) return 1;  // a maintenance request raised by the iteration: the run loop services it
-    *result = status_message(*e->h_st, errbuf, errlen);
-    return 2;
-}
-
-// Certified hybrid (restated in oracle/ellp_oracle.c, hybrid_run): the explicit-inverse loop has stopped — on a guarded
-// pivot (ST_NEED_EXACT: nothing of that iteration is committed), on a terminal status, or on an error of its own arithmetic
-// (singular rebuild, NaN, an assertion of the reference).  h_st is the drained device state.  The LU-per-iteration kernel
-// (k_mid: the reference's arithmetic on a fresh factorisation, primal…:173-189,289-292,404-406; dual…:241-246,281-284)
-// runs up to exact_K loop bodies from the same arrays; dual engines recompute x_B = A_B^-1 (b - A_N x_N) from that LU
-// first.  The loop body in which a terminal status was found is examined again, not counted twice.
-// Returns 0: nothing to do; 1: the loop goes on (status RUNNING, B^-1 rebuilt from the basis k_mid left);
-// 2: the solve has ended, *result holds the status k_mid found (certified, or corrected).
-static int exact_takeover(ellp_engine *e, uint64_t remaining, ellp_status *result, char *errbuf, size_t errlen) {
-    if (e->cert_large && e->world == 1 && !e->colshard) return exact_certify_large(e, remaining, result, errbuf, errlen);
-    if (!e->hybrid || e->world != 1 || e->colshard) return 0;
-    const int s = e->h_st->status;
-    const bool guard = s == ST_NEED_EXACT;
-    const bool terminal = s == ELLP_OPTIMAL || s == ELLP_INFEASIBLE || s == ELLP_UNBOUNDED;
-    const bool failed = s == ELLP_ERR_SINGULAR || s == ELLP_ERR_NAN || s == ELLP_ERR_PANIC;
-    if (!guard && !terminal && !failed) return 0;
-    DevState ns = *e->h_st;
-    uint64_t budget = remaining;
-    if (terminal && ns.iters > 0) {
-        ns.iters -= 1;
-        budget += 1;
-    }
-    if (budget == 0) return 0;  // a guarded pivot at the very end of the caller's slice: the next slice starts here
-    ns.status = ST_RUNNING;
-    ns.nan_flag = 0;
-    ns.tiny = 0;
-    ns.tiny_p = 0;
-    ns.fin = 0;
-    ns.need_rebuild = 0;
-    ns.panic_code = 0;
-    auto fail = [&](hipError_t rc) {
-        set_err(errbuf, errlen, "HIP error %s in the hand-over to the exact kernel", hipGetErrorString(rc));
-        *result = ELLP_ERR_DEVICE;
-        return 2;
-    };
-    hipError_t rc;
-    *e->h_st = ns;
-    if ((rc = hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream)) != hipSuccess) return fail(rc);
-    const uint64_t K = budget < (uint64_t)e->exact_K ? budget : (uint64_t)e->exact_K;
-    static const int dual_resync = [] {  // diagnostics: ELLP_HYBRID_RESYNC = 1 (default) recomputes x_B only, 2 x_B, y and d
-        const char *v = getenv("ELLP_HYBRID_RESYNC");
-        return v && v[0] ? atoi(v) : 1;
-    }();
-    if ((rc = launch_mid(e, K, e->kind == ELLP_ENGINE_DUAL ? dual_resync : 0)) != hipSuccess) return fail(rc);
-    if ((rc = hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream)) != hipSuccess) return fail(rc);
-    if ((rc = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(rc);
-    const uint64_t did = e->h_st->iters - ns.iters;
-    const int s2 = e->h_st->status;
-    e->hy_exact_iters += did;
-    if (guard) e->hy_guards += 1;
-    else {
-        e->hy_certs += 1;
-        if (!(s2 == s && did <= 1)) e->hy_disagree += 1;
-    }
-    if (getenv("ELLP_HYBRID_DEBUG"))
-        fprintf(stderr, "ellp hybrid: fast status %d at iteration %llu -> exact kernel, %llu iterations, status %d\n", s,
-                (unsigned long long)ns.iters, (unsigned long long)did, s2);
-    e->u_valid = false;
-    e->since_btran = 0;
-    e->maint_chain = 0;
-    e->enqueued = 0;
-    e->iters_seen = e->h_st->iters;
-    if (e->h_st->pivots != ns.pivots || failed) {
-        // the explicit inverse follows the basis (also when the solve has ended: a phase hand-off reads it)
-        static const int32_t running = ST_RUNNING;
-        if (s2 != ST_RUNNING) (void)hipMemcpyAsync(&e->st->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-        launch_refactor(e);
-        e->hy_rebuilds += 1;
-        DevState after;
-        if ((rc = hipMemcpyAsync(&after, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream)) != hipSuccess) return fail(rc);
-        if ((rc = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(rc);
-        prof_collect(e);
-        if (after.status != ST_RUNNING) {
-            if (s2 == ST_RUNNING) {  // the basis the exact kernel left fails the rebuild's guard: that is the loop's next LU
-                *e->h_st = after;
-                *result = status_message(after, errbuf, errlen);
-                return 2;
-            }
-            e->w_valid = false;
-        }
-        e->h_st->cur = after.cur;
-        if (s2 != ST_RUNNING) {
-            static int32_t keep;
-            keep = s2;
-            (void)hipMemcpyAsync(&e->st->status, &keep, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-            (void)hipMemcpyAsync(&e->st->panic_code, &e->h_st->panic_code, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
-            (void)hipStreamSynchronize(e->stream);
-        }
-    }
-    if (s2 == ST_RUNNING) {
-        if (e->kind == ELLP_ENGINE_DUAL) launch_dleave(e);  // the three-launch loop starts from DevState::lr
-        return 1;
-    }
-    *result = status_message(*e->h_st, errbuf, errlen);
-    return 2;
-}
-
-ellp_status ellp_engine_run(ellp_engine *e, uint64_t max_iters, ellp_stats *stats, char *errbuf, size_t errlen) {
-    if (!e) return ELLP_ERR_ARG;
-    if (errbuf && errlen) errbuf[0] = 0;
-    HIPCHK(hipSetDevice(e->device));
-    e->obj_fresh = false;
-    auto t0 = std::chrono::steady_clock::now();
-    const uint64_t poll = e->opts.poll_interval > 0 ? (uint64_t)e->opts.poll_interval : (e->m <= 256 ? 64 : 16);
-    int64_t period = e->refactor_period;
-    if (period <= 0) period = default_period(e->m, e->ld, e->nN);
-    ellp_status result = ELLP_MAXITER;
-    if ((e->hybrid || e->cert_large) && !e->snap.valid && e->world == 1 && !e->colshard && e->nN > 0 && getenv("ELLP_NO_REDO") == nullptr) {
-        launch_flush(e);
-        HIPCHK(take_snapshot(e));  // the start of the phase (certify or redo, see end_point_ok)
-    }
-    if (e->nN == 0) {
-        result = ELLP_OPTIMAL;  // primal…:149-151 / dual…:175-177
-    } else if (e->small && e->world == 1) {
-        result = run_small(e, max_iters, errbuf, errlen);
-    } else if (e->exact_large_only && e->world == 1 && !e->colshard) {
-        result = run_exact_large(e, max_iters, errbuf, errlen);
-    } else {
-        uint64_t remaining = max_iters;
-        if (e->colshard) return run_colsharded(e, max_iters, stats, errbuf, errlen);
-        if (e->world != 1) {
-            set_err(errbuf, errlen, "a sharded engine is driven with ellp_engine_step + an all-gather (ellp_amd/dist.py)");
-            return ELLP_ERR_ARG;
-        }
-        if (e->kind == ELLP_ENGINE_DUAL && remaining > 0 && e->need_dleave) {
-            launch_dleave(e);
-            e->need_dleave = false;
-        }
-        // a previous slice may already have terminated (h_st is current if the previous call was a run that read it)
-        if (!e->hst_fresh) {
-            HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-        }
-        e->hst_fresh = false;
-        reconcile_counters(e);
-        adopt_fin(e);
-        const uint64_t iters0 = e->h_st->iters;
-        if (e->h_st->status == ST_NEED_EXACT && remaining > 0) {  // a guarded pivot closed the previous slice
-            const int tk = exact_takeover(e, remaining, &result, errbuf, errlen);
-            const uint64_t done0 = e->h_st->iters - iters0;
-            remaining = (tk == 2 || done0 >= max_iters) ? 0 : max_iters - done0;
-        } else if (e->h_st->status == ST_NEED_EXACT) {
-            remaining = 0;  // nothing to run: the status stays for the next slice
-        } else if (e->h_st->status != ST_RUNNING) {
-            result = status_message(*e->h_st, errbuf, errlen);
-            remaining = 0;
-        }
-        const bool can_look_ahead = e->ill_tol <= 0.0 && !e->opts.profile;
-        while (remaining > 0 && result == ELLP_MAXITER) {
-            // Look-ahead polling (no tiny-pivot maintenance, no profiling, no follow-up refresh due):
-            // batch k+1 is enqueued BEFORE the host waits for the status of batch k, so the stream never
-            // drains while the host looks at a read-back.  A batch enqueued after termination — or after a
-            // maintenance request of the drift monitor — is a few no-op launches (every kernel returns at
-            // once when status != RUNNING).  Iterations are counted on the device afterwards.
-            if (can_look_ahead && e->maint_chain == 0) {
-                if (!e->look_ev[0]) {
-                    HIPCHK(hipEventCreateWithFlags(&e->look_ev[0], hipEventDisableTiming));
-                    HIPCHK(hipEventCreateWithFlags(&e->look_ev[1], hipEventDisableTiming));
-                }
-                const uint64_t lpoll = e->opts.poll_interval > 0 ? (uint64_t)e->opts.poll_interval : 64;
-                bool pending[2] = {false, false};
-                bool stop = false;
-                int slot = 0, last_slot = -1, waited_slot = -1;
-                bool last_is_final = false;
-                uint64_t to_launch = remaining;
-                while (!stop) {
-                    if (to_launch > 0) {
-                        const uint64_t batch = to_launch < lpoll ? to_launch : lpoll;
-                        for (uint64_t it = 0; it < batch; ++it) {
-                            if (e->since_refactor >= (uint64_t)period) maintain_inverse(e);
-                            if (e->kind == ELLP_ENGINE_PRIMAL) launch_primal_iteration(e);
-                            else launch_dual_iteration(e);
-                        }
-                        to_launch -= batch;
-                        launch_dual_close(e);  // a batch ends on a complete state (a fused dual iteration may be open)
-                        if (to_launch == 0 && e->kind == ELLP_ENGINE_PRIMAL) {
-                            // the objective ellp_stats reports (c . x) rides on the last read-back instead of costing a
-                            // launch and a synchronisation of its own after the loop (fill_stats)
-                            hipLaunchKernelGGL(k_primal_obj, dim3(1), dim3(1024), 0, e->stream, e->c_B, e->c_N, e->x, e->B_index,
-                                               e->N_index, e->m, e->nN, e->st);
-                        }
-                        HIPCHK(hipMemcpyAsync(&e->h_look[slot], e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-                        HIPCHK(hipEventRecord(e->look_ev[slot], e->stream));
-                        pending[slot] = true;
-                        last_slot = slot;
-                        last_is_final = to_launch == 0;
-                    }
-                    const int other = slot ^ 1;
-                    const int wait_on = pending[other] ? other : (to_launch == 0 && pending[slot] ? slot : -1);
-                    if (wait_on >= 0) {
-                        HIPCHK(hipEventSynchronize(e->look_ev[wait_on]));
-                        pending[wait_on] = false;
-                        waited_slot = wait_on;
-                        if (e->h_look[wait_on].status != ST_RUNNING || e->h_look[wait_on].tiny || e->h_look[wait_on].fin) stop = true;
-                    }
-                    if (to_launch == 0 && !pending[0] && !pending[1]) break;
-                    slot ^= 1;
-                }
-                if (last_is_final && waited_slot == last_slot && !pending[0] && !pending[1]) {
-                    // the read-back just waited for came behind everything that was enqueued: it IS the final state
-                    *e->h_st = e->h_look[last_slot];
-                    e->obj_fresh = e->kind == ELLP_ENGINE_PRIMAL;
-                } else {
-                    HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-                    HIPCHK(hipStreamSynchronize(e->stream));
-                }
-                HIPCHK(hipGetLastError());
-                reconcile_counters(e);
-                adopt_fin(e);
-                if (getenv("ELLP_RUN_DEBUG"))
-                    fprintf(stderr, "ellp run (look-ahead): status %d iters %llu tiny %d fin %d need_rebuild %d lr %lld obj %.17g\n", e->h_st->status,
-                            (unsigned long long)e->h_st->iters, e->h_st->tiny, e->h_st->fin, e->h_st->need_rebuild, (long long)e->h_st->lr, e->h_st->obj);
-                const uint64_t done = e->h_st->iters - iters0;
-                remaining = done < max_iters ? max_iters - done : 0;
-                if (service_maintenance_request(e)) continue;  // refreshed; the follow-up runs in the loop below
-                if (e->h_st->status != ST_RUNNING) {
-                    const int tk = exact_takeover(e, remaining, &result, errbuf, errlen);
-                    if (tk == 1) {
-                        const uint64_t done2 = e->h_st->iters - iters0;
-                        remaining = done2 < max_iters ? max_iters - done2 : 0;
-                    } else if (tk == 0) {
-                        if (e->h_st->status == ST_NEED_EXACT) break;  // the slice is used up: the next one starts with the hand-over
-                        result = status_message(*e->h_st, errbuf, errlen);
-                    }
-                }
-                continue;
-            }
-            const bool chained = e->maint_chain > 0;
-            const uint64_t batch = chained ? 1 : (remaining < poll ? remaining : poll);
-            for (uint64_t it = 0; it < batch; ++it) {
-                if (e->since_refactor >= (uint64_t)period) maintain_inverse(e);
-                if (e->kind == ELLP_ENGINE_PRIMAL) launch_primal_iteration(e);
-                else launch_dual_iteration(e);
-            }
-            // this path serves the reactive maintenance of small LPs (and profiling): its follow-up refresh is
-            // meant to come AFTER the iteration that follows a tiny pivot, so that iteration is completed here
-            if (e->ill_tol > 0.0) launch_flush(e);
-            launch_dual_close(e);
-            HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-            HIPCHK(hipGetLastError());
-            prof_collect(e);
-            reconcile_counters(e);
-            adopt_fin(e);
-            if (getenv("ELLP_RUN_DEBUG"))
-                fprintf(stderr, "ellp run (polled): status %d iters %llu tiny %d fin %d need_rebuild %d lr %lld obj %.17g\n", e->h_st->status,
-                        (unsigned long long)e->h_st->iters, e->h_st->tiny, e->h_st->fin, e->h_st->need_rebuild, (long long)e->h_st->lr, e->h_st->obj);
-            // iterations that really ran (a maintenance request voids the rest of its batch)
-            const uint64_t done = e->h_st->iters - iters0;
-            remaining = done < max_iters ? max_iters - done : 0;
-            if (chained) e->maint_chain = 0;
-            if (service_maintenance_request(e)) continue;
-            if (chained && e->h_st->status == ST_RUNNING) maintain_inverse(e, true);  // the follow-up refresh
-            if (e->h_st->status != ST_RUNNING) {
-                const int tk = exact_takeover(e, remaining, &result, errbuf, errlen);
-                if (tk == 1) {
-                    const uint64_t done2 = e->h_st->iters - iters0;
-                    remaining = done2 < max_iters ? max_iters - done2 : 0;
-                } else if (tk == 0) {
-                    if (e->h_st->status == ST_NEED_EXACT) break;  // the slice is used up: the next one starts with the hand-over
-                    result = status_message(*e->h_st, errbuf, errlen);
-                }
-            }
-        }
-    }
-    // Certify or redo: a hybrid solve that has ended Optimal (certified by the exact kernel) on a point that does not keep the
-    // invariants of the reference's loop — the explicit-inverse stretch has let x, or the dual's carried d, drift past EPS:
-    // the caller's next test on that point (the phase-1 objective against EPS, primal…:42-50 / dual…:45-50; the assertions of
-    // DualPhase2::from, dual_problem.rs:293-310) would fail where the reference's own arithmetic passes — is repeated from the
-    // start of the phase by the LU-per-iteration kernel alone: from there on the engine IS the reference's loop, bit for bit.
-    if (result == ELLP_OPTIMAL && (e->hybrid || (e->cert_large && !e->exact_large_only)) && e->snap.valid && e->world == 1) {
-        double det[3] = {0.0, 0.0, 0.0};
-        bool ok = end_point_ok(e, det);
-        if (getenv("ELLP_FORCE_REDO")) ok = false;  // tests: the redo path itself (snapshot, restore, the exact kernel from the start)
-        const bool large = !e->hybrid;
-        if (!ok && large) {
-            // Above 1,024 rows the exact loop costs an LU of 2 m launches and two or three solves of m steps per iteration (about
-            // 18 us x m): the redo is taken when the iterations this phase needed, at that price, stay within
-            // ELLP_REDO_MAX_SECONDS (default 900 — a 1,850-row phase of 3,000 iterations: 100 s; config 3's 600,000: never);
-            // otherwise the point goes out as it is, counted as uncertified (ELLP_TAP_STATE).
-            const char *capv = getenv("ELLP_REDO_MAX_SECONDS");  // read when it matters: once per phase end that fails the check
-            const double cap = capv && capv[0] ? atof(capv) : 900.0;
-            const double est = (double)e->h_st->iters * 18e-6 * (double)e->m;
-            if (est > cap) {
-                if (getenv("ELLP_HYBRID_DEBUG"))
-                    fprintf(stderr, "ellp hybrid: end point violates an invariant (x %.3e, d %.3e); a redo would take about %.0f s: not done\n", det[0], det[1], est);
-                e->hy_uncertified += 1;
-                ok = true;
-            }
-        }
-        if (!ok && large) {
-            if (getenv("ELLP_HYBRID_DEBUG"))
-                fprintf(stderr, "ellp hybrid: end point violates an invariant (x %.3e, d %.3e, objective %.17g): redo on fresh LUs\n", det[0], det[1], det[2]);
-            const ellp_status rs = redo_from_snapshot(e, true, errbuf, errlen);
-            if (rs != ELLP_OPTIMAL) return rs;
-            result = run_exact_large(e, e->opts.max_iter, errbuf, errlen);
-            e->obj_fresh = false;
-        } else if (!ok) {
-            if (getenv("ELLP_HYBRID_DEBUG"))
-                fprintf(stderr, "ellp hybrid: end point violates an invariant (x %.3e, d %.3e, objective %.17g against the carried %.17g): redo\n",
-                        det[0], det[1], det[2], e->h_st->obj);
-            const ellp_status rs = redo_from_snapshot(e, false, errbuf, errlen);
-            if (rs != ELLP_OPTIMAL) return rs;
-            result = run_small(e, e->opts.max_iter, errbuf, errlen);
-            e->obj_fresh = false;
-        }
-    }
-    // The caller's budget (ellp_opts.max_iter) is spent: the reference has run that many FULL loop bodies
-    // (primal…:162-202), so an unbounded ray, a panic or a NaN found by the ratio test of the last one is its
-    // result, not MaxIter.  On the two-launch pipeline that ratio test is still open (its fold belongs to the next
-    // pricing launch, which will not come): close it and take the status from behind the closing kernel.  Slices
-    // inside the budget stay open — that is what makes slicing free.
-    if (result == ELLP_MAXITER && e->lag_open && !e->small && e->world == 1 && e->h_st->iters >= e->opts.max_iter) {
-        launch_flush(e);
-        hipLaunchKernelGGL(k_primal_obj, dim3(1), dim3(1024), 0, e->stream, e->c_B, e->c_N, e->x, e->B_index, e->N_index, e->m,
-                           e->nN, e->st);
-        HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        reconcile_counters(e);
-        adopt_fin(e);
-        e->obj_fresh = true;
-        if (e->h_st->status != ST_RUNNING && e->h_st->status != ST_NEED_MAINT) result = status_message(*e->h_st, errbuf, errlen);
-    }
-    if (stats) {
-        fill_stats(e, stats);
-        stats->t_loop_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    // A slice that ends normally has read h_st behind its last iteration; what may have been enqueued after that
-    // read (fill_stats' objective kernel, a follow-up refresh) changes neither the status nor the iteration
-    // counter, and a request it raises is seen by the next slice's first read-back.  So the next ellp_engine_run
-    // need not start with a read-back of its own (15 us of a 20-iteration slice).
-    e->hst_fresh = result == ELLP_MAXITER && !e->small && e->world == 1 && !e->colshard && e->nN > 0 &&
-                   e->h_st->status == ST_RUNNING;
-    return result;
-}
+#include "ellp_run.inc"
 
 ellp_status ellp_engine_read_point(ellp_engine *e, double *x, int64_t *B_index, int64_t *N_index, uint8_t *N_bound,
                                    double *y, double *d, char *errbuf, size_t errlen) {
@@ -5434,7 +3933,8 @@ ellp_status ellp_engine_read_point(ellp_engine *e, double *x, int64_t *B_index, 
     HIPCHK(hipStreamSynchronize(e->stream));
     if (was_open) {
         // completing the open iteration may have ended the solve (its ratio test found an unbounded ray, a panic of
-        // the reference, a NaN): that status is reported here, with the point as it stands
+        // the reference, a NaN): that status is reported here, with the point as it stands.  No reconcile_counters: the
+        // closing kernel is no loop body, nothing was enqueued that a stop could have voided
         adopt_fin(e);
         const int32_t stt = e->h_st->status;
         if (stt != ST_RUNNING && stt != ST_NEED_MAINT && stt != ELLP_OPTIMAL) return status_message(*e->h_st, errbuf, errlen);
@@ -5451,9 +3951,7 @@ int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap) {
     int64_t count = 0;
     switch (what) {
     case ELLP_TAP_U:
-        if (hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess)
-            return ELLP_ERR_DEVICE;
+        if (read_state(e) != hipSuccess) return ELLP_ERR_DEVICE;
         src = e->u + (e->h_st->usel ? e->ld : 0);
         count = e->m;
         break;
@@ -5478,9 +3976,7 @@ int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap) {
         break;
     case ELLP_TAP_STATE: {
         if (cap < 12) return ELLP_ERR_ARG;
-        if (hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess)
-            return ELLP_ERR_DEVICE;
+        if (read_state(e) != hipSuccess) return ELLP_ERR_DEVICE;
         const DevState &h = *e->h_st;
         const double v[12] = {(double)h.status, (double)h.cur, (double)h.s_q, (double)h.s_r, h.s_theta_d, h.s_delta,
                               (double)h.lr, h.ldelta, (double)h.iters, (double)h.pivots, h.lambda, h.s_rq};
@@ -5531,9 +4027,7 @@ int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap) {
         count = e->m * e->m;
         if (count > cap) return ELLP_ERR_ARG;
         if (ensure_inverse(e, nullptr, 0) != ELLP_OPTIMAL) return ELLP_ERR_DEVICE;
-        if (hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess)
-            return ELLP_ERR_DEVICE;
+        if (read_state(e) != hipSuccess) return ELLP_ERR_DEVICE;
         if (hipMemcpy2DAsync(dst, sizeof(double) * (size_t)e->m, e->h_st->cur ? e->W2 : e->W, sizeof(double) * (size_t)e->ld,
                              sizeof(double) * (size_t)e->m, (size_t)e->m, hipMemcpyDeviceToHost, e->stream) != hipSuccess)
             return ELLP_ERR_DEVICE;
@@ -5608,9 +4102,7 @@ ellp_status ellp_engine_debug_set_inverse(ellp_engine *e, const double *W) {
     if (hipSetDevice(e->device) != hipSuccess) return ELLP_ERR_DEVICE;
     if (ensure_inverse(e, nullptr, 0) != ELLP_OPTIMAL) return ELLP_ERR_DEVICE;
     // the mirror of ELLP_TAP_BINV: row-major m x m without the padding, into the buffer st->cur names
-    if (hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-        hipStreamSynchronize(e->stream) != hipSuccess)
-        return ELLP_ERR_DEVICE;
+    if (read_state(e) != hipSuccess) return ELLP_ERR_DEVICE;
     if (e->m > 0 &&
         hipMemcpy2DAsync(e->h_st->cur ? e->W2 : e->W, sizeof(double) * (size_t)e->ld, W, sizeof(double) * (size_t)e->m,
                          sizeof(double) * (size_t)e->m, (size_t)e->m, hipMemcpyHostToDevice, e->stream) != hipSuccess)
@@ -5790,10 +4282,9 @@ ellp_status ellp_engine_poll(ellp_engine *e, ellp_stats *stats, char *errbuf, si
     if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
     if (!e) return ELLP_ERR_ARG;
     HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(read_state(e));
     prof_collect(e);
-    reconcile_counters(e);
+    reconcile_counters(e);  // the counters alone: a DevState::fin stays for the next kernel's leader to adopt (adopt_fin)
     (void)service_maintenance_request(e);
     fill_stats(e, stats);
     if (e->h_st->status == ST_RUNNING) return ELLP_MAXITER;  // still running: the slice is simply used up
@@ -5835,12 +4326,10 @@ ellp_status ellp_engine_rephase(ellp_engine *e, const double *c, const uint8_t *
                        e->B_index, e->N_index, e->c_B, e->c_N, e->Nb, e->m, e->nN);
     if (e->c_tail && (rc = hipMemcpyAsync(e->c_tail, c_dev + e->n, sizeof(double) * (size_t)(e->n_c - e->n), hipMemcpyDeviceToDevice, e->stream)) != hipSuccess)
         return bail(rc);
-    hipLaunchKernelGGL(k_primal_obj, dim3(1), dim3(1024), 0, e->stream, e->c_B, e->c_N, e->x, e->B_index, e->N_index, e->m,
-                       e->nN, e->st);  // c.x with the new costs (the objective trace continues from it)
+    launch_primal_obj(e);  // c.x with the new costs (the objective trace continues from it)
     if (e->trace_len > 0) (void)hipMemsetAsync(e->trace_it, 0, sizeof(unsigned long long) * (size_t)e->trace_len, e->stream);
     // a new solve_with_initial starts here: status, counters and flags afresh; B^-1 and `cur` stay
-    if ((rc = hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream)) != hipSuccess) return bail(rc);
-    if ((rc = hipStreamSynchronize(e->stream)) != hipSuccess) return bail(rc);
+    if ((rc = read_state(e)) != hipSuccess) return bail(rc);
     DevState ns = *e->h_st;
     ns.status = ST_RUNNING;
     ns.nan_flag = 0;
@@ -5917,8 +4406,7 @@ static ellp_status dual_point_from_inverse(ellp_engine *e, const double *c_dev, 
     std::vector<uint8_t> Nb((size_t)(nN > 0 ? nN : 1));
     HIPCHK(hipMemcpyAsync(d.data(), e->dd, sizeof(double) * (size_t)n_c, hipMemcpyDeviceToHost, e->stream));
     if (nN > 0) HIPCHK(hipMemcpyAsync(Nb.data(), e->Nb, (size_t)nN, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(read_state(e));
     HIPCHK(hipGetLastError());
     if (e->h_st->status != ST_RUNNING) return status_message(*e->h_st, errbuf, errlen);
     for (int64_t j = 0; j < nN; ++j) {
@@ -6000,8 +4488,7 @@ ellp_status ellp_engine_dual_rephase(ellp_engine *e, const double *c, const doub
                        e->N_index, e->c_B, e->c_N, e->Nb, m, nN);
     if (e->c_tail) DCHK(hipMemcpyAsync(e->c_tail, c_dev + e->n, sizeof(double) * (size_t)(n_c - e->n), hipMemcpyDeviceToDevice, e->stream));
     // a new solve_with_initial: status and counters afresh (the maintenance kernels need a RUNNING engine)
-    DCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    DCHK(hipStreamSynchronize(e->stream));
+    DCHK(read_state(e));
     DevState ns = *e->h_st;
     ns.status = ST_RUNNING;
     ns.nan_flag = 0;
@@ -6017,8 +4504,7 @@ ellp_status ellp_engine_dual_rephase(ellp_engine *e, const double *c, const doub
     // rebuilt from A_B first — once per solve
     launch_dual_close(e);
     launch_refactor(e);
-    DCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-    DCHK(hipStreamSynchronize(e->stream));
+    DCHK(read_state(e));
     if (e->h_st->status != ST_RUNNING) {
         cleanup();
         return status_message(*e->h_st, errbuf, errlen);
@@ -6079,8 +4565,7 @@ ellp_status ellp_engine_create_dual_phase1(int64_t m, int64_t n, const double *A
     };
     if (e->small) {  // k_small keeps no inverse; the point below is made from one all the same
         launch_refactor(e);
-        if (hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess) {
+        if (read_state(e) != hipSuccess) {
             set_err(errbuf, errlen, "HIP error in ellp_engine_create_dual_phase1");
             return fail(ELLP_ERR_DEVICE);
         }
@@ -6382,7 +4867,7 @@ ellp_status shard_exchange(ellp_engine *e, const double *src, double *dst, int64
 
 PackArgs pack_args(ellp_engine *e, int forced) {
     PackArgs a{};
-    a.A_N = e->A_N; a.xc = Xchg{e->X, e->seg, e->nbs, e->cpb}; a.N_index = e->N_index;
+    a.A_N = e->A_N; a.xc = xchg_of(e); a.N_index = e->N_index;
     a.pack = e->packs + (int64_t)e->rank * pack_doubles(e->ld);
     a.st = e->st; a.ld = e->ld; a.nN = e->nN; a.own0 = e->own0; a.own1 = e->own1;
     a.block0 = e->rank * e->nbs;
@@ -6403,7 +4888,7 @@ void launch_xchg_fused(ellp_engine *e) {
 }
 void launch_select(ellp_engine *e, int mode) {
     SelectArgs a{};
-    a.packs = e->packs; a.xc = Xchg{e->X, e->seg, e->nbs, e->cpb}; a.N_index = e->N_index; a.A_N = e->A_N;
+    a.packs = e->packs; a.xc = xchg_of(e); a.N_index = e->N_index; a.A_N = e->A_N;
     a.aq_cur = e->aq_cur; a.st = e->st; a.ld = e->ld; a.nN = e->nN; a.own0 = e->own0; a.own1 = e->own1;
     a.world = e->world; a.nblocks = e->nblocks; a.cpb = e->cpb; a.mode = mode; a.eps = e->eps;
     hipLaunchKernelGGL(k_sh_select, dim3(1), dim3(256), sizeof(double) * (size_t)e->nblocks + 16, e->stream, a);
@@ -6487,8 +4972,7 @@ ellp_status ellp_engine_mailbox_selftest(ellp_engine *e, int rounds, char *errbu
         const ellp_status s = shard_exchange(e, d_src, e->packs, n, errbuf, errlen);
         if (s != ELLP_OPTIMAL) return s;
         HIPCHK(hipMemcpyAsync(all.data(), e->packs, sizeof(double) * (size_t)(n * e->world), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(read_state(e));
         if (e->h_st->status != ST_RUNNING) {
             // re-arm: the engine is still good, only this transport is not
             const int32_t running = ST_RUNNING;
@@ -6536,8 +5020,7 @@ static ellp_status run_colsharded(ellp_engine *e, uint64_t max_iters, ellp_stats
         }
         // read back; the two internal requests of the selection are serviced here, one iteration at a time
         for (;;) {
-            HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
+            HIPCHK(read_state(e));
             HIPCHK(hipGetLastError());
             prof_collect(e);
             reconcile_counters(e);

@@ -667,8 +667,7 @@ ellp_status post_complete_open(ellp_engine *e, ellp_status *closing, char *errbu
     launch_flush(e);
     *closing = ELLP_OPTIMAL;
     if (was_open) {
-        HIPCHK(hipMemcpyAsync(e->h_st, e->st, sizeof(DevState), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(read_state(e));
         adopt_fin(e);
         const int32_t stt = e->h_st->status;
         if (stt != ST_RUNNING && stt != ST_NEED_MAINT && stt != ELLP_OPTIMAL) *closing = status_message(*e->h_st, errbuf, errlen);
