@@ -99,6 +99,16 @@ class _ResultRng(C.Structure):
                 ("N_bound", C.POINTER(C.c_uint8)), ("x_std", _PD)]
 
 
+class _Start(C.Structure):
+    """ellp_start (include/ellp_host.h)"""
+    _fields_ = [("n_B", C.c_int64), ("B_index", C.c_void_p), ("n_N", C.c_int64), ("N_index", C.c_void_p), ("N_bound", C.c_void_p)]
+
+
+class _StartReport(C.Structure):
+    """ellp_start_report (include/ellp_host.h)"""
+    _fields_ = [("used", C.c_int), ("reason", C.c_int), ("info", _engine.StartInfo)]
+
+
 class _FlatPhase(C.Structure):
     _fields_ = ([(k, C.c_int64) for k in ("m", "n", "n_c", "n_B", "n_N")] +
                 [(k, C.POINTER(C.c_double)) for k in ("A", "c", "b", "lb", "ub", "x", "y", "d")] +
@@ -148,6 +158,12 @@ def host_lib():
     L.ellp_solve_flags.restype = C.c_int
     L.ellp_solve_flags.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_uint, C.POINTER(_ResultRng)]
     L.ellp_result_rng_free.argtypes = [C.POINTER(_ResultRng)]
+    L.ellp_solve_start.restype = C.c_int
+    L.ellp_solve_start.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_uint, C.POINTER(_Start),
+                                   C.POINTER(_ResultRng), C.POINTER(_StartReport)]
+    L.ellp_debug_map_start.restype = C.c_int
+    L.ellp_debug_map_start.argtypes = [C.c_void_p, C.POINTER(_Start), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int64]
     L.ellp_solve_batch.restype = C.c_int
     L.ellp_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_void_p]
     L.ellp_debug_phase1.restype = C.c_int
@@ -298,7 +314,10 @@ class Solution:
         return r["rhs_down"], r["rhs_up"], np.stack([r["rhs_blocking_down"], r["rhs_blocking_up"]], axis=1)
 
     def basis(self):
-        """the final basis in standard form, as the ranging saw it: dict(B, N, Nb, x, row_origin, inverse_residual)"""
+        """the final basis in standard form, as the ranging saw it: dict(B, N, Nb, x, row_origin, inverse_residual); after
+        solve(prob, start=...) also without the ranging (then without inverse_residual).  It can be handed back as `start`."""
+        if getattr(self, "_rng", None) is None and getattr(self, "_basis", None) is not None:
+            return dict(self._basis)
         r = self._ranging()
         return {k: r[k] for k in ("B", "N", "Nb", "x", "row_origin", "inverse_residual")}
 
@@ -334,10 +353,19 @@ class _Solver:
     def default(cls):
         return cls()
 
-    def solve(self, prob, postsolve=False, ranging=False):
+    def solve(self, prob, start=None, postsolve=False, ranging=False):
         """postsolve=True: an Optimal result's Solution also has duals(), reduced_costs() and kkt() (one more pass on the
         device after the solve; off by default, and off means not one extra device call).  ranging=True (implies the
-        postsolve): also cost_ranging(), rhs_ranging() and basis()."""
+        postsolve): also cost_ranging(), rhs_ranging() and basis().
+
+        start: a basis to start from — a dict with B and optionally N, Nb (what Solution.basis() returns), or a Solution that
+        has a basis.  The point of that basis is made on the device; where it is feasible for this solver's method (primal
+        feasible for the primal solver, dual feasible for the dual solver) phase 2 starts there and iters[0] is 0, otherwise
+        the solve is exactly the cold one.  Each solver runs its own method only: after a changed right-hand side use the
+        dual solver, after a changed cost the primal solver.  The result has .start = dict(used, reason, ...) (reasons:
+        include/ellp_host.h), and an Optimal Solution's basis() works without ranging=True, so re-solves chain."""
+        if start is not None:
+            return self._solve_start(prob, start, (3 if ranging else 0) | (1 if postsolve else 0))
         if ranging:
             rr = _ResultRng()
             host_lib().ellp_solve_flags(prob._h, self._KIND, self.max_iter,
@@ -383,6 +411,33 @@ class _Solver:
         finally:
             host_lib().ellp_result_free(C.byref(r))
 
+    def _solve_start(self, prob, start, flags):
+        st, keep = _start_struct(start)
+        rr, rep = _ResultRng(), _StartReport()
+        host_lib().ellp_solve_start(prob._h, self._KIND, self.max_iter, C.byref(self._opts) if self._opts is not None else None,
+                                    flags, C.byref(st), C.byref(rr), C.byref(rep))
+        del keep
+        try:
+            res = _to_result(rr.ex.result)
+            res.start = dict(rep.info.as_dict(), used=bool(rep.used), reason=int(rep.reason))
+            if res.kind == SolverResult.Optimal:
+                rx = rr.ex
+                arr = lambda p, n: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=p._type_)
+                if rx.has_postsolve:
+                    res.solution._post = (arr(rx.duals, rx.n_duals), arr(rx.reduced_costs, rx.n_reduced_costs), rx.kkt.as_dict())
+                res.solution._basis = dict(B=arr(rr.B_index, rr.n_B), N=arr(rr.N_index, rr.n_N), Nb=arr(rr.N_bound, rr.n_N),
+                                           x=arr(rr.x_std, rr.n_x_std), row_origin=arr(rr.row_origin, rr.n_B))
+                if rr.has_ranging:
+                    res.solution._rng = dict(
+                        cost_down=arr(rr.cost_down, rr.n_cost), cost_up=arr(rr.cost_up, rr.n_cost),
+                        cost_blocking_down=arr(rr.cost_blocking_down, rr.n_cost), cost_blocking_up=arr(rr.cost_blocking_up, rr.n_cost),
+                        rhs_down=arr(rr.rhs_down, rr.n_rhs), rhs_up=arr(rr.rhs_up, rr.n_rhs),
+                        rhs_blocking_down=arr(rr.rhs_blocking_down, rr.n_rhs), rhs_blocking_up=arr(rr.rhs_blocking_up, rr.n_rhs),
+                        inverse_residual=float(rr.inverse_residual), **res.solution._basis)
+            return res
+        finally:
+            host_lib().ellp_result_rng_free(C.byref(rr))
+
     def solve_batch(self, problems):
         """solve() of every problem in `problems`: the device loops of all problems the LU-per-iteration kernels take run
         in batched launches, one workgroup per problem; the others are solved one by one.  The primal solver sends a
@@ -417,6 +472,35 @@ class _Solver:
             for r in rs:
                 L.ellp_result_free(C.byref(r))
         return out
+
+
+def _start_struct(start):
+    """ellp_start from a dict(B[, N, Nb]) or a Solution with a basis; the second value keeps the arrays alive"""
+    if isinstance(start, Solution):
+        start = start.basis()
+    B = np.ascontiguousarray(start["B"], dtype=np.int64)
+    N = np.ascontiguousarray(start["N"], dtype=np.int64) if start.get("N") is not None else None
+    Nb = np.ascontiguousarray(start["Nb"], dtype=np.uint8) if N is not None and start.get("Nb") is not None else None
+    if Nb is not None and len(Nb) != len(N):
+        raise ValueError("start: N and Nb differ in length")
+    st = _Start(len(B), B.ctypes.data, 0 if N is None else len(N), None if N is None else max(N.ctypes.data, 1),
+                None if Nb is None else Nb.ctypes.data)
+    return st, (B, N, Nb)
+
+
+def _debug_map_start(prob, start):
+    """the start as solve(prob, start=...) maps it into the standard form, on the host: (reason, rows, cols, B, N, Nb)"""
+    st, keep = _start_struct(start)
+    cap = prob.num_vars + prob.num_constraints + 1
+    B, N, Nb = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.uint8)
+    rows, cols = C.c_int64(0), C.c_int64(0)
+    rc = host_lib().ellp_debug_map_start(prob._h, C.byref(st), C.byref(rows), C.byref(cols), B.ctypes.data, N.ctypes.data,
+                                         Nb.ctypes.data, cap)
+    del keep
+    m, n = rows.value, cols.value
+    if rc != 0:
+        return rc, m, n, None, None, None
+    return 0, m, n, B[:m].copy(), N[:n - m].copy(), Nb[:n - m].copy()
 
 
 def _to_result(r):

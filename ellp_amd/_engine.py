@@ -60,6 +60,22 @@ class Kkt(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+START_KEEP_LABELS, START_LABELS_BY_D = 0, 1
+
+
+class StartInfo(C.Structure):
+    """ellp_start_info (include/ellp_hip.h): the measures of a point made from a basis"""
+    _fields_ = [("primal_infeasibility", C.c_double), ("primal_infeasibility_sum", C.c_double),
+                ("dual_infeasibility", C.c_double), ("x_backward_error", C.c_double), ("worst_primal_var", C.c_int64),
+                ("worst_dual_var", C.c_int64), ("labels_changed", C.c_int64), ("primal_feasible", C.c_int32),
+                ("dual_feasible", C.c_int32), ("x_refinement_steps", C.c_int32), ("reserved", C.c_int32), ("kkt", Kkt)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("reserved", "kkt")}
+        d["kkt"] = self.kkt.as_dict()
+        return d
+
+
 # int fn(void *user, void *host_buffer, int64_t segment_bytes, int world)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
 
@@ -240,6 +256,9 @@ def lib():
     L.ellp_postsolve.restype = C.c_int
     L.ellp_postsolve.argtypes = _PROBLEM_ARGS + [C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Kkt),
                                                  C.c_char_p, C.c_size_t]
+    L.ellp_basis_start.restype = C.c_int
+    L.ellp_basis_start.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                   C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StartInfo), C.c_char_p, C.c_size_t]
     _lib = L
     return L
 
@@ -411,6 +430,25 @@ def postsolve(fp, opts=None):
     if s != OPTIMAL:
         raise EllpHipError(s, err.value.decode())
     return y, d, r, k.as_dict()
+
+
+def basis_start(fp, mode=START_KEEP_LABELS, opts=None):
+    """ellp_basis_start: the point of the basis a FlatProblem holds (its B, N and Nb; its x is not read; n_c == n): x, y, d and
+    the repaired labels, made on the device.  Returns (status, x, y, d, Nb, info_dict) with status OPTIMAL, ERR_SINGULAR or
+    ERR_ARG (x, y, d, Nb are then None and info_dict holds only the message); raises EllpHipError on a device error."""
+    o = opts or default_opts()
+    x, y, d, info = np.zeros(max(fp.n, 0)), np.zeros(max(fp.m, 0)), np.zeros(max(fp.n, 0)), StartInfo()
+    Nb = fp.Nb.copy()
+    err = C.create_string_buffer(512)
+    s = lib().ellp_basis_start(fp.m, fp.n, _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind), _p(fp.lb), _p(fp.ub), _p(fp.B), fp.nB,
+                               _p(fp.N), _p(Nb), fp.nN, int(mode), C.byref(o), _p(x), _p(y), _p(d), C.byref(info), err, 512)
+    if s in (ERR_ARG, ERR_SINGULAR):
+        return s, None, None, None, None, {"message": err.value.decode()}
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    out = info.as_dict()
+    out["message"] = ""
+    return s, x, y, d, Nb, out
 
 
 def ranging(fp, opts=None):

@@ -481,6 +481,7 @@ struct PostProf {
     enum { LU = 0, SOLVE = 1, PASS = 2, REST = 3, NCAT = 4 };
     bool on;
     hipStream_t stream;
+    const char *name = "postsolve_profile";  // the first word of the line (ellp_basis_start brackets its stages with the same struct)
     struct Span { int cat; hipEvent_t a, b; };
     std::vector<Span> spans;
     PostProf(hipStream_t s) : on(getenv("ELLP_POST_PROFILE") && getenv("ELLP_POST_PROFILE")[0] == '1'), stream(s) {}
@@ -503,7 +504,7 @@ struct PostProf {
             if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) ms[sp.cat] += t;
             passes += sp.cat == PASS;
         }
-        fprintf(stderr, "postsolve_profile m=%lld nN=%lld steps=%d passes=%d lu_ms=%.4f solve_ms=%.4f pass_ms=%.4f rest_ms=%.4f\n", (long long)m,
+        fprintf(stderr, "%s m=%lld nN=%lld steps=%d passes=%d lu_ms=%.4f solve_ms=%.4f pass_ms=%.4f rest_ms=%.4f\n", name, (long long)m,
                 (long long)nN, steps, passes, ms[LU], ms[SOLVE], ms[PASS], ms[REST]);
     }
     ~PostProf() {
@@ -514,13 +515,12 @@ struct PostProf {
     }
 };
 
-// steps 2 to 5 on a complete state; the outputs are written only when everything succeeded
-ellp_status post_compute(ellp_engine *e, double *y, double *d, double *r, ellp_kkt *kkt, char *errbuf, size_t errlen) {
-    const int64_t m = e->m, ld = e->ld, nN = e->nN, n = e->n, n_c = e->n_c;
-    HIPCHK(post_workspace(e));
+// the fresh LU of A_B and the refined y (post_y; rho, den and omega of it; the basic part of d and of the partial sums of r
+// from the last pass over A_B); *steps: the refinement steps taken.  Shared by the postsolve and ellp_basis_start
+ellp_status post_solve_y(ellp_engine *e, PostProf &prof, int32_t *steps_out, char *errbuf, size_t errlen) {
+    const int64_t m = e->m, ld = e->ld;
     const size_t lds = 2 * sizeof(double) * (size_t)m;
     const unsigned mb = (unsigned)((m + 255) / 256);
-    PostProf prof(e->stream);
     HIPCHK(hipMemsetAsync(e->post_fail, 0, sizeof(int), e->stream));
     prof.begin(PostProf::LU);
     hipLaunchKernelGGL(k_rows_from_cols, dim3((unsigned)((m + 31) / 32), (unsigned)((m + 31) / 32)), dim3(256), 0, e->stream, e->A_B,
@@ -564,6 +564,19 @@ ellp_status post_compute(ellp_engine *e, double *y, double *d, double *r, ellp_k
         last = omega;
         steps += 1;
     }
+    *steps_out = steps;
+    return ELLP_OPTIMAL;
+}
+
+// steps 2 to 5 on a complete state; the outputs are written only when everything succeeded
+ellp_status post_compute(ellp_engine *e, double *y, double *d, double *r, ellp_kkt *kkt, char *errbuf, size_t errlen) {
+    const int64_t m = e->m, nN = e->nN, n = e->n, n_c = e->n_c;
+    HIPCHK(post_workspace(e));
+    const unsigned mb = (unsigned)((m + 255) / 256);
+    PostProf prof(e->stream);
+    int32_t steps = 0;
+    const ellp_status ys = post_solve_y(e, prof, &steps, errbuf, errlen);
+    if (ys != ELLP_OPTIMAL) return ys;
     prof.begin(PostProf::PASS);
     post_launch_pass(e, false);
     prof.end();

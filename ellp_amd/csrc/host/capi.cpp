@@ -105,7 +105,7 @@ ellp::EngineOptions engine_options(const ellp_opts *opts) {
 }
 // *out from what `run` returns or throws
 template <class F>
-int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr, ellp_result_rng *rng = nullptr) {
+int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr, ellp_result_rng *rng = nullptr, bool basis_always = false) {
     std::memset(out, 0, sizeof(*out));
     try {
         ellp::SolverResult r = run();
@@ -133,14 +133,14 @@ int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr, ellp_re
                 ex->reduced_costs = dup(ps.reduced_costs);
                 ex->kkt = ps.kkt;
             }
+            auto dup = [](const auto &v) {
+                using T = typename std::decay_t<decltype(v)>::value_type;
+                T *q = new T[v.size() ? v.size() : 1];
+                std::memcpy(q, v.data(), sizeof(T) * v.size());
+                return q;
+            };
             if (rng && r.solution->rng) {
                 const ellp::Ranging &rg = *r.solution->rng;
-                auto dup = [](const auto &v) {
-                    using T = typename std::decay_t<decltype(v)>::value_type;
-                    T *q = new T[v.size() ? v.size() : 1];
-                    std::memcpy(q, v.data(), sizeof(T) * v.size());
-                    return q;
-                };
                 rng->has_ranging = 1;
                 rng->n_cost = static_cast<int64_t>(rg.cost_down.size());
                 rng->cost_down = dup(rg.cost_down); rng->cost_up = dup(rg.cost_up);
@@ -149,6 +149,8 @@ int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr, ellp_re
                 rng->rhs_down = dup(rg.rhs_down); rng->rhs_up = dup(rg.rhs_up);
                 rng->rhs_blocking_down = dup(rg.rhs_blocking_down); rng->rhs_blocking_up = dup(rg.rhs_blocking_up);
                 rng->inverse_residual = rg.inverse_residual;
+            }
+            if (rng && (r.solution->rng || basis_always)) {  // the final basis: with the ranging, and always after ellp_solve_start
                 const ellp::Point &pt = r.solution->point;
                 std::vector<int64_t> B, N, ro;
                 std::vector<uint8_t> Nb;
@@ -182,6 +184,18 @@ int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr, ellp_re
         put(out->err, sizeof(out->err), e.what());
     }
     return out->status;
+}
+// the C view of a start as the C++ one; a negative count or a missing array gives sizes no standard form has (reason 1)
+ellp::StartBasis start_basis(const ellp_start *st) {
+    ellp::StartBasis sb;
+    if (st->n_B > 0 && st->B_index) sb.B.assign(st->B_index, st->B_index + st->n_B);
+    if (st->N_index) {
+        sb.has_N = true;
+        if (st->n_N > 0) sb.N.assign(st->N_index, st->N_index + st->n_N);
+        if (st->N_bound) sb.Nb.assign(st->N_bound, st->N_bound + sb.N.size());
+        else sb.Nb.assign(sb.N.size(), 0);  // without labels: every one Lower before the repair
+    }
+    return sb;
 }
 }  // namespace
 
@@ -236,6 +250,60 @@ int ellp_solve_flags(const ellp_problem *p, int solver, uint64_t max_iter, const
     }, &out->ex, out);
     out->ex.result = base;
     return s;
+}
+
+int ellp_solve_start(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, unsigned flags, const ellp_start *start,
+                     ellp_result_rng *out, ellp_start_report *report) {
+    if (report) std::memset(report, 0, sizeof(*report));
+    if (!out) return ELLP_ERR_ARG;
+    std::memset(out, 0, sizeof(*out));
+    if (!p || !start || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL) || (flags & ~(ELLP_SOLVE_POSTSOLVE | ELLP_SOLVE_RANGING))) {
+        out->ex.result.status = ELLP_ERR_ARG;
+        put(out->ex.result.err, sizeof(out->ex.result.err), "ellp_solve_start: no problem, no start, an unknown solver or an unknown flag");
+        return ELLP_ERR_ARG;
+    }
+    const ellp::StartBasis sb = start_basis(start);
+    const ellp::EngineOptions eo = engine_options(opts);
+    const std::optional<std::uint64_t> mi =
+        max_iter == ELLP_MAX_ITER_NONE ? std::nullopt : std::optional<std::uint64_t>(max_iter);
+    const bool post = (flags & ELLP_SOLVE_POSTSOLVE) != 0, rng = (flags & ELLP_SOLVE_RANGING) != 0;
+    ellp::StartReport rep;
+    ellp_result base;
+    const int s = fill_result(&base, [&] {
+        return solver == ELLP_SOLVER_PRIMAL
+                   ? ellp::PrimalSimplexSolver(mi).with_engine(eo).with_postsolve(post).with_ranging(rng).solve_from(p->prob, sb, &rep)
+                   : ellp::DualSimplexSolver(mi).with_engine(eo).with_postsolve(post).with_ranging(rng).solve_from(p->prob, sb, &rep);
+    }, &out->ex, out, /*basis_always=*/true);
+    out->ex.result = base;
+    if (report) {
+        report->used = rep.used ? 1 : 0;
+        report->reason = rep.reason;
+        report->info = rep.info;
+    }
+    return s;
+}
+
+int ellp_debug_map_start(const ellp_problem *p, const ellp_start *start, int64_t *rows, int64_t *cols, int64_t *B_out, int64_t *N_out,
+                         uint8_t *Nb_out, int64_t capacity) {
+    if (!p || !start || !rows || !cols) return ELLP_ERR_ARG;
+    try {
+        auto sf = ellp::StandardForm::from_problem(p->prob);
+        if (!sf) return ELLP_ERR_ARG;
+        *rows = static_cast<int64_t>(sf->rows());
+        *cols = static_cast<int64_t>(sf->cols());
+        if (sf->rows() == 0) return ellp::START_NO_ROWS;
+        std::vector<int64_t> B, N;
+        std::vector<uint8_t> Nb;
+        const int reason = ellp::map_start(*sf, start_basis(start), B, N, Nb);
+        if (reason != ellp::START_USED) return reason;
+        if (capacity < *cols) return ELLP_ERR_ARG;
+        if (B_out) std::memcpy(B_out, B.data(), sizeof(int64_t) * B.size());
+        if (N_out) std::memcpy(N_out, N.data(), sizeof(int64_t) * N.size());
+        if (Nb_out) std::memcpy(Nb_out, Nb.data(), Nb.size());
+        return 0;
+    } catch (const std::exception &) {
+        return ELLP_ERR_PANIC;
+    }
 }
 
 void ellp_result_rng_free(ellp_result_rng *r) {

@@ -230,6 +230,34 @@ struct EngineOptions {
                        // ELLP_FLAG_PRIMAL_STEEPEST_EDGE, ELLP_FLAG_DUAL_BOUND_FLIPPING; ELLP_FLAG_NO_CERTIFY
 };
 
+// extension (solve_from): a basis to start from, in the indices of StandardForm::from_problem(prob) — the Problem's variables,
+// then the slacks; what Solution's basis reports after a dual solve, and after a primal solve with the phase-1 columns
+// appended at indices >= cols() (such an entry of N is dropped, one in B makes the start unusable).  has_N false: N is the
+// complement of B in ascending order, every label Lower before the repair of ellp_basis_start.
+struct StartBasis {
+    std::vector<std::int64_t> B, N;
+    std::vector<std::uint8_t> Nb;
+    bool has_N = false;
+};
+// why a start was not used (an unusable start is never an error: solve_from then returns exactly what solve returns)
+enum StartReason {
+    START_USED = 0,
+    START_BAD_SIZE = 1,     // B has not rows() entries, or N (after the drop) not cols() - rows()
+    START_BAD_INDEX = 2,    // an index out of range (a phase-1 column in B is one), or listed twice
+    START_SINGULAR = 3,     // A_B is not invertible
+    START_NOT_FEASIBLE = 4, // the point is not primal feasible (primal solver) / not dual feasible (dual solver)
+    START_NO_ROWS = 5,      // a problem without rows has no basis: the start is ignored
+};
+struct StartReport {
+    bool used = false;
+    int reason = START_USED;
+    ellp_start_info info{};  // the measures of ellp_basis_start (zero where it was not reached)
+};
+// the start mapped into the standard form and checked (sizes, then indices and duplicates): START_USED and B, N, Nb of the
+// call to ellp_basis_start, or the reason.  Host only
+int map_start(const StandardForm &sf, const StartBasis &start, std::vector<std::int64_t> &B, std::vector<std::int64_t> &N,
+              std::vector<std::uint8_t> &Nb);
+
 class PrimalSimplexSolver {  // src/solvers/primal/primal_simplex_solver.rs:15-93
 public:
     PrimalSimplexSolver() : max_iter_(1000) {}  // Default, :19-23
@@ -244,6 +272,10 @@ public:
     PrimalSimplexSolver &with_ranging(bool on) { ranging_ = on; if (on) postsolve_ = true; return *this; }
 
     SolverResult solve(Problem prob) const;  // :32-93
+    // extension: phase 2 directly from the point of `start` where that point is primal feasible (ellp_basis_start, KEEP_LABELS),
+    // iters_phase1 = 0; else exactly solve(prob).  This solver runs the primal method only: a start that is dual but not
+    // primal feasible (a changed right-hand side) is one for DualSimplexSolver::solve_from
+    SolverResult solve_from(Problem prob, const StartBasis &start, StartReport *report = nullptr) const;
     // :95-236 — the loop itself runs on the GPU (ellp_primal_solve_with_initial)
     SolutionStatus solve_with_initial(const StandardForm &std_form, Point &pt, std::uint64_t *iters = nullptr) const;
 
@@ -264,6 +296,9 @@ public:
     DualSimplexSolver &with_ranging(bool on) { ranging_ = on; if (on) postsolve_ = true; return *this; }
 
     SolverResult solve(Problem prob) const;
+    // extension: phase 2 directly from the point of `start` where it is dual feasible (ellp_basis_start, LABELS_BY_D); else
+    // exactly solve(prob).  The dual method only: after a changed cost call PrimalSimplexSolver::solve_from
+    SolverResult solve_from(Problem prob, const StartBasis &start, StartReport *report = nullptr) const;
     SolutionStatus solve_with_initial(const StandardForm &std_form, DualFeasiblePoint &pt,
                                       std::uint64_t *iters = nullptr) const;
 

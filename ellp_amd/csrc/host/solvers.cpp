@@ -493,6 +493,171 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
     return res;
 }
 
+// ---- solve_from: a warm start
+
+int map_start(const StandardForm &sf, const StartBasis &start, std::vector<std::int64_t> &B, std::vector<std::int64_t> &N,
+              std::vector<std::uint8_t> &Nb) {
+    const std::int64_t m = static_cast<std::int64_t>(sf.rows()), n = static_cast<std::int64_t>(sf.cols());
+    if (static_cast<std::int64_t>(start.B.size()) != m) return START_BAD_SIZE;
+    for (std::int64_t v : start.B)
+        if (v < 0 || v >= n) return START_BAD_INDEX;  // v >= n: a phase-1 column of a primal solve's basis
+    B = start.B;
+    N.clear();
+    Nb.clear();
+    std::vector<std::uint8_t> seen(static_cast<size_t>(n), 0);
+    if (start.has_N) {
+        if (start.Nb.size() != start.N.size()) return START_BAD_SIZE;
+        for (size_t j = 0; j < start.N.size(); ++j) {
+            if (start.N[j] >= n) continue;  // a phase-1 column that ended nonbasic: it does not exist here
+            N.push_back(start.N[j]);
+            Nb.push_back(start.Nb[j]);
+        }
+        if (static_cast<std::int64_t>(N.size()) != n - m) return START_BAD_SIZE;
+        for (size_t j = 0; j < N.size(); ++j)
+            if (N[j] < 0 || Nb[j] > 2) return START_BAD_INDEX;
+    }
+    for (std::int64_t v : B) {
+        if (seen[static_cast<size_t>(v)]) return START_BAD_INDEX;
+        seen[static_cast<size_t>(v)] = 1;
+    }
+    if (start.has_N) {
+        for (std::int64_t v : N) {
+            if (seen[static_cast<size_t>(v)]) return START_BAD_INDEX;
+            seen[static_cast<size_t>(v)] = 1;
+        }
+    } else {
+        for (std::int64_t v = 0; v < n; ++v)
+            if (!seen[static_cast<size_t>(v)]) {
+                N.push_back(v);
+                Nb.push_back(static_cast<std::uint8_t>(NonbasicBound::Lower));
+            }
+    }
+    return START_USED;
+}
+
+namespace {
+
+// the point of the start in standard form, or the reason it cannot be used; on START_USED pt (and y, d) hold what
+// ellp_basis_start made
+int start_point(const StandardForm &sf, const StartBasis &start, int mode, const EngineOptions &eng, DualFeasiblePoint &dp,
+                ellp_start_info &info) {
+    if (sf.rows() == 0) return START_NO_ROWS;
+    std::vector<std::int64_t> B, N;
+    std::vector<std::uint8_t> Nb;
+    const int mapped = map_start(sf, start, B, N, Nb);
+    if (mapped != START_USED) return mapped;
+    if (sf.bounds.size() != sf.cols()) return START_BAD_SIZE;  // the standard form of a Problem has no cost without a column
+    Point shape;
+    shape.B.resize(B.size());
+    shape.N.resize(N.size());
+    Flat f = flatten(sf, shape);
+    const size_t m = sf.rows(), n = sf.cols();
+    dp.point.x.assign(n, 0.0);
+    dp.y.assign(m, 0.0);
+    dp.d.assign(n, 0.0);
+    const ellp_opts o = make_opts(0, eng);
+    char err[512] = {0};
+    const ellp_status s = ellp_basis_start(static_cast<std::int64_t>(m), static_cast<std::int64_t>(n), sf.A.a.data(), sf.c.data(), sf.b.data(),
+                                           f.kind.data(), f.lb.data(), f.ub.data(), B.data(), static_cast<std::int64_t>(B.size()), N.data(),
+                                           Nb.data(), static_cast<std::int64_t>(N.size()), mode, &o, dp.point.x.data(), dp.y.data(),
+                                           dp.d.data(), &info, err, sizeof(err));
+    if (s == ELLP_ERR_SINGULAR) return START_SINGULAR;
+    if (s == ELLP_ERR_ARG) return START_BAD_INDEX;  // more rows than an engine takes, or what map_start should have caught
+    if (s != ELLP_OPTIMAL) to_status(s, err);       // throws: no device
+    if (!(mode == ELLP_START_KEEP_LABELS ? info.primal_feasible : info.dual_feasible)) return START_NOT_FEASIBLE;
+    dp.point.B.resize(B.size());
+    dp.point.N.resize(N.size());
+    f.B = B;
+    f.N = N;
+    f.Nb = Nb;
+    unflatten(f, dp.point);
+    return START_USED;
+}
+
+// phase 2 from the point of a usable start, on a resident engine where the seam sends the problem to the device
+// (plain: the seam's call for a problem without nonbasic columns, as in solve(); map_status: the phase-2 switch of solve())
+template <class Plain, class MapStatus>
+SolverResult run_from_start(int kind, StandardForm sf, DualFeasiblePoint dp, std::uint64_t max_iter, const EngineOptions &engine,
+                            bool postsolve, bool ranging, Plain &&plain, MapStatus &&map_status) {
+    SolverResult res;
+    EngineHandle eng;
+    SolutionStatus s2;
+    if (!dp.point.N.empty()) {
+        Flat f = flatten(sf, dp.point);
+        const ellp_opts o = make_opts(max_iter, engine);
+        char err[512] = {0};
+        const bool is_dual = kind == ELLP_ENGINE_DUAL;
+        const ellp_status cs = ellp_engine_create(
+            kind, static_cast<std::int64_t>(sf.rows()), static_cast<std::int64_t>(sf.cols()), static_cast<std::int64_t>(sf.bounds.size()),
+            sf.A.a.data(), sf.c.data(), sf.b.data(), f.kind.data(), f.lb.data(), f.ub.data(), dp.point.x.data(), f.B.data(),
+            static_cast<std::int64_t>(f.B.size()), f.N.data(), f.Nb.data(), static_cast<std::int64_t>(f.N.size()),
+            is_dual ? dp.y.data() : nullptr, is_dual ? dp.d.data() : nullptr, &o, &eng.e, err, sizeof(err));
+        if (cs != ELLP_OPTIMAL) to_status(cs, err);
+        s2 = is_dual ? run_resident_dual(eng.e, max_iter, f, dp, &res.iters_phase2) : run_resident(eng.e, max_iter, f, dp.point, &res.iters_phase2);
+    } else {
+        s2 = plain(sf, dp, &res.iters_phase2);
+    }
+    if (!map_status(s2, res)) return res;
+    if (s2 == SolutionStatus::MaxIter) {
+        res.kind = SolverResult::MaxIter;
+        res.max_iter_obj = kind == ELLP_ENGINE_DUAL ? sf.dual_obj(dp.y, dp.d) : sf.obj(dp.point.x);
+        return res;
+    }
+    res.kind = SolverResult::Optimal;
+    res.solution = Solution{std::move(sf), std::move(dp.point), std::nullopt, std::nullopt};
+    if (ranging) attach_ranging(*res.solution, eng.e, engine);
+    else if (postsolve) attach_postsolve(*res.solution, eng.e, engine);
+    return res;
+}
+
+}  // namespace
+
+SolverResult PrimalSimplexSolver::solve_from(Problem prob, const StartBasis &start, StartReport *report) const {
+    StartReport local;
+    StartReport &rep = report ? *report : local;
+    rep = StartReport{};
+    auto sfo = StandardForm::from_problem(prob);
+    if (!sfo) {  // as solve()
+        SolverResult res;
+        res.kind = SolverResult::Infeasible;
+        return res;
+    }
+    DualFeasiblePoint dp;
+    rep.reason = start_point(*sfo, start, ELLP_START_KEEP_LABELS, engine_, dp, rep.info);
+    if (rep.reason != START_USED) return solve(std::move(prob));
+    rep.used = true;
+    return run_from_start(ELLP_ENGINE_PRIMAL, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_,
+                          [this](const StandardForm &sf, DualFeasiblePoint &p, std::uint64_t *it) { return solve_with_initial(sf, p.point, it); },
+                          [](SolutionStatus s, SolverResult &res) {
+                              if (s == SolutionStatus::Infeasible) throw EllPPanic("primal phase 2 should never be infeasible");
+                              if (s == SolutionStatus::Unbounded) { res.kind = SolverResult::Unbounded; return false; }
+                              return true;
+                          });
+}
+
+SolverResult DualSimplexSolver::solve_from(Problem prob, const StartBasis &start, StartReport *report) const {
+    StartReport local;
+    StartReport &rep = report ? *report : local;
+    rep = StartReport{};
+    auto sfo = StandardForm::from_problem(prob);
+    if (!sfo) {
+        SolverResult res;
+        res.kind = SolverResult::Infeasible;
+        return res;
+    }
+    DualFeasiblePoint dp;
+    rep.reason = start_point(*sfo, start, ELLP_START_LABELS_BY_D, engine_, dp, rep.info);
+    if (rep.reason != START_USED) return solve(std::move(prob));
+    rep.used = true;
+    return run_from_start(ELLP_ENGINE_DUAL, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_,
+                          [this](const StandardForm &sf, DualFeasiblePoint &p, std::uint64_t *it) { return solve_with_initial(sf, p, it); },
+                          [](SolutionStatus s, SolverResult &res) {
+                              if (s == SolutionStatus::Unbounded) throw EllPPanic("dual phase 2 should never return unbounded");
+                              if (s == SolutionStatus::Infeasible) { res.kind = SolverResult::Infeasible; return false; }
+                              return true;
+                          });
+}
+
 }  // namespace ellp
 
 // ---- solve_batch: solve() of many problems, the device loops in batched calls for the problems the LU-per-iteration kernels

@@ -607,6 +607,44 @@ ellp_status ellp_postsolve(int64_t m, int64_t n, int64_t n_c, const double *A, c
                            char *errbuf, size_t errbuf_len);
 
 /*
+ * A starting point from a basis: what a warm-started solve hands to ellp_engine_create.  Standard form,
+ * minimisation, n_c = n; the arguments are those of ellp_postsolve without x.  In this order, on the postsolve's kernels
+ * and workspace: the fresh LU of A_B and y = B^-T c_B refined to omega <= 2u; d = c - A^T y; the labels and the nonbasic
+ * values (by kind: Free -> label Free, 0; Lower -> Lower, lb; Upper -> Upper, ub; Fixed -> Lower, lb; TwoSided with
+ * ELLP_START_KEEP_LABELS: the given label, a given Free becomes Lower; TwoSided with ELLP_START_LABELS_BY_D: d_v >= 0 or NaN ->
+ * Lower, else Upper — the rule of DualPhase2::from); t = b - A_N x_N; x_B = B^-1 t, refined as y is until
+ * omega_x = max_i |t - A_B x_B|_i / (|t| + |A_B||x_B|)_i <= 2u (at most 4 steps, given up when a step does not halve it);
+ * the KKT report of that point and the measures a solver needs to decide whether it may start there.  d, t and the residuals
+ * come from the postsolve's compensated pass (KEEP_LABELS: one read of A_N; LABELS_BY_D: two, the labels need d first).
+ * Reduction orders are fixed by the launch geometry: two calls on the same arguments return the same bits.
+ *   N_bound: in/out, the repaired labels are written back; x: n, y: m, d: n doubles; y, d and info may be NULL.
+ * ELLP_ERR_SINGULAR: a zero pivot, every output (N_bound too) untouched.  ELLP_ERR_ARG with a message before any HIP call: a
+ * NULL input or x, m < 1, m > 8192, n_B != m, n_B + n_N != n, an index out of range or listed twice across B and N, a label
+ * or a kind above its range, an unknown mode.
+ */
+enum { ELLP_START_KEEP_LABELS = 0, ELLP_START_LABELS_BY_D = 1 };
+
+typedef struct ellp_start_info {
+    double primal_infeasibility;     /* max over BASIC positions of the bound violation of x (by kind, as ellp_kkt.bound_violation) */
+    double primal_infeasibility_sum; /* the sum of those violations, compensated, basic positions in ascending order */
+    double dual_infeasibility;       /* as ellp_kkt.dual_infeasibility for the labels returned */
+    double x_backward_error;         /* omega of x_B: max_i |t - A_B x_B|_i / (|t| + |A_B| |x_B|)_i, t = b - A_N x_N */
+    int64_t worst_primal_var, worst_dual_var; /* smallest index holding the maximum; of NaNs the first; -1: the maximum is 0 */
+    int64_t labels_changed;          /* nonbasic positions whose returned label differs from the one passed in */
+    int32_t primal_feasible, dual_feasible; /* measure < eps (the eps option); 0 for a NaN; dual_feasible is also 0 when
+                                        kkt.basic_reduced_cost is a NaN (a NaN in c_B shows there even without nonbasic columns) */
+    int32_t x_refinement_steps, reserved;
+    ellp_kkt kkt;                    /* the full report of the point made (its y_backward_error and refinement_steps are y's) */
+} ellp_start_info;
+
+ellp_status ellp_basis_start(int64_t m, int64_t n, const double *A, const double *c, const double *b,
+                             const uint8_t *bound_kind, const double *lb, const double *ub,
+                             const int64_t *B_index, int64_t n_B, const int64_t *N_index, uint8_t *N_bound /* in/out */, int64_t n_N,
+                             int mode, const ellp_opts *opts,
+                             double *x /* out, n */, double *y /* out, m */, double *d /* out, n */,
+                             ellp_start_info *info, char *errbuf, size_t errbuf_len);
+
+/*
  * Sensitivity ranging: over what change of one cost coefficient the basis stays optimal, and over what change of one
  * right-hand side it stays feasible.  Standard form, minimisation, at the basis and point the engine stands
  * on.  The call runs the postsolve above (with the completion of an open iteration, the fresh LU and the refined y) and uses

@@ -102,6 +102,32 @@ typedef struct ellp_result_rng {
 int ellp_solve_flags(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, unsigned flags, ellp_result_rng *out);
 void ellp_result_rng_free(ellp_result_rng *r);
 
+/* A warm start: solve from a given basis.  Indices are those of the standard form of the problem — its
+ * variables, then the slacks — which is what B_index / N_index of an ellp_result_rng hold after a dual solve; after a primal
+ * solve the phase-1 columns follow at indices >= the standard form's columns: such an entry of N is dropped, one in B makes
+ * the start unusable.  N_index NULL: N is the complement of B in ascending order, every label Lower; N_bound NULL: every
+ * label Lower (ellp_basis_start repairs the labels by kind, and for the dual solver by the sign of d).
+ * The point of the basis is made on the device (ellp_basis_start: ELLP_START_KEEP_LABELS for the primal solver, which needs
+ * primal_feasible; ELLP_START_LABELS_BY_D for the dual solver, which needs dual_feasible).  Each solver runs its own method
+ * only: after a changed right-hand side call the dual solver, after a changed cost the primal solver.  A usable start runs
+ * phase 2 directly on the standard form (iters_phase1 = 0, report->used = 1).  An unusable start is never an error: the call
+ * then does exactly what ellp_solve_flags does, with used = 0 and reason
+ *   1  B has not one entry per row, or N (after the drop) not one per remaining column;
+ *   2  an index out of range (a phase-1 column in B is one) or listed twice;
+ *   3  A_B is singular;   4  the point is not feasible for this solver's method;   5  the problem has no rows.
+ * On Optimal the basis fields of ellp_result_rng (B_index, N_index, N_bound, x_std, row_origin) are always filled, so that
+ * solves chain; has_postsolve / has_ranging follow flags as in ellp_solve_flags.  ELLP_ERR_ARG: p, start or out NULL, an
+ * unknown solver or flag.  report may be NULL.  Free with ellp_result_rng_free. */
+typedef struct ellp_start { int64_t n_B; const int64_t *B_index; int64_t n_N; const int64_t *N_index; const uint8_t *N_bound; } ellp_start;
+typedef struct ellp_start_report { int used; int reason; ellp_start_info info; } ellp_start_report;
+int ellp_solve_start(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, unsigned flags,
+                     const ellp_start *start, ellp_result_rng *out, ellp_start_report *report);
+/* Test/diagnostic tap, host only: the start as ellp_solve_start maps it into the standard form.  *rows, *cols: the standard
+ * form's; B_out (rows), N_out / Nb_out (cols - rows) when the return is 0; capacity: what the arrays hold, at least *cols.
+ * Returns 0, a reason (1, 2, 5) or a negative ellp_status. */
+int ellp_debug_map_start(const ellp_problem *p, const ellp_start *start, int64_t *rows, int64_t *cols, int64_t *B_out,
+                         int64_t *N_out, uint8_t *Nb_out, int64_t capacity);
+
 /* solve() of many problems by one solver in lock step: every phase's device loops of the problems the small kernel
  * takes (1 to 128 rows, with nonbasic columns), and of the 129 to 1,024-row problems the single call runs on the exact
  * mid-size kernel (pipeline 3, ELLP_MID_AUTO_MAX, the dual's bound flipping), run in one batched
