@@ -3420,6 +3420,24 @@ static const void *small_kernel(int kind, int nt) {
 // artificial columns of primal phase 1 and are made on the device (build_phase1)
 // The checks ellp_engine_create makes of one LP's arguments, before any HIP call (also those of every item of
 // ellp_batch_solve_with_initial)
+// every bound kind is one of the five of ellp_hip.h: asked at creation and at both phase hand-offs
+static ellp_status check_bound_kinds(int64_t n_c, const uint8_t *bound_kind, char *errbuf, size_t errlen) {
+    for (int64_t i = 0; i < n_c; ++i)
+        if (bound_kind[i] > 4) {
+            set_err(errbuf, errlen, "bound_kind[%lld] out of range", (long long)i);
+            return ELLP_ERR_ARG;
+        }
+    return ELLP_OPTIMAL;
+}
+
+// ellp_engine::box_problem: every bound TwoSided or Fixed and b = 0
+static bool is_box_problem(int64_t m, int64_t n_c, const uint8_t *bound_kind, const double *b) {
+    bool box = true;
+    for (int64_t i = 0; i < n_c && box; ++i) box = bound_kind[i] == ELLP_BOUND_TWOSIDED || bound_kind[i] == ELLP_BOUND_FIXED;
+    for (int64_t i = 0; i < m && box; ++i) box = b[i] == 0.0;
+    return box;
+}
+
 static ellp_status check_problem(int kind, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
                                  const uint8_t *bound_kind, const double *lb, const double *ub, const double *x,
                                  const int64_t *B_index, int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N,
@@ -3466,12 +3484,7 @@ static ellp_status check_problem(int kind, int64_t m, int64_t n, int64_t n_c, co
             set_err(errbuf, errlen, "N_index/N_bound[%lld] out of range", (long long)j);
             return ELLP_ERR_ARG;
         }
-    for (int64_t i = 0; i < n_c; ++i)
-        if (bound_kind[i] > 4) {
-            set_err(errbuf, errlen, "bound_kind[%lld] out of range", (long long)i);
-            return ELLP_ERR_ARG;
-        }
-    return ELLP_OPTIMAL;
+    return check_bound_kinds(n_c, bound_kind, errbuf, errlen);
 }
 
 // The device state a fresh engine starts from: running, no pivot yet, the objective of the starting point
@@ -3596,31 +3609,19 @@ static ellp_status create_core_arrays(ellp_engine *e, char *errbuf, size_t errle
     return ELLP_OPTIMAL;
 }
 
-// the upload's two temporaries: released on every way out of the stage, once the stream that reads them has drained
-struct UploadTemps {
-    hipStream_t stream;
-    double *A_full = nullptr, *c_full = nullptr;
-    ~UploadTemps() {
-        if (!A_full) return;
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(A_full);
-        (void)hipFree(c_full);
-    }
-};
-
 // upload (A goes through a temporary full copy, then columns are gathered on the device) and the starting DevState
 static ellp_status create_upload(ellp_engine *e, const double *A, const double *c, const double *b, const uint8_t *bound_kind,
                                  const double *lb, const double *ub, const double *x, const int64_t *B_index, const int64_t *N_index,
                                  const uint8_t *N_bound, const double *y, const double *d, int64_t n_explicit, char *errbuf,
                                  size_t errlen) {
     const int64_t m = e->m, n = e->n, n_c = e->n_c, n_N = e->nN, ld = e->ld;
-    UploadTemps t{e->stream};
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&t.A_full), sizeof(double) * (size_t)(m * n > 0 ? m * n : 1)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&t.c_full), sizeof(double) * (size_t)n_c));
-    HIPCHK(hipMemcpyAsync(t.A_full, A, sizeof(double) * (size_t)(m * n_explicit), hipMemcpyHostToDevice, e->stream));
+    DevTemp<double> A_full(e->stream), c_full(e->stream);  // released on every way out of the stage, once the stream has drained
+    HIPCHK(A_full.alloc((size_t)(m * n)));
+    HIPCHK(c_full.alloc((size_t)n_c));
+    HIPCHK(hipMemcpyAsync(A_full.p, A, sizeof(double) * (size_t)(m * n_explicit), hipMemcpyHostToDevice, e->stream));
     if (n_explicit < n)  // the artificial columns: zero here, their +-1 is set once b~ is known (k_phase1_art)
-        HIPCHK(hipMemsetAsync(t.A_full + m * n_explicit, 0, sizeof(double) * (size_t)(m * (n - n_explicit)), e->stream));
-    HIPCHK(hipMemcpyAsync(t.c_full, c, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemsetAsync(A_full.p + m * n_explicit, 0, sizeof(double) * (size_t)(m * (n - n_explicit)), e->stream));
+    HIPCHK(hipMemcpyAsync(c_full.p, c, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipMemcpyAsync(e->B_index, B_index, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice, e->stream));
     if (n_N > 0) {
         HIPCHK(hipMemcpyAsync(e->N_index, N_index, sizeof(int64_t) * (size_t)n_N, hipMemcpyHostToDevice, e->stream));
@@ -3633,13 +3634,13 @@ static ellp_status create_upload(ellp_engine *e, const double *A, const double *
     HIPCHK(hipMemcpyAsync(e->kindv, bound_kind, (size_t)n_c, hipMemcpyHostToDevice, e->stream));
     if (n_c > n) {  // the costs no stored column carries: kept for the postsolve's d and c . x
         HIPCHK(dmalloc(e, &e->c_tail, (size_t)(n_c - n)));
-        HIPCHK(hipMemcpyAsync(e->c_tail, t.c_full + n, sizeof(double) * (size_t)(n_c - n), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->c_tail, c_full.p + n, sizeof(double) * (size_t)(n_c - n), hipMemcpyDeviceToDevice, e->stream));
     }
-    hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)m), dim3(256), 0, e->stream, t.A_full, m, e->B_index, e->A_B, ld);
-    hipLaunchKernelGGL(k_gather_vec, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, t.c_full, e->B_index, e->c_B, m);
+    hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)m), dim3(256), 0, e->stream, A_full.p, m, e->B_index, e->A_B, ld);
+    hipLaunchKernelGGL(k_gather_vec, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, c_full.p, e->B_index, e->c_B, m);
     if (n_N > 0) {
-        hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)n_N), dim3(256), 0, e->stream, t.A_full, m, e->N_index, e->A_N, ld);
-        hipLaunchKernelGGL(k_gather_vec, dim3((unsigned)((n_N + 255) / 256)), dim3(256), 0, e->stream, t.c_full, e->N_index, e->c_N,
+        hipLaunchKernelGGL(k_gather_cols, dim3((unsigned)n_N), dim3(256), 0, e->stream, A_full.p, m, e->N_index, e->A_N, ld);
+        hipLaunchKernelGGL(k_gather_vec, dim3((unsigned)((n_N + 255) / 256)), dim3(256), 0, e->stream, c_full.p, e->N_index, e->c_N,
                            n_N);
     }
     HIPCHK(hipGetLastError());
@@ -3757,14 +3758,12 @@ static ellp_status create_initial_inverse(ellp_engine *e, char *errbuf, size_t e
     else launch_refactor(e);
     if (e->se && e->se_perm) {  // steepest-edge weights at a basis that is not a signed permutation: exact, from the inverse just built
         const int64_t rt = (m + 63) / 64;
-        double *part = nullptr;
-        if (hipMalloc(reinterpret_cast<void **>(&part), sizeof(double) * (size_t)(rt * n_N)) == hipSuccess) {
+        DevTemp<double> part(e->stream);
+        if (part.alloc((size_t)(rt * n_N)) == hipSuccess) {
             hipLaunchKernelGGL(k_se_exact_part, dim3((unsigned)((n_N + 63) / 64), (unsigned)rt), dim3(256), 0, e->stream, e->W, e->W2, e->A_N,
-                               e->st, m, ld, n_N, e->se_perm, part);
+                               e->st, m, ld, n_N, e->se_perm, part.p);
             hipLaunchKernelGGL(k_se_exact_reduce, dim3((unsigned)((n_N + 255) / 256)), dim3(256), 0, e->stream, e->st, n_N, (int)rt,
-                               e->se_perm, part, e->se_gamma);
-            (void)hipStreamSynchronize(e->stream);
-            (void)hipFree(part);
+                               e->se_perm, part.p, e->se_gamma);
         } else {
             (void)hipGetLastError();  // no scratch memory: the weights stay at 1 (a reference-framework start)
         }
@@ -3823,12 +3822,7 @@ static ellp_status engine_create_impl(int kind, int64_t m, int64_t n, int64_t n_
     e->n = n;
     e->n_c = n_c;
     e->nN = n_N;
-    if (kind == ELLP_ENGINE_DUAL) {
-        bool box = true;
-        for (int64_t i = 0; i < n_c && box; ++i) box = bound_kind[i] == ELLP_BOUND_TWOSIDED || bound_kind[i] == ELLP_BOUND_FIXED;
-        for (int64_t i = 0; i < m && box; ++i) box = b[i] == 0.0;
-        e->box_problem = box;
-    }
+    if (kind == ELLP_ENGINE_DUAL) e->box_problem = is_box_problem(m, n_c, bound_kind, b);
     ellp_status s = create_host_set(e, errbuf, errlen);
     if (s == ELLP_OPTIMAL) s = create_core_arrays(e, errbuf, errlen);
     if (s == ELLP_OPTIMAL) s = create_upload(e, A, c, b, bound_kind, lb, ub, x, B_index, N_index, N_bound, y, d, n_explicit, errbuf, errlen);
@@ -3877,39 +3871,6 @@ ellp_status ellp_engine_plan(int kind, int64_t m, int64_t n_N, const ellp_opts *
         (double)p.lagged, (double)p.dual_fused, (double)p.dual_fold, (double)p.want_unit_table, (double)p.want_stamps};
     memcpy(out, v, sizeof(v));
     return ELLP_OPTIMAL;
-}
-
-ellp_status ellp_engine_create_primal_phase1(int64_t m, int64_t n, const double *A, const double *b,
-                                             const uint8_t *bound_kind, const double *lb, const double *ub,
-                                             const double *x, const uint8_t *N_bound, const ellp_opts *opts_in,
-                                             ellp_engine **out, char *errbuf, size_t errlen) {
-    if (!out) return ELLP_ERR_ARG;
-    *out = nullptr;
-    if (m <= 0 || n <= 0 || !A || !b || !bound_kind || !lb || !ub || !x || !N_bound) {
-        set_err(errbuf, errlen, "null pointer or inconsistent sizes");
-        return ELLP_ERR_ARG;
-    }
-    // the phase-1 problem (primal_problem.rs:137-141, :236-253): costs 0 on the originals and 1 on the m
-    // artificials, the artificials Lower(0) and basic, every original variable nonbasic at the bound the
-    // caller names
-    const int64_t nt = n + m;
-    std::vector<double> c((size_t)nt, 0.0), lb2((size_t)nt, 0.0), ub2((size_t)nt, 0.0), x2((size_t)nt, 0.0);
-    std::vector<uint8_t> kind2((size_t)nt, (uint8_t)ELLP_BOUND_LOWER), Nb(N_bound, N_bound + n);
-    std::vector<int64_t> B((size_t)m), N((size_t)n);
-    for (int64_t j = 0; j < n; ++j) {
-        kind2[(size_t)j] = bound_kind[j];
-        lb2[(size_t)j] = lb[j];
-        ub2[(size_t)j] = ub[j];
-        x2[(size_t)j] = x[j];
-        N[(size_t)j] = j;
-    }
-    for (int64_t i = 0; i < m; ++i) {
-        c[(size_t)(n + i)] = 1.0;
-        B[(size_t)i] = n + i;
-    }
-    return engine_create_impl(ELLP_ENGINE_PRIMAL, m, nt, nt, A, c.data(), b, kind2.data(), lb2.data(), ub2.data(),
-                              x2.data(), B.data(), m, N.data(), Nb.data(), n, nullptr, nullptr, opts_in, out, errbuf, errlen,
-                              n, true);
 }
 
 #include "ellp_run.inc"
@@ -4291,311 +4252,7 @@ ellp_status ellp_engine_poll(ellp_engine *e, ellp_stats *stats, char *errbuf, si
     return status_message(*e->h_st, errbuf, errlen);
 }
 
-ellp_status ellp_engine_rephase(ellp_engine *e, const double *c, const uint8_t *bound_kind, const double *lb,
-                                const double *ub, char *errbuf, size_t errlen) {
-    if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
-    if (!e || !c || !bound_kind || !lb || !ub) return ELLP_ERR_ARG;
-    if (errbuf && errlen) errbuf[0] = 0;
-    if (e->kind != ELLP_ENGINE_PRIMAL) {
-        set_err(errbuf, errlen, "rephase is the primal phase-1 -> phase-2 hand-off");
-        return ELLP_ERR_ARG;
-    }
-    for (int64_t i = 0; i < e->n_c; ++i)
-        if (bound_kind[i] > 4) {
-            set_err(errbuf, errlen, "bound_kind[%lld] out of range", (long long)i);
-            return ELLP_ERR_ARG;
-        }
-    HIPCHK(hipSetDevice(e->device));
-    launch_flush(e);
-    HIPCHK(hipStreamSynchronize(e->stream));
-    double *c_dev = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&c_dev), sizeof(double) * (size_t)e->n_c));
-    auto bail = [&](hipError_t err) {
-        (void)hipStreamSynchronize(e->stream);
-        (void)hipFree(c_dev);
-        set_err(errbuf, errlen, "HIP error %s in ellp_engine_rephase", hipGetErrorString(err));
-        return ELLP_ERR_DEVICE;
-    };
-    hipError_t rc;
-    if ((rc = hipMemcpyAsync(c_dev, c, sizeof(double) * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream)) != hipSuccess) return bail(rc);
-    if ((rc = hipMemcpyAsync(e->lb, lb, sizeof(double) * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream)) != hipSuccess) return bail(rc);
-    if ((rc = hipMemcpyAsync(e->ub, ub, sizeof(double) * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream)) != hipSuccess) return bail(rc);
-    if ((rc = hipMemcpyAsync(e->kindv, bound_kind, (size_t)e->n_c, hipMemcpyHostToDevice, e->stream)) != hipSuccess) return bail(rc);
-    const int64_t cnt = e->m > e->nN ? e->m : e->nN;
-    hipLaunchKernelGGL(k_rephase, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, e->stream, c_dev, e->kindv,
-                       e->B_index, e->N_index, e->c_B, e->c_N, e->Nb, e->m, e->nN);
-    if (e->c_tail && (rc = hipMemcpyAsync(e->c_tail, c_dev + e->n, sizeof(double) * (size_t)(e->n_c - e->n), hipMemcpyDeviceToDevice, e->stream)) != hipSuccess)
-        return bail(rc);
-    launch_primal_obj(e);  // c.x with the new costs (the objective trace continues from it)
-    if (e->trace_len > 0) (void)hipMemsetAsync(e->trace_it, 0, sizeof(unsigned long long) * (size_t)e->trace_len, e->stream);
-    // a new solve_with_initial starts here: status, counters and flags afresh; B^-1 and `cur` stay
-    if ((rc = read_state(e)) != hipSuccess) return bail(rc);
-    DevState ns = *e->h_st;
-    ns.status = ST_RUNNING;
-    ns.nan_flag = 0;
-    ns.tiny = 0;
-    ns.tiny_p = 0;
-    ns.fin = 0;
-    ns.pe_valid = 0;
-    ns.open = 0;
-    ns.se_valid = 0;  // steepest edge: the last pivot's weight update has been applied by the pricing launch that ended the phase
-    ns.mv_pending = 0;
-    ns.pp_seg = 0;  // partial pricing starts over with the first segment
-    ns.pp_empty = 0;
-    ns.pp_skip = 0;
-    ns.pp_lo = 0;
-    ns.pp_hi = e->pp_P > 1 ? e->pp_S : e->nN;
-    ns.need_rebuild = 0;
-    ns.panic_code = 0;
-    ns.iters = ns.pivots = ns.flips = 0;
-    ns.lambda = 0.0;
-    *e->h_st = ns;
-    if ((rc = hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream)) != hipSuccess) return bail(rc);
-    if ((rc = hipStreamSynchronize(e->stream)) != hipSuccess) return bail(rc);
-    (void)hipFree(c_dev);
-    e->u_valid = false;  // u = B^-T c_B with the new costs
-    e->maint_chain = 0;
-    e->enqueued = 0;
-    e->iters_seen = 0;
-    e->snap.valid = false;  // a new phase starts here
-    e->exact_large_only = e->exact_large_always;  // ... in the fast loop again, unless the caller chose the exact loop (pipeline 3)
-    return ELLP_OPTIMAL;
-}
-
-// y = B^-T c_B, d = c - A^T y, labels and values of the nonbasic variables, x_B = B^-1 (b - A_N x_N), all from the
-// resident B^-1: the common part of DualPhase2::from (dual_problem.rs:278-328; labels :286-323) and of
-// DualPhase1::new (:165-214; labels :177-203, `phase1`).  Ends with the loop's own entry assertion
-// (dual_simplex_solver.rs:139-151).  c_dev: the costs by variable index, on the device.
-static ellp_status dual_point_from_inverse(ellp_engine *e, const double *c_dev, int phase1, const int64_t *N_host,
-                                           char *errbuf, size_t errlen) {
-    const int64_t m = e->m, nN = e->nN, ld = e->ld, n_c = e->n_c;
-    // Certified-hybrid engines take y (and, below, x_B) from a fresh LU of the basis — the LU-per-iteration kernel with zero
-    // iterations — as the reference does (dual_problem.rs:162-172, :275-284), not from the explicit inverse: the point is the
-    // START of a phase whose carried d the caller will test against EPS at its end, and a d that starts 1e-9 off stays 1e-9 off
-    // even when the exact kernel repeats the phase.
-    const bool from_lu = e->hybrid && e->LUa != nullptr && e->world == 1;
-    if (from_lu) {
-        HIPCHK(launch_mid(e, 0, 2));
-    } else if (e->exact_large_always) {
-        // the exact loop above 1,024 rows: y = B^-T c_B from a fresh LU of the basis as well (x_B follows in every loop body)
-        HIPCHK(exact_workspace(e));
-        HIPCHK(hipMemsetAsync(e->ex_fail, 0, sizeof(int), e->stream));
-        hipLaunchKernelGGL(k_rows_from_cols, dim3((unsigned)((m + 31) / 32), (unsigned)((m + 31) / 32)), dim3(256), 0, e->stream, e->A_B, e->luw.M, m, ld);
-        ellp_lu_rows_factor(&e->luw, e->stream);
-        hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), 2 * sizeof(double) * (size_t)m, e->stream, e->luw.M, e->luw.piv, m, e->c_B, e->ex_sol, 1, e->ex_fail);
-        int failed = 0;
-        HIPCHK(hipMemcpyAsync(&failed, e->ex_fail, sizeof(int), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (failed) {
-            set_err(errbuf, errlen, "unwrap() on None: the basis is exactly singular");
-            return ELLP_ERR_PANIC;
-        }
-        HIPCHK(hipMemsetAsync(e->y, 0, sizeof(double) * (size_t)ld, e->stream));
-        HIPCHK(hipMemcpyAsync(e->y, e->ex_sol, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, e->stream));
-    } else {
-        launch_btran(e);  // into e->u (a dual engine has no other use for it)
-        HIPCHK(hipMemcpyAsync(e->y, e->u, sizeof(double) * (size_t)ld, hipMemcpyDeviceToDevice, e->stream));
-    }
-    HIPCHK(hipMemsetAsync(e->x, 0, sizeof(double) * (size_t)n_c, e->stream));
-    DualRephaseArgs da{e->A_N, e->A_B, e->y, c_dev, e->kindv, e->lb, e->ub, e->N_index, e->B_index, e->dd, e->x, e->Nb,
-                       e->st, m, ld, nN, e->eps, phase1};
-    hipLaunchKernelGGL(k_dual_rephase, dim3((unsigned)((nN + m + 3) / 4)), dim3(256), 0, e->stream, da);
-    launch_resync(e, 1);
-    if (from_lu) HIPCHK(launch_mid(e, 0, 1));  // x_B = A_B^-1 (b - A_N x_N) from the LU
-    std::vector<double> d((size_t)n_c);
-    std::vector<uint8_t> Nb((size_t)(nN > 0 ? nN : 1));
-    HIPCHK(hipMemcpyAsync(d.data(), e->dd, sizeof(double) * (size_t)n_c, hipMemcpyDeviceToHost, e->stream));
-    if (nN > 0) HIPCHK(hipMemcpyAsync(Nb.data(), e->Nb, (size_t)nN, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(read_state(e));
-    HIPCHK(hipGetLastError());
-    if (e->h_st->status != ST_RUNNING) return status_message(*e->h_st, errbuf, errlen);
-    for (int64_t j = 0; j < nN; ++j) {
-        const double di = d[(size_t)N_host[(size_t)j]];
-        bool infeasible;
-        if (Nb[(size_t)j] == ELLP_NB_LOWER) infeasible = di < -e->eps;
-        else if (Nb[(size_t)j] == ELLP_NB_UPPER) infeasible = di > e->eps;
-        else infeasible = std::fabs(di) > e->eps;
-        if (infeasible) {
-            set_err(errbuf, errlen, "initial point of dual phase 2 is dual infeasible");
-            return ELLP_ERR_PANIC;
-        }
-    }
-    return ELLP_OPTIMAL;
-}
-
-ellp_status ellp_engine_dual_rephase(ellp_engine *e, const double *c, const double *b, const uint8_t *bound_kind,
-                                     const double *lb, const double *ub, char *errbuf, size_t errlen) {
-    if (e) e->hst_fresh = false;  // anything but ellp_engine_run may change the device state behind h_st
-    if (!e || !c || !b || !bound_kind || !lb || !ub) return ELLP_ERR_ARG;
-    if (errbuf && errlen) errbuf[0] = 0;
-    if (e->kind != ELLP_ENGINE_DUAL || e->small || e->colshard || e->world != 1) {
-        set_err(errbuf, errlen, "dual_rephase: a resident, unsharded dual engine of the explicit-inverse kind is needed");
-        return ELLP_ERR_ARG;
-    }
-    for (int64_t i = 0; i < e->n_c; ++i)
-        if (bound_kind[i] > 4) {
-            set_err(errbuf, errlen, "bound_kind[%lld] out of range", (long long)i);
-            return ELLP_ERR_ARG;
-        }
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const int64_t m = e->m, nN = e->nN, ld = e->ld, n_c = e->n_c;
-    // ---- N in variable-index order (dual_problem.rs:286-323 enumerates `is_basic`), columns moved along
-    std::vector<int64_t> N((size_t)nN), perm((size_t)nN), Nsorted((size_t)nN);
-    if (nN > 0) HIPCHK(hipMemcpy(N.data(), e->N_index, sizeof(int64_t) * (size_t)nN, hipMemcpyDeviceToHost));
-    for (int64_t j = 0; j < nN; ++j) perm[(size_t)j] = j;
-    std::sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b2) { return N[(size_t)a] < N[(size_t)b2]; });
-    bool moved = false;
-    for (int64_t j = 0; j < nN; ++j) {
-        Nsorted[(size_t)j] = N[(size_t)perm[(size_t)j]];
-        moved = moved || perm[(size_t)j] != j;
-    }
-    double *c_dev = nullptr, *A2 = nullptr;
-    int64_t *perm_dev = nullptr;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(e->stream);
-        if (c_dev) (void)hipFree(c_dev);
-        if (perm_dev) (void)hipFree(perm_dev);
-    };
-#define DCHK(expr)                                                                                        \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) {                                                                           \
-            cleanup();                                                                                    \
-            set_err(errbuf, errlen, "HIP error %s in ellp_engine_dual_rephase (%s)", hipGetErrorString(_e), #expr); \
-            return ELLP_ERR_DEVICE;                                                                       \
-        }                                                                                                 \
-    } while (0)
-    if (moved && nN > 0) {
-        DCHK(hipMalloc(reinterpret_cast<void **>(&A2), sizeof(double) * (size_t)(ld * nN)));
-        DCHK(hipMalloc(reinterpret_cast<void **>(&perm_dev), sizeof(int64_t) * (size_t)nN));
-        DCHK(hipMemcpyAsync(perm_dev, perm.data(), sizeof(int64_t) * (size_t)nN, hipMemcpyHostToDevice, e->stream));
-        hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)nN), dim3(256), 0, e->stream, e->A_N, A2, perm_dev, ld);
-        DCHK(hipMemcpyAsync(e->N_index, Nsorted.data(), sizeof(int64_t) * (size_t)nN, hipMemcpyHostToDevice, e->stream));
-        DCHK(hipStreamSynchronize(e->stream));
-        replace_alloc(e, e->A_N, A2);
-        e->A_N = A2;
-    }
-    // ---- new costs, right-hand side, bounds
-    DCHK(hipMalloc(reinterpret_cast<void **>(&c_dev), sizeof(double) * (size_t)n_c));
-    DCHK(hipMemcpyAsync(c_dev, c, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-    DCHK(hipMemcpyAsync(e->b_dev, b, sizeof(double) * (size_t)m, hipMemcpyHostToDevice, e->stream));
-    DCHK(hipMemcpyAsync(e->lb, lb, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-    DCHK(hipMemcpyAsync(e->ub, ub, sizeof(double) * (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-    DCHK(hipMemcpyAsync(e->kindv, bound_kind, (size_t)n_c, hipMemcpyHostToDevice, e->stream));
-    const int64_t cnt = m > nN ? m : nN;
-    hipLaunchKernelGGL(k_rephase, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, e->stream, c_dev, e->kindv, e->B_index,
-                       e->N_index, e->c_B, e->c_N, e->Nb, m, nN);
-    if (e->c_tail) DCHK(hipMemcpyAsync(e->c_tail, c_dev + e->n, sizeof(double) * (size_t)(n_c - e->n), hipMemcpyDeviceToDevice, e->stream));
-    // a new solve_with_initial: status and counters afresh (the maintenance kernels need a RUNNING engine)
-    DCHK(read_state(e));
-    DevState ns = *e->h_st;
-    ns.status = ST_RUNNING;
-    ns.nan_flag = 0;
-    ns.tiny = 0;
-    ns.need_rebuild = 0;
-    ns.panic_code = 0;
-    ns.iters = ns.pivots = ns.flips = 0;
-    ns.lr = -1;
-    *e->h_st = ns;
-    DCHK(hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream));
-    // y, d and the labels are made from B^-1 and checked against the reference's EPS assertions (dual_problem.rs:275-323);
-    // the reference takes a FRESH LU there, so the resident inverse (up to a maintenance period of eta updates old) is
-    // rebuilt from A_B first — once per solve
-    launch_dual_close(e);
-    launch_refactor(e);
-    DCHK(read_state(e));
-    if (e->h_st->status != ST_RUNNING) {
-        cleanup();
-        return status_message(*e->h_st, errbuf, errlen);
-    }
-    e->since_refactor = 0;
-    const ellp_status ps = dual_point_from_inverse(e, c_dev, 0, Nsorted.data(), errbuf, errlen);
-    cleanup();
-#undef DCHK
-    if (ps != ELLP_OPTIMAL) return ps;
-    std::vector<double> y((size_t)m), d((size_t)n_c);
-    HIPCHK(hipMemcpy(y.data(), e->y, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(d.data(), e->dd, sizeof(double) * (size_t)n_c, hipMemcpyDeviceToHost));
-    const double obj = host_dual_obj(m, n_c, b, bound_kind, lb, ub, y.data(), d.data());
-    HIPCHK(hipMemcpy(&e->st->obj, &obj, sizeof(double), hipMemcpyHostToDevice));
-    e->h_st->obj = obj;
-    e->need_dleave = true;
-    e->maint_chain = 0;
-    e->enqueued = 0;
-    e->iters_seen = 0;
-    e->snap.valid = false;  // a new phase starts here
-    e->exact_large_only = e->exact_large_always;  // ... in the fast loop again, unless the caller chose the exact loop (pipeline 3)
-    {
-        bool box = true;
-        for (int64_t i = 0; i < n_c && box; ++i) box = bound_kind[i] == ELLP_BOUND_TWOSIDED || bound_kind[i] == ELLP_BOUND_FIXED;
-        for (int64_t i = 0; i < m && box; ++i) box = b[i] == 0.0;
-        e->box_problem = box;
-    }
-    if (e->trace_len > 0) HIPCHK(hipMemset(e->trace_it, 0, sizeof(unsigned long long) * (size_t)e->trace_len));
-    return ELLP_OPTIMAL;
-}
-
-// DualPhase1::new's point (dual_problem.rs:162-214) made on the device: the caller has the box problem's standard
-// form and the basis the LU of A^T picked (B_index, and N_index in the order of the permutation, :153-160); the
-// engine builds B^-1 and from it y = B^-T c_B, d = c - A^T y, the nonbasic labels and values by the sign of d,
-// b~ = b - A x and x_B = B^-1 b~.  No LU of A_B on the host, no solves, no A x product there.
-ellp_status ellp_engine_create_dual_phase1(int64_t m, int64_t n, const double *A, const double *c, const double *b,
-                                           const uint8_t *bound_kind, const double *lb, const double *ub,
-                                           const int64_t *B_index, const int64_t *N_index, const ellp_opts *opts_in,
-                                           ellp_engine **out, char *errbuf, size_t errlen) {
-    if (errbuf && errlen) errbuf[0] = 0;
-    if (!out) return ELLP_ERR_ARG;
-    *out = nullptr;
-    if (m <= 0 || n <= m || !A || !c || !b || !bound_kind || !lb || !ub || !B_index || !N_index) {
-        set_err(errbuf, errlen, "bad arguments (a nonbasic variable is needed: n > m)");
-        return ELLP_ERR_ARG;
-    }
-    const int64_t nN = n - m;
-    std::vector<double> zeros((size_t)(n > m ? n : m), 0.0);
-    std::vector<uint8_t> Nb((size_t)(nN > 0 ? nN : 1), (uint8_t)ELLP_NB_LOWER);
-    ellp_engine *e = nullptr;
-    ellp_status s = engine_create_impl(ELLP_ENGINE_DUAL, m, n, n, A, c, b, bound_kind, lb, ub, zeros.data(), B_index, m,
-                                       N_index, Nb.data(), nN, zeros.data(), zeros.data(), opts_in, &e, errbuf, errlen, n,
-                                       false);
-    if (s != ELLP_OPTIMAL) return s;
-    auto fail = [&](ellp_status st) {
-        ellp_engine_destroy(e);
-        return st;
-    };
-    if (e->small) {  // k_small keeps no inverse; the point below is made from one all the same
-        launch_refactor(e);
-        if (read_state(e) != hipSuccess) {
-            set_err(errbuf, errlen, "HIP error in ellp_engine_create_dual_phase1");
-            return fail(ELLP_ERR_DEVICE);
-        }
-        if (e->h_st->status != ST_RUNNING) return fail(status_message(*e->h_st, errbuf, errlen));
-    }
-    double *c_dev = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&c_dev), sizeof(double) * (size_t)n) != hipSuccess ||
-        hipMemcpyAsync(c_dev, c, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, e->stream) != hipSuccess) {
-        if (c_dev) (void)hipFree(c_dev);
-        set_err(errbuf, errlen, "HIP error in ellp_engine_create_dual_phase1");
-        return fail(ELLP_ERR_DEVICE);
-    }
-    s = dual_point_from_inverse(e, c_dev, 1, N_index, errbuf, errlen);
-    (void)hipStreamSynchronize(e->stream);
-    (void)hipFree(c_dev);
-    if (s != ELLP_OPTIMAL) return fail(s);
-    std::vector<double> y((size_t)m), d((size_t)n);
-    if (hipMemcpy(y.data(), e->y, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(d.data(), e->dd, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
-        set_err(errbuf, errlen, "HIP error in ellp_engine_create_dual_phase1");
-        return fail(ELLP_ERR_DEVICE);
-    }
-    const double obj = host_dual_obj(m, n, b, bound_kind, lb, ub, y.data(), d.data());
-    if (hipMemcpy(&e->st->obj, &obj, sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(ELLP_ERR_DEVICE);
-    e->h_st->obj = obj;
-    e->need_dleave = true;
-    e->u_valid = false;
-    *out = e;
-    return ELLP_OPTIMAL;
-}
+#include "ellp_phase.inc"
 
 // ---- direct RCCL exchange -------------------------------------------------------------------
 static const RcclApi *load_rccl(const char *path, char *errbuf, size_t errlen) {
@@ -4974,7 +4631,7 @@ ellp_status ellp_engine_mailbox_selftest(ellp_engine *e, int rounds, char *errbu
         HIPCHK(hipMemcpyAsync(all.data(), e->packs, sizeof(double) * (size_t)(n * e->world), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(read_state(e));
         if (e->h_st->status != ST_RUNNING) {
-            // re-arm: the engine is still good, only this transport is not
+            // re-arm: the engine is still good, only this transport is not (one word, synchronously, on the null stream: not store_state)
             const int32_t running = ST_RUNNING;
             (void)hipMemcpy(&e->st->status, &running, sizeof(int32_t), hipMemcpyHostToDevice);
             e->h_st->status = ST_RUNNING;
@@ -5006,7 +4663,7 @@ static ellp_status run_colsharded(ellp_engine *e, uint64_t max_iters, ellp_stats
     uint64_t remaining = max_iters;
     const uint64_t poll = e->opts.poll_interval > 0 ? (uint64_t)e->opts.poll_interval : 32;
     int64_t period = e->refactor_period > 0 ? e->refactor_period : default_period(e->m, e->ld, e->nN);
-    auto rearm = [&]() {
+    auto rearm = [&]() {  // one word, asynchronously on purpose; not store_state, which would upload the whole struct
         static const int32_t running = ST_RUNNING;  // static: the copy is asynchronous
         (void)hipMemcpyAsync(&e->st->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
         e->h_st->status = ST_RUNNING;

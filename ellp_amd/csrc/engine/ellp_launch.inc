@@ -1,7 +1,8 @@
 // ellp_launch.inc — the host side of every launch of the explicit-inverse engine: the event brackets (Prof), the argument
 // structs filled from ellp_engine, the run-time value -> template instantiation dispatch, one iteration of each loop
 // (launch_primal_iteration, launch_dual_iteration), the maintenance of B^-1 (maintain_inverse,
-// service_maintenance_request) and the state read-back (read_state, settle_state).  No kernel lives here.  Included inside
+// service_maintenance_request), the state read-back (read_state, settle_state) and the pieces a stopped engine is made ready
+// again from (the DevState groups, store_state, nothing_enqueued / begin_phase, DevTemp).  No kernel lives here.  Included inside
 // the anonymous namespace behind struct ellp_engine and dmalloc, in front of everything that drives an engine
 // (creation, ellp_run.inc, the sharding API, ellp_post.inc).
 
@@ -431,6 +432,71 @@ void settle_state(ellp_engine *e) {
     adopt_fin(e);
 }
 
+// ---- a stopped engine made ready again: the DevState a hand-off (ellp_phase.inc) or a re-arm inside ellp_engine_run
+// (ellp_run.inc) uploads is the drained one with some groups of fields cleared.  One function per group; a site calls the
+// groups it clears and says which it leaves, and why.
+// the words every kernel tests at entry, and the requests and codes that come with a stop
+inline void clear_stop_words(DevState &s) {
+    s.status = ST_RUNNING;
+    s.nan_flag = 0;
+    s.tiny = 0;
+    s.need_rebuild = 0;
+    s.panic_code = 0;
+}
+// two-launch pipeline: what one launch leaves for the next one's leader (a tiny pivot, the final status)
+inline void clear_relays(DevState &s) { s.tiny_p = s.fin = 0; }
+// two-launch pipeline: the iteration nobody has folded yet, its pending eta update and column move
+inline void clear_open_iteration(DevState &s) { s.open = s.pe_valid = s.mv_pending = 0; }
+// a new solve_with_initial counts from zero
+inline void clear_counts(DevState &s) { s.iters = s.pivots = s.flips = 0; }
+// partial pricing starts over with the first segment
+inline void restart_pricing_window(DevState &s, const ellp_engine *e) {
+    s.pp_seg = s.pp_empty = s.pp_skip = 0;
+    s.pp_lo = 0;
+    s.pp_hi = e->pp_P > 1 ? e->pp_S : e->nN;
+}
+// the state becomes the host's copy and its upload is enqueued
+inline hipError_t store_state(ellp_engine *e, const DevState &s) {
+    *e->h_st = s;
+    return hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream);
+}
+// ... and the host's side of it: nothing is enqueued, no follow-up refresh is due, DevState::iters stands at `iters`
+inline void nothing_enqueued(ellp_engine *e, uint64_t iters) {
+    e->maint_chain = 0;
+    e->enqueued = 0;
+    e->iters_seen = iters;
+}
+// a new phase starts here: its counters at zero, the old phase's snapshot dropped, and the fast loop again unless the caller
+// chose the exact loop (pipeline 3)
+inline void begin_phase(ellp_engine *e) {
+    nothing_enqueued(e, 0);
+    e->snap.valid = false;
+    e->exact_large_only = e->exact_large_always;
+}
+
+// A device temporary of one host function: hipMalloc on request; on every way out the stream that may still read it is
+// drained and the buffer freed.  release(): the engine adopts the buffer (replace_alloc).
+template <typename T>
+struct DevTemp {
+    hipStream_t stream;
+    T *p = nullptr;
+    explicit DevTemp(hipStream_t s) : stream(s) {}
+    DevTemp(DevTemp &&o) noexcept : stream(o.stream), p(o.release()) {}
+    DevTemp &operator=(DevTemp &&) = delete;  // move-only: no copy either
+    ~DevTemp() {
+        if (!p) return;
+        (void)hipStreamSynchronize(stream);
+        (void)hipFree(p);
+    }
+    hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void **>(&p), sizeof(T) * (count ? count : 1)); }
+    T *release() {
+        T *q = p;
+        p = nullptr;
+        return q;
+    }
+    operator T *() const { return p; }
+};
+
 // DevState::obj = c . x of a primal engine (one small launch; the next read-back brings it)
 void launch_primal_obj(ellp_engine *e) {
     hipLaunchKernelGGL(k_primal_obj, dim3(1), dim3(1024), 0, e->stream, e->c_B, e->c_N, e->x, e->B_index, e->N_index, e->m, e->nN,
@@ -450,6 +516,7 @@ bool service_maintenance_request(ellp_engine *e) {
     if (e->h_st->status != ST_NEED_MAINT && !(e->h_st->status == ST_RUNNING && e->h_st->tiny)) return false;
     const int32_t running = ST_RUNNING, zero = 0;
     const bool rebuild = e->h_st->need_rebuild != 0;  // a refresh found B^-1 too far off for Newton-Schulz
+    // three words, not store_state: that would upload the whole struct where this copies twelve bytes
     (void)hipMemcpyAsync(&e->st->status, &running, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
     (void)hipMemcpyAsync(&e->st->tiny, &zero, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
     (void)hipMemcpyAsync(&e->st->need_rebuild, &zero, sizeof(int32_t), hipMemcpyHostToDevice, e->stream);

@@ -756,26 +756,19 @@ ellp_status ellp_engine_tableau_rows(ellp_engine *e, const int64_t *positions, i
     if (s == ELLP_OPTIMAL) {
         // the call's own buffers: the positions, k rows of the tableau, k rows of W
         const int64_t m = e->m, nN = e->nN;
-        struct Tmp {
-            int64_t *pos = nullptr;
-            double *al = nullptr, *rh = nullptr;
-            ~Tmp() {
-                if (pos) (void)hipFree(pos);
-                if (al) (void)hipFree(al);
-                if (rh) (void)hipFree(rh);
-            }
-        } t;
+        DevTemp<int64_t> pos(e->stream);
+        DevTemp<double> al(e->stream), rh(e->stream);
         auto body = [&](char *errbuf, size_t errlen) -> ellp_status {
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&t.pos), sizeof(int64_t) * (size_t)k));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&t.al), sizeof(double) * (size_t)(k * (nN > 0 ? nN : 1))));
-            if (rho) HIPCHK(hipMalloc(reinterpret_cast<void **>(&t.rh), sizeof(double) * (size_t)(k * m)));
-            HIPCHK(hipMemcpyAsync(t.pos, positions, sizeof(int64_t) * (size_t)k, hipMemcpyHostToDevice, e->stream));
-            range_launch_tab(e, t.pos, k, t.al);
-            if (rho) hipLaunchKernelGGL(k_range_gather, dim3((unsigned)k), dim3(256), 0, e->stream, e->rng_W, t.pos, t.rh, m, e->ld);
+            HIPCHK(pos.alloc((size_t)k));
+            HIPCHK(al.alloc((size_t)(k * (nN > 0 ? nN : 1))));
+            if (rho) HIPCHK(rh.alloc((size_t)(k * m)));
+            HIPCHK(hipMemcpyAsync(pos.p, positions, sizeof(int64_t) * (size_t)k, hipMemcpyHostToDevice, e->stream));
+            range_launch_tab(e, pos.p, k, al.p);
+            if (rho) hipLaunchKernelGGL(k_range_gather, dim3((unsigned)k), dim3(256), 0, e->stream, e->rng_W, pos.p, rh.p, m, e->ld);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(e->stream));
-            if (nN > 0) HIPCHK(hipMemcpy(alpha, t.al, sizeof(double) * (size_t)(k * nN), hipMemcpyDeviceToHost));
-            if (rho) HIPCHK(hipMemcpy(rho, t.rh, sizeof(double) * (size_t)(k * m), hipMemcpyDeviceToHost));
+            if (nN > 0) HIPCHK(hipMemcpy(alpha, al.p, sizeof(double) * (size_t)(k * nN), hipMemcpyDeviceToHost));
+            if (rho) HIPCHK(hipMemcpy(rho, rh.p, sizeof(double) * (size_t)(k * m), hipMemcpyDeviceToHost));
             return ELLP_OPTIMAL;
         };
         s = body(eb, el);

@@ -2,8 +2,9 @@
 // explicit-inverse loop with look-ahead or polled read-backs), the certified hybrid's hand-over to the exact kernels
 // (exact_takeover, exact_certify_large), certify-or-redo from the snapshot of the phase's start, and the budget close of the
 // two-launch pipeline; with them ensure_inverse, ellp_engine_refresh and ellp_engine_refactor.  Host code only: what it
-// launches is in ellp_launch.inc.  Included inside extern "C", behind creation (engine_create_impl and the phase-1
-// constructors) and in front of the entry points that call ensure_inverse (read_point, tap, the sharding API).
+// launches, and the pieces its re-arms are made of, are in ellp_launch.inc.  Included inside extern "C", behind creation
+// (engine_create_impl) and in front of the entry points that call ensure_inverse (read_point, tap, the sharding API) and of
+// the phase hand-offs (ellp_phase.inc).
 
 // The explicit-inverse engine is about to be used on an engine that has been running k_small: build
 // B^-1 from the current A_B and leave the small path for good.
@@ -200,45 +201,39 @@ static ellp_status redo_from_snapshot(ellp_engine *e, bool large, char *errbuf, 
             set_err(errbuf, errlen, "redo: the index sets of the snapshot and of the engine differ");
             return ELLP_ERR_PANIC;
         }
-    double *A2 = nullptr;
-    int64_t *src_dev = nullptr;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&A2), sizeof(double) * (size_t)(ld * (m + nN))));
-    hipError_t rc = hipMalloc(reinterpret_cast<void **>(&src_dev), 8 * (size_t)(m + nN));
-    if (rc != hipSuccess) { (void)hipFree(A2); HIPCHK(rc); }
-    auto done = [&](hipError_t err) {
-        (void)hipStreamSynchronize(e->stream);
-        (void)hipFree(A2);
-        (void)hipFree(src_dev);
-        return err;
-    };
-#define RCHK(expr) do { hipError_t _r = (expr); if (_r != hipSuccess) { HIPCHK(done(_r)); } } while (0)
-    RCHK(hipMemcpyAsync(src_dev, src.data(), 8 * (size_t)(m + nN), hipMemcpyHostToDevice, e->stream));
-    hipLaunchKernelGGL(k_restore_cols, dim3((unsigned)(m + nN)), dim3(256), 0, e->stream, e->A_B, e->A_N, src_dev, A2, ld);
-    RCHK(hipMemcpyAsync(e->A_B, A2, sizeof(double) * (size_t)(ld * m), hipMemcpyDeviceToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->A_N, A2 + ld * m, sizeof(double) * (size_t)(ld * nN), hipMemcpyDeviceToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->x, sn.x.data(), 8 * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->B_index, sn.B.data(), 8 * (size_t)m, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->N_index, sn.N.data(), 8 * (size_t)nN, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->Nb, sn.Nb.data(), (size_t)nN, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->c_B, sn.c_B.data(), 8 * (size_t)m, hipMemcpyHostToDevice, e->stream));
-    RCHK(hipMemcpyAsync(e->c_N, sn.c_N.data(), 8 * (size_t)nN, hipMemcpyHostToDevice, e->stream));
-    if (e->kind == ELLP_ENGINE_DUAL) {
-        RCHK(hipMemcpyAsync(e->y, sn.y.data(), 8 * (size_t)m, hipMemcpyHostToDevice, e->stream));
-        RCHK(hipMemcpyAsync(e->dd, sn.d.data(), 8 * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream));
+    {
+        DevTemp<double> A2(e->stream);  // both freed, behind a drained stream, before the rebuild below
+        DevTemp<int64_t> src_dev(e->stream);
+        HIPCHK(A2.alloc((size_t)(ld * (m + nN))));
+        HIPCHK(src_dev.alloc((size_t)(m + nN)));
+        HIPCHK(hipMemcpyAsync(src_dev.p, src.data(), 8 * (size_t)(m + nN), hipMemcpyHostToDevice, e->stream));
+        hipLaunchKernelGGL(k_restore_cols, dim3((unsigned)(m + nN)), dim3(256), 0, e->stream, e->A_B, e->A_N, src_dev.p, A2.p, ld);
+        HIPCHK(hipMemcpyAsync(e->A_B, A2.p, sizeof(double) * (size_t)(ld * m), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->A_N, A2.p + ld * m, sizeof(double) * (size_t)(ld * nN), hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->x, sn.x.data(), 8 * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->B_index, sn.B.data(), 8 * (size_t)m, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->N_index, sn.N.data(), 8 * (size_t)nN, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->Nb, sn.Nb.data(), (size_t)nN, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->c_B, sn.c_B.data(), 8 * (size_t)m, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->c_N, sn.c_N.data(), 8 * (size_t)nN, hipMemcpyHostToDevice, e->stream));
+        if (e->kind == ELLP_ENGINE_DUAL) {
+            HIPCHK(hipMemcpyAsync(e->y, sn.y.data(), 8 * (size_t)m, hipMemcpyHostToDevice, e->stream));
+            HIPCHK(hipMemcpyAsync(e->dd, sn.d.data(), 8 * (size_t)e->n_c, hipMemcpyHostToDevice, e->stream));
+        }
+        // the phase's solve_with_initial starts again: every group but the pricing window (a certifying engine has none:
+        // the plan certifies with pp_P <= 1 only)
+        DevState ns = *e->h_st;
+        clear_stop_words(ns);
+        clear_relays(ns);
+        clear_open_iteration(ns);
+        ns.se_valid = 0;
+        clear_counts(ns);
+        ns.lambda = 0.0;
+        ns.obj = sn.obj;
+        ns.lr = -1;
+        HIPCHK(store_state(e, ns));
+        if (e->trace_len > 0) HIPCHK(hipMemsetAsync(e->trace_it, 0, sizeof(unsigned long long) * (size_t)e->trace_len, e->stream));
     }
-    DevState ns = *e->h_st;
-    ns.status = ST_RUNNING;
-    ns.nan_flag = 0; ns.tiny = 0; ns.tiny_p = 0; ns.fin = 0; ns.need_rebuild = 0; ns.panic_code = 0; ns.open = 0;
-    ns.pe_valid = 0; ns.mv_pending = 0; ns.se_valid = 0;
-    ns.iters = ns.pivots = ns.flips = 0;
-    ns.lambda = 0.0;
-    ns.obj = sn.obj;
-    ns.lr = -1;
-    *e->h_st = ns;
-    RCHK(hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream));
-    if (e->trace_len > 0) RCHK(hipMemsetAsync(e->trace_it, 0, sizeof(unsigned long long) * (size_t)e->trace_len, e->stream));
-    RCHK(done(hipSuccess));
-#undef RCHK
     if (large) {
         // above 1,024 rows the exact loop is run_exact_large; the explicit inverse follows the restored basis (the exact
         // iterations keep updating it, and the next phase's fast loop starts from it)
@@ -259,9 +254,7 @@ static ellp_status redo_from_snapshot(ellp_engine *e, bool large, char *errbuf, 
     e->lag_open = e->dual_open = false;
     e->u_valid = false;
     e->need_dleave = true;
-    e->maint_chain = 0;
-    e->enqueued = 0;
-    e->iters_seen = 0;
+    nothing_enqueued(e, 0);  // the same phase again: its snapshot stays, and exact_large_only is this function's to set
     e->since_refactor = e->since_btran = e->since_drift = 0;
     e->hy_redos += 1;
     return ELLP_OPTIMAL;
@@ -424,13 +417,15 @@ static int exact_certify_large(ellp_engine *e, uint64_t remaining, ellp_status *
     }
     // re-arm: the state is complete (a status found by k_ftran_eta comes with that pass's eta update done; one found by a
     // ratio-test fold comes before anything of its iteration is committed); the loop body that found it is not counted twice
+    // The counts, lambda and the pricing window go on (the same solve).  se_valid is not cleared here: nothing sets it, the
+    // plan certifies without steepest edge only.
     DevState ns = *e->h_st;
-    ns.status = ST_RUNNING;
-    ns.nan_flag = 0; ns.tiny = 0; ns.tiny_p = 0; ns.fin = 0; ns.need_rebuild = 0; ns.panic_code = 0;
-    ns.open = 0; ns.pe_valid = 0; ns.mv_pending = 0; ns.usel = 0; ns.usel_next = 0;
+    clear_stop_words(ns);
+    clear_relays(ns);
+    clear_open_iteration(ns);
+    ns.usel = ns.usel_next = 0;  // k_exact_put_u writes the first u buffer
     if (!guard && ns.iters > 0) ns.iters -= 1;
-    *e->h_st = ns;
-    if ((rc = hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream)) != hipSuccess) return fail(rc);
+    if ((rc = store_state(e, ns)) != hipSuccess) return fail(rc);
     if ((rc = hipMemsetAsync(e->ex_fail, 0, sizeof(int), e->stream)) != hipSuccess) return fail(rc);
     e->guard_off = true;
     e->lag_open = false;
@@ -467,9 +462,7 @@ static int exact_certify_large(ellp_engine *e, uint64_t remaining, ellp_status *
                 (unsigned long long)ns.iters, s2, failed ? " (LU singular: not certified)" : "");
     e->u_valid = false;
     e->since_btran = 0;
-    e->maint_chain = 0;
-    e->enqueued = 0;
-    e->iters_seen = e->h_st->iters;
+    nothing_enqueued(e, e->h_st->iters);
     e->need_dleave = false;
     if (s2 == ST_RUNNING && !e->h_st->tiny) return 1;
     if (s2 == ST_RUNNING) return 1;  // a maintenance request raised by the iteration: the run loop services it
@@ -500,21 +493,18 @@ static int exact_takeover(ellp_engine *e, uint64_t remaining, ellp_status *resul
         budget += 1;
     }
     if (budget == 0) return 0;  // a guarded pivot at the very end of the caller's slice: the next slice starts here
-    ns.status = ST_RUNNING;
-    ns.nan_flag = 0;
-    ns.tiny = 0;
-    ns.tiny_p = 0;
-    ns.fin = 0;
-    ns.need_rebuild = 0;
-    ns.panic_code = 0;
+    // The counts, lambda and the pricing window go on (the same solve).  Kept as found, and a question for a later change:
+    // open, pe_valid and mv_pending are NOT cleared here, although exact_certify_large clears them at the same
+    // moment of its own hand-over.
+    clear_stop_words(ns);
+    clear_relays(ns);
     auto fail = [&](hipError_t rc) {
         set_err(errbuf, errlen, "HIP error %s in the hand-over to the exact kernel", hipGetErrorString(rc));
         *result = ELLP_ERR_DEVICE;
         return 2;
     };
     hipError_t rc;
-    *e->h_st = ns;
-    if ((rc = hipMemcpyAsync(e->st, e->h_st, sizeof(DevState), hipMemcpyHostToDevice, e->stream)) != hipSuccess) return fail(rc);
+    if ((rc = store_state(e, ns)) != hipSuccess) return fail(rc);
     const uint64_t K = budget < (uint64_t)e->exact_K ? budget : (uint64_t)e->exact_K;
     static const int dual_resync = [] {  // diagnostics: ELLP_HYBRID_RESYNC = 1 (default) recomputes x_B only, 2 x_B, y and d
         const char *v = getenv("ELLP_HYBRID_RESYNC");
@@ -535,9 +525,7 @@ static int exact_takeover(ellp_engine *e, uint64_t remaining, ellp_status *resul
                 (unsigned long long)ns.iters, (unsigned long long)did, s2);
     e->u_valid = false;
     e->since_btran = 0;
-    e->maint_chain = 0;
-    e->enqueued = 0;
-    e->iters_seen = e->h_st->iters;
+    nothing_enqueued(e, e->h_st->iters);
     if (e->h_st->pivots != ns.pivots || failed) {
         // the explicit inverse follows the basis (also when the solve has ended: a phase hand-off reads it)
         static const int32_t running = ST_RUNNING;
