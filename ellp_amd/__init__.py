@@ -164,6 +164,8 @@ def host_lib():
     L.ellp_debug_map_start.restype = C.c_int
     L.ellp_debug_map_start.argtypes = [C.c_void_p, C.POINTER(_Start), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int64]
+    L.ellp_solve_batch_ex.restype = C.c_int
+    L.ellp_solve_batch_ex.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_int, C.c_void_p]
     L.ellp_solve_batch.restype = C.c_int
     L.ellp_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_void_p]
     L.ellp_debug_phase1.restype = C.c_int
@@ -438,7 +440,7 @@ class _Solver:
         finally:
             host_lib().ellp_result_rng_free(C.byref(rr))
 
-    def solve_batch(self, problems):
+    def solve_batch(self, problems, postsolve=False):
         """solve() of every problem in `problems`: the device loops of all problems the LU-per-iteration kernels take run
         in batched launches, one workgroup per problem; the others are solved one by one.  The primal solver sends a
         problem to the device once and runs both of its phases there (ellp_batch_primal_solve): the workgroup that ends
@@ -449,12 +451,43 @@ class _Solver:
         ELLP_MID_AUTO_MAX; for the dual solver also bound flipping).  The dual's phase-1 starts of those problems, which solve() builds on the device,
         are built for all of them in one batched call (ellp_batch_dual_phase1_start).  Returns a list with one entry per problem: the SolverResult
         solve(p) returns, or, where solve(p) would raise, the exception instance it would raise (returned, not raised).
-        Results are those of solve(p) to the bit."""
+        Results are those of solve(p) to the bit.
+
+        postsolve=True: every Optimal entry's Solution also has duals(), reduced_costs() and kkt(), with the bits of
+        solve(p, postsolve=True), from ONE batched call for the whole batch (ellp_batch_postsolve: one workgroup per problem
+        up to 128 rows; _engine.batch_postsolve_info() reports its launches, items and chunks); where
+        solve(p, postsolve=True) would raise, the entry is that exception.  Off by default, and off means not one extra
+        device call."""
         problems = list(problems)
         n = len(problems)
         if n == 0:
             return []
         handles = (C.c_void_p * n)(*[p._h for p in problems])
+        if postsolve:
+            rxs = (_ResultEx * n)()
+            L = host_lib()
+            s = L.ellp_solve_batch_ex(handles, n, self._KIND, self.max_iter,
+                                      C.byref(self._opts) if self._opts is not None else None, 1, rxs)
+            if s == _engine.ERR_ARG:
+                raise ValueError("solve_batch: invalid arguments")
+            out = []
+            try:
+                for rx in rxs:
+                    try:
+                        res = _to_result(rx.result)
+                    except Exception as e:  # noqa: BLE001 — the exception solve() would raise, handed back
+                        out.append(e)
+                        continue
+                    if res.kind == SolverResult.Optimal and rx.has_postsolve:
+                        y = np.ctypeslib.as_array(rx.duals, shape=(rx.n_duals,)).copy() if rx.n_duals else np.zeros(0)
+                        d = (np.ctypeslib.as_array(rx.reduced_costs, shape=(rx.n_reduced_costs,)).copy()
+                             if rx.n_reduced_costs else np.zeros(0))
+                        res.solution._post = (y, d, rx.kkt.as_dict())
+                    out.append(res)
+            finally:
+                for rx in rxs:
+                    L.ellp_result_ex_free(C.byref(rx))
+            return out
         rs = (_Result * n)()
         L = host_lib()
         s = L.ellp_solve_batch(handles, n, self._KIND, self.max_iter,

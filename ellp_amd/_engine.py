@@ -256,6 +256,10 @@ def lib():
     L.ellp_postsolve.restype = C.c_int
     L.ellp_postsolve.argtypes = _PROBLEM_ARGS + [C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Kkt),
                                                  C.c_char_p, C.c_size_t]
+    L.ellp_batch_postsolve.restype = C.c_int
+    L.ellp_batch_postsolve.argtypes = [C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.ellp_batch_postsolve_info.restype = None
+    L.ellp_batch_postsolve_info.argtypes = [C.POINTER(C.c_uint64)]
     L.ellp_basis_start.restype = C.c_int
     L.ellp_basis_start.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                    C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StartInfo), C.c_char_p, C.c_size_t]
@@ -494,6 +498,50 @@ def batch_solve_with_initial(kind, flat_problems, opts=None):
     if s != OPTIMAL:
         raise EllpHipError(s, err.value.decode())
     return [(status[k], stats[k], items[k].err.decode()) for k in range(n)]
+
+
+class BatchPostOut(C.Structure):
+    """ellp_batch_post_out (include/ellp_hip.h)"""
+    _fields_ = [("y", C.c_void_p), ("d", C.c_void_p), ("r", C.c_void_p), ("kkt", C.POINTER(Kkt))]
+
+
+def batch_postsolve(flat_problems, opts=None, fill=0.0):
+    """ellp_batch_postsolve: the postsolve of every FlatProblem (the arrays a solve_with_initial call left) in one batched
+    call, with the bits of postsolve(fp) per problem.  Returns one (status, y, d, r, kkt_dict, msg) per problem; status is
+    OPTIMAL, ERR_ARG or ERR_SINGULAR, and where it is not OPTIMAL y, d and r are as they were made (every entry `fill`: the
+    call does not touch them) and kkt_dict is None.  Raises EllpHipError if the call as a whole is refused (device)."""
+    fps = list(flat_problems)
+    n = len(fps)
+    items = (BatchItem * max(n, 1))()
+    outs = (BatchPostOut * max(n, 1))()
+    kkts = (Kkt * max(n, 1))()
+    arrays = []
+    for k, (it, fp) in enumerate(zip(items, fps)):
+        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
+        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
+        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
+        it.B_index, it.n_B = _p(fp.B), fp.nB
+        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(fp.Nb), fp.nN
+        y, d, r = np.full(max(fp.m, 0), fill), np.full(max(fp.n_c, 0), fill), np.full(max(fp.m, 0), fill)
+        arrays.append((y, d, r))
+        outs[k].y, outs[k].d, outs[k].r = y.ctypes.data, d.ctypes.data, r.ctypes.data
+        outs[k].kkt = C.pointer(kkts[k])
+    status = (C.c_int * max(n, 1))()
+    o = opts or default_opts()
+    err = C.create_string_buffer(512)
+    s = lib().ellp_batch_postsolve(n, items, C.byref(o), outs, status, err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    return [(status[k], *arrays[k], kkts[k].as_dict() if status[k] == OPTIMAL else None, items[k].err.decode())
+            for k in range(n)]
+
+
+def batch_postsolve_info():
+    """ellp_batch_postsolve_info: the calling thread's last ellp_batch_postsolve: kernel launches of the batched path, items
+    on the batched kernel, items on the single path (inside the call), chunks."""
+    out = (C.c_uint64 * 4)()
+    lib().ellp_batch_postsolve_info(out)
+    return {"launches": int(out[0]), "batched": int(out[1]), "single": int(out[2]), "chunks": int(out[3])}
 
 
 class BatchPrimalItem(C.Structure):

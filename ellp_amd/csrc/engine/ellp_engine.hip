@@ -4807,5 +4807,6 @@ ellp_status ellp_dual_solve_with_initial(int64_t m, int64_t n, int64_t n_c, cons
 #include "ellp_batch.inc"
 #include "ellp_dstart.inc"
 #include "ellp_post.inc"
+#include "ellp_bpost.inc"
 #include "ellp_start.inc"
 #include "ellp_range.inc"

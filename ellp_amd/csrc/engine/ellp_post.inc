@@ -302,7 +302,9 @@ struct PostReportArgs {
     int32_t steps;
     ellp_kkt *out;
 };
-__global__ __launch_bounds__(1024) void k_post_report(PostReportArgs a) {
+// The report of one LP, by one workgroup of 1,024 threads (the strided sums and the trees fix the order of the objectives);
+// k_post_report runs it for an engine, k_post_report_batch (ellp_bpost.inc) once per item of a batch
+__device__ __forceinline__ void post_report(const PostReportArgs &a, int32_t steps) {
     __shared__ PostMax sh[1024];
     __shared__ double shs[1024], shc[1024];
     const int tid = threadIdx.x;
@@ -391,11 +393,12 @@ __global__ __launch_bounds__(1024) void k_post_report(PostReportArgs a) {
         k.worst_row = (pr.v == 0.0) ? -1 : pr.i;
         k.worst_bound_var = (bv.v == 0.0) ? -1 : bv.i;
         k.worst_dual_var = (di.v == 0.0) ? -1 : di.i;
-        k.refinement_steps = a.steps;
+        k.refinement_steps = steps;
         k.reserved = 0;
         *a.out = k;
     }
 }
+__global__ __launch_bounds__(1024) void k_post_report(PostReportArgs a) { post_report(a, a.steps); }
 
 int post_cpb(int64_t ncols) {
     int cpb = 64;
@@ -606,10 +609,10 @@ ellp_status post_compute(ellp_engine *e, double *y, double *d, double *r, ellp_k
 // The host-memory forms (ellp_postsolve, ellp_ranging): the checks answered before any HIP call, then a minimal engine that
 // holds the point in the engine's layout.  who: the caller's name in the messages.
 typedef std::unique_ptr<ellp_engine, void (*)(ellp_engine *)> PostOwn;
-ellp_status post_host_engine(const char *who, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
+// the checks (ellp_batch_postsolve makes them per item)
+ellp_status post_host_checks(const char *who, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
                              const uint8_t *bound_kind, const double *lb, const double *ub, const double *x, const int64_t *B_index,
-                             int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N, const ellp_opts *opts_in,
-                             PostOwn &own, char *errbuf, size_t errlen) {
+                             int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N, char *errbuf, size_t errlen) {
     if (m < 1) {
         set_err(errbuf, errlen, "%s: m < 1 (without rows y is empty and d = c: answered on the host)", who);
         return ELLP_ERR_ARG;
@@ -630,6 +633,14 @@ ellp_status post_host_engine(const char *who, int64_t m, int64_t n, int64_t n_c,
     const ellp_status cs = check_problem(ELLP_ENGINE_PRIMAL, m, n, n_c, A, c, b, bound_kind, lb, ub, x, B_index, n_B, N_index, N_bound,
                                          n_N, nullptr, nullptr, errbuf, errlen);
     if (cs != ELLP_OPTIMAL) return ELLP_ERR_ARG;  // an index, a label or a kind out of range
+    return ELLP_OPTIMAL;
+}
+ellp_status post_host_engine(const char *who, int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
+                             const uint8_t *bound_kind, const double *lb, const double *ub, const double *x, const int64_t *B_index,
+                             int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N, const ellp_opts *opts_in,
+                             PostOwn &own, char *errbuf, size_t errlen) {
+    const ellp_status chk = post_host_checks(who, m, n, n_c, A, c, b, bound_kind, lb, ub, x, B_index, n_B, N_index, N_bound, n_N, errbuf, errlen);
+    if (chk != ELLP_OPTIMAL) return chk;
     ellp_opts opts;
     ellp_default_opts(&opts);
     if (opts_in) opts = *opts_in;

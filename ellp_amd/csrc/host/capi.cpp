@@ -353,6 +353,37 @@ int ellp_solve_batch(const ellp_problem *const *probs, int64_t count, int solver
     return ELLP_OPTIMAL;
 }
 
+int ellp_solve_batch_ex(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+                        int postsolve, ellp_result_ex *out) {
+    if (count < 0 || (count > 0 && (!probs || !out)) || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL))
+        return ELLP_ERR_ARG;
+    for (int64_t k = 0; k < count; ++k)
+        if (!probs[k]) return ELLP_ERR_ARG;
+    std::vector<ellp::Problem> ps;
+    ps.reserve(static_cast<size_t>(count));
+    for (int64_t k = 0; k < count; ++k) ps.push_back(probs[k]->prob);
+    std::vector<ellp::BatchOutcome> res;
+    for (int64_t k = 0; k < count; ++k) std::memset(&out[k], 0, sizeof(out[k]));
+    try {
+        res = ellp::solve_batch(solver, std::move(ps), max_iter, engine_options(opts), postsolve != 0);
+    } catch (const std::exception &e) {  // host memory: the batch as a whole
+        for (int64_t k = 0; k < count; ++k) {
+            out[k].result.status = ELLP_ERR_DEVICE;
+            put(out[k].result.err, sizeof(out[k].result.err), e.what());
+        }
+        return ELLP_ERR_DEVICE;
+    }
+    for (int64_t k = 0; k < count; ++k) {
+        ellp_result base;
+        fill_result(&base, [&] {
+            if (res[k].error) std::rethrow_exception(res[k].error);
+            return std::move(res[k].result);
+        }, &out[k]);
+        out[k].result = base;
+    }
+    return ELLP_OPTIMAL;
+}
+
 static void fill_flat(ellp_flat_phase *o, const ellp::StandardForm &sf, const ellp::Point &pt,
                       const std::vector<double> *y, const std::vector<double> *d) {
     auto dupd = [](const std::vector<double> &v) {

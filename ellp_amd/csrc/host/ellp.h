@@ -316,7 +316,10 @@ struct BatchOutcome {
     SolverResult result;
     std::exception_ptr error;
 };
-std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng);
+// postsolve: every Optimal outcome's Solution carries duals(), reduced_costs() and kkt(), from ONE ellp_batch_postsolve call for
+// the whole batch, with the bits of solve() with_postsolve(true); false: not one extra device call
+std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng,
+                                      bool postsolve = false);
 
 // src/parse_mps.rs:11-66.  Variables/rows are taken in file order (the reference iterates
 // HashMaps, so its order is unspecified).

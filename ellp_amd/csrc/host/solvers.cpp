@@ -131,9 +131,24 @@ SolutionStatus run_resident(ellp_engine *e, std::uint64_t max_iter, Flat &f, Poi
 // phase 2 (examined where it stands, ellp_engine_postsolve); null, or an engine that call refuses (a sharded one): the
 // phase-2 arrays go up once more (ellp_postsolve).
 // Without rows it is answered here: y is empty and d = c.
+//
+// In two steps: y, d and the report of the standard form (here, or for many solutions at once by solve_batch's one
+// ellp_batch_postsolve call), then map_postsolve: y to the Problem's constraints, d to its variables.
+void map_postsolve(Solution &sol, const std::vector<double> &y, const std::vector<double> &d, const ellp_kkt &kkt) {
+    const StandardForm &sf = sol.std_form;
+    const size_t m = sf.rows(), nv = sf.prob.variables.size();
+    if (sf.row_origin.size() != m) throw EllPPanic("assertion failed: std_form.row_origin.len() == std_form.rows()");
+    Postsolve ps;
+    ps.kkt = kkt;
+    ps.duals.assign(sf.prob.constraints.size(), 0.0);
+    for (size_t k = 0; k < m; ++k) ps.duals[sf.row_origin[k]] = y[k];
+    ps.reduced_costs.assign(d.begin(), d.begin() + static_cast<std::ptrdiff_t>(nv));
+    sol.post = std::move(ps);
+}
+
 void attach_postsolve(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
     const StandardForm &sf = sol.std_form;
-    const size_t m = sf.rows(), nc = sf.bounds.size(), nv = sf.prob.variables.size();
+    const size_t m = sf.rows(), nc = sf.bounds.size();
     Postsolve ps;
     std::vector<double> y(m, 0.0), d(nc, 0.0);
     if (m == 0) {
@@ -185,11 +200,7 @@ void attach_postsolve(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
         }
         if (s != ELLP_OPTIMAL) to_status(s, err);  // throws: a singular basis is an EllPError, a refusal of the arrays a panic
     }
-    if (sf.row_origin.size() != m) throw EllPPanic("assertion failed: std_form.row_origin.len() == std_form.rows()");
-    ps.duals.assign(sf.prob.constraints.size(), 0.0);
-    for (size_t k = 0; k < m; ++k) ps.duals[sf.row_origin[k]] = y[k];
-    ps.reduced_costs.assign(d.begin(), d.begin() + static_cast<std::ptrdiff_t>(nv));
-    sol.post = std::move(ps);
+    map_postsolve(sol, y, d, ps.kkt);
 }
 
 // with_ranging(true): the cost and right-hand-side ranges of an Optimal solution, from the engine that ran phase 2 where there
@@ -1101,9 +1112,87 @@ void dual_batch(std::vector<Problem> &probs, std::uint64_t max_iter, const Engin
     }
 }
 
+// solve_batch(..., postsolve): duals, reduced costs and the report of every Optimal outcome, ONE ellp_batch_postsolve call
+// for all of them (the items over 128 rows take the single call's path inside it); without rows it is answered on the
+// host, as attach_postsolve answers it.  An item's refusal or singular basis becomes that outcome's exception, the one
+// solve() with_postsolve(true) throws.  No Optimal outcome with rows: not one device call.
+void batch_postsolve(std::vector<BatchOutcome> &out, const EngineOptions &eng) {
+    struct Job {
+        size_t k;
+        Flat f;
+        std::vector<double> y, d;
+        ellp_kkt kkt;
+    };
+    auto fail = [&](size_t k) {
+        out[k].error = std::current_exception();
+        out[k].result = SolverResult{};
+    };
+    std::vector<Job> jobs;
+    for (size_t k = 0; k < out.size(); ++k) {
+        if (out[k].error || out[k].result.kind != SolverResult::Optimal || !out[k].result.solution) continue;
+        Solution &sol = *out[k].result.solution;
+        if (sol.std_form.rows() == 0) {
+            try {
+                attach_postsolve(sol, nullptr, eng);
+            } catch (...) {
+                fail(k);
+            }
+            continue;
+        }
+        Job j;
+        j.k = k;
+        j.f = flatten(sol.std_form, sol.point);
+        j.y.assign(sol.std_form.rows(), 0.0);
+        j.d.assign(sol.std_form.bounds.size(), 0.0);
+        std::memset(&j.kkt, 0, sizeof(j.kkt));
+        jobs.push_back(std::move(j));
+    }
+    if (jobs.empty()) return;
+    std::vector<ellp_batch_item> items(jobs.size());
+    std::vector<ellp_batch_post_out> outs(jobs.size());
+    for (size_t q = 0; q < jobs.size(); ++q) {
+        Job &j = jobs[q];
+        Solution &sol = *out[j.k].result.solution;
+        const StandardForm &sf = sol.std_form;
+        ellp_batch_item &it = items[q];
+        std::memset(&it, 0, sizeof(it));
+        it.m = static_cast<std::int64_t>(sf.rows());
+        it.n = static_cast<std::int64_t>(sf.cols());
+        it.n_c = static_cast<std::int64_t>(sf.bounds.size());
+        it.A = sf.A.a.data();
+        it.c = sf.c.data();
+        it.b = sf.b.data();
+        it.bound_kind = j.f.kind.data();
+        it.lb = j.f.lb.data();
+        it.ub = j.f.ub.data();
+        it.x = sol.point.x.data();
+        it.B_index = j.f.B.data();
+        it.n_B = static_cast<std::int64_t>(j.f.B.size());
+        it.N_index = j.f.N.data();
+        it.N_bound = j.f.Nb.data();
+        it.n_N = static_cast<std::int64_t>(j.f.N.size());
+        outs[q] = ellp_batch_post_out{j.y.data(), j.d.data(), nullptr, &j.kkt};
+    }
+    const ellp_opts o = make_opts(0, eng);
+    std::vector<ellp_status> st(jobs.size(), ELLP_ERR_DEVICE);
+    char err[512] = {0};
+    const ellp_status rc = ellp_batch_postsolve(static_cast<std::int64_t>(items.size()), items.data(), &o, outs.data(), st.data(), err, sizeof(err));
+    for (size_t q = 0; q < jobs.size(); ++q) {
+        Job &j = jobs[q];
+        try {
+            if (rc != ELLP_OPTIMAL) to_status(rc, err);                 // throws, as attach_postsolve
+            else if (st[q] != ELLP_OPTIMAL) to_status(st[q], items[q].err);
+            map_postsolve(*out[j.k].result.solution, j.y, j.d, j.kkt);
+        } catch (...) {
+            fail(j.k);
+        }
+    }
+}
+
 }  // namespace
 
-std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng) {
+std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng,
+                                      bool postsolve) {
     std::vector<BatchOutcome> out(probs.size());
     if (solver == ELLP_ENGINE_PRIMAL) {
         std::vector<size_t> all(probs.size());
@@ -1112,6 +1201,7 @@ std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, st
     } else {
         dual_batch(probs, max_iter, eng, out);
     }
+    if (postsolve) batch_postsolve(out, eng);
     return out;
 }
 

@@ -607,6 +607,33 @@ ellp_status ellp_postsolve(int64_t m, int64_t n, int64_t n_c, const double *A, c
                            char *errbuf, size_t errbuf_len);
 
 /*
+ * The postsolve of many small LPs in one call: the items are those of ellp_batch_solve_with_initial
+ * after it returned (x, B_index, N_index and N_bound are read; an item's y and d are ignored), outs[i] says where item i's
+ * results go.  Every output of every item is, bit for bit, what ellp_postsolve returns for that item alone, whatever batch
+ * it sits in, at whatever position and however the batch is chunked.  An item of up to 128 rows and 65,536 nonbasic
+ * columns is done by one workgroup (k_post_batch: the basis and its LU in LDS, the refinement loop and its stop rule on
+ * the device), two launches per chunk whatever the item count; any other valid item is run inside the call through
+ * ellp_postsolve.  Per item: status_out[i] and items[i].err, the checks, messages and statuses of ellp_postsolve
+ * (ELLP_ERR_ARG before any HIP call; ELLP_ERR_SINGULAR with the item's outputs untouched); a failing item changes nothing
+ * for the others.  The call as a whole: ELLP_ERR_ARG (count < 0; items, outs or status_out NULL), ELLP_ERR_DEVICE, or
+ * ELLP_OPTIMAL; every check runs before any HIP call.  Chunks (budget ELLP_BATCH_MAX_BYTES, at most 65,535 items), the
+ * pinned staging buffer, the slab and the buffer pool are those of ellp_batch_solve_with_initial: one upload and one
+ * read-back per chunk.  Of opts only device is read by the batched kernel.
+ */
+typedef struct ellp_batch_post_out {
+    double *y, *d, *r; /* m, n_c, m doubles */
+    ellp_kkt *kkt;
+} ellp_batch_post_out; /* any may be NULL; all NULL: the item's ELLP_ERR_ARG */
+
+ellp_status ellp_batch_postsolve(int64_t count, ellp_batch_item *items, const ellp_opts *opts,
+                                 const ellp_batch_post_out *outs, ellp_status *status_out,
+                                 char *errbuf, size_t errbuf_len);
+
+/* Diagnostics of the calling thread's last ellp_batch_postsolve that passed the checks of the call: out4[0] kernel launches
+ * of the batched path, [1] items on the batched kernel, [2] items on the single path, [3] chunks. */
+void ellp_batch_postsolve_info(uint64_t *out4);
+
+/*
  * A starting point from a basis: what a warm-started solve hands to ellp_engine_create.  Standard form,
  * minimisation, n_c = n; the arguments are those of ellp_postsolve without x.  In this order, on the postsolve's kernels
  * and workspace: the fresh LU of A_B and y = B^-T c_B refined to omega <= 2u; d = c - A^T y; the labels and the nonbasic

@@ -137,6 +137,14 @@ int ellp_debug_map_start(const ellp_problem *p, const ellp_start *start, int64_t
 int ellp_solve_batch(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
                      ellp_result *out);
 
+/* ellp_solve_batch with the postsolve of ellp_solve_ex: postsolve != 0 adds, to every Optimal out[k], the duals, reduced costs
+ * and KKT report that ellp_solve_ex(probs[k], ..., 1, ...) returns, bit for bit, from ONE ellp_batch_postsolve call for the
+ * whole batch (ellp_hip.h; a problem without rows is answered on the host).  A refusal or a singular basis of one problem is
+ * that out[k]'s status and message, as ellp_solve_ex reports it.  postsolve == 0: exactly ellp_solve_batch, not one extra
+ * device call, has_postsolve = 0.  Free each out[k] with ellp_result_ex_free.  ellp_solve_batch is unchanged. */
+int ellp_solve_batch_ex(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+                        int postsolve, ellp_result_ex *out);
+
 /* Test/diagnostic tap: the flattened phase-1 problem (exactly the arrays that solve() hands to
  * ellp_*_solve_with_initial) so the host setup can be checked without a GPU.  All arrays are
  * owned by the struct (ellp_flat_phase_free).  Returns 0, 1 if the setup already proves
