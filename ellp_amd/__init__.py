@@ -166,6 +166,9 @@ def host_lib():
                                        C.c_void_p, C.c_void_p, C.c_int64]
     L.ellp_solve_batch_ex.restype = C.c_int
     L.ellp_solve_batch_ex.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_int, C.c_void_p]
+    L.ellp_solve_batch_start.restype = C.c_int
+    L.ellp_solve_batch_start.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_uint, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
     L.ellp_solve_batch.restype = C.c_int
     L.ellp_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_void_p]
     L.ellp_debug_phase1.restype = C.c_int
@@ -420,27 +423,11 @@ class _Solver:
                                     flags, C.byref(st), C.byref(rr), C.byref(rep))
         del keep
         try:
-            res = _to_result(rr.ex.result)
-            res.start = dict(rep.info.as_dict(), used=bool(rep.used), reason=int(rep.reason))
-            if res.kind == SolverResult.Optimal:
-                rx = rr.ex
-                arr = lambda p, n: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=p._type_)
-                if rx.has_postsolve:
-                    res.solution._post = (arr(rx.duals, rx.n_duals), arr(rx.reduced_costs, rx.n_reduced_costs), rx.kkt.as_dict())
-                res.solution._basis = dict(B=arr(rr.B_index, rr.n_B), N=arr(rr.N_index, rr.n_N), Nb=arr(rr.N_bound, rr.n_N),
-                                           x=arr(rr.x_std, rr.n_x_std), row_origin=arr(rr.row_origin, rr.n_B))
-                if rr.has_ranging:
-                    res.solution._rng = dict(
-                        cost_down=arr(rr.cost_down, rr.n_cost), cost_up=arr(rr.cost_up, rr.n_cost),
-                        cost_blocking_down=arr(rr.cost_blocking_down, rr.n_cost), cost_blocking_up=arr(rr.cost_blocking_up, rr.n_cost),
-                        rhs_down=arr(rr.rhs_down, rr.n_rhs), rhs_up=arr(rr.rhs_up, rr.n_rhs),
-                        rhs_blocking_down=arr(rr.rhs_blocking_down, rr.n_rhs), rhs_blocking_up=arr(rr.rhs_blocking_up, rr.n_rhs),
-                        inverse_residual=float(rr.inverse_residual), **res.solution._basis)
-            return res
+            return _started_result(rr, rep)
         finally:
             host_lib().ellp_result_rng_free(C.byref(rr))
 
-    def solve_batch(self, problems, postsolve=False):
+    def solve_batch(self, problems, starts=None, postsolve=False):
         """solve() of every problem in `problems`: the device loops of all problems the LU-per-iteration kernels take run
         in batched launches, one workgroup per problem; the others are solved one by one.  The primal solver sends a
         problem to the device once and runs both of its phases there (ellp_batch_primal_solve): the workgroup that ends
@@ -457,9 +444,21 @@ class _Solver:
         solve(p, postsolve=True), from ONE batched call for the whole batch (ellp_batch_postsolve: one workgroup per problem
         up to 128 rows; _engine.batch_postsolve_info() reports its launches, items and chunks); where
         solve(p, postsolve=True) would raise, the entry is that exception.  Off by default, and off means not one extra
+        device call.
+
+        starts: a list as long as `problems` whose entries are None, a dict or a Solution with a basis, as solve(p, start=s)
+        takes them.  Entry k is then solve(problems[k], start=starts[k]) to the bit, and carries its .start where a start was
+        given — but the points of all starts are made in ONE batched call (ellp_batch_basis_start: one workgroup per problem
+        up to 128 rows; _engine.batch_basis_start_info() reports its launches, items and chunks), and phase 2 of the usable
+        starts the batch takes runs in ONE batched call of its own; unusable starts and entries without one join the cold
+        batch.  With starts given — even if every entry is None — every Optimal entry has basis(), so batches chain:
+        r1 = solve_batch(ps, starts=[None] * n); solve_batch(ps2, starts=[r.solution if r.kind == "optimal" else None
+        for r in r1]).  A length mismatch raises ValueError.  starts=None: the call path without starts, not one extra
         device call."""
         problems = list(problems)
         n = len(problems)
+        if starts is not None:
+            return self._solve_batch_start(problems, list(starts), postsolve)
         if n == 0:
             return []
         handles = (C.c_void_p * n)(*[p._h for p in problems])
@@ -505,6 +504,61 @@ class _Solver:
             for r in rs:
                 L.ellp_result_free(C.byref(r))
         return out
+
+
+    def _solve_batch_start(self, problems, starts, postsolve):
+        n = len(problems)
+        if len(starts) != n:
+            raise ValueError(f"solve_batch: {len(starts)} starts for {n} problems")
+        for s in starts:
+            if s is not None and not isinstance(s, (dict, Solution)):
+                raise TypeError("solve_batch: a start is None, a dict(B[, N, Nb]) or a Solution with a basis")
+        if n == 0:
+            return []
+        structs = [None if s is None else _start_struct(s) for s in starts]  # (ellp_start, the arrays it points into)
+        handles = (C.c_void_p * n)(*[p._h for p in problems])
+        sptr = (C.POINTER(_Start) * n)(*[None if st is None else C.pointer(st[0]) for st in structs])
+        rrs, reps = (_ResultRng * n)(), (_StartReport * n)()
+        L = host_lib()
+        s = L.ellp_solve_batch_start(handles, n, self._KIND, self.max_iter, C.byref(self._opts) if self._opts is not None else None,
+                                     1 if postsolve else 0, sptr, rrs, reps)
+        del structs
+        if s == _engine.ERR_ARG:
+            raise ValueError("solve_batch: invalid arguments")
+        out = []
+        try:
+            for k in range(n):
+                try:
+                    out.append(_started_result(rrs[k], reps[k] if starts[k] is not None else None))
+                except Exception as e:  # noqa: BLE001 — the exception solve() would raise, handed back
+                    out.append(e)
+        finally:
+            for rr in rrs:
+                L.ellp_result_rng_free(C.byref(rr))
+        return out
+
+
+def _started_result(rr, rep):
+    """SolverResult from a filled ellp_result_rng of ellp_solve_start / ellp_solve_batch_start: .start from the report (None: the
+    problem had no start), and on Optimal the postsolve, the basis and the ranging that came with it"""
+    res = _to_result(rr.ex.result)
+    if rep is not None:
+        res.start = dict(rep.info.as_dict(), used=bool(rep.used), reason=int(rep.reason))
+    if res.kind == SolverResult.Optimal:
+        rx = rr.ex
+        arr = lambda p, n: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=p._type_)
+        if rx.has_postsolve:
+            res.solution._post = (arr(rx.duals, rx.n_duals), arr(rx.reduced_costs, rx.n_reduced_costs), rx.kkt.as_dict())
+        res.solution._basis = dict(B=arr(rr.B_index, rr.n_B), N=arr(rr.N_index, rr.n_N), Nb=arr(rr.N_bound, rr.n_N),
+                                   x=arr(rr.x_std, rr.n_x_std), row_origin=arr(rr.row_origin, rr.n_B))
+        if rr.has_ranging:
+            res.solution._rng = dict(
+                cost_down=arr(rr.cost_down, rr.n_cost), cost_up=arr(rr.cost_up, rr.n_cost),
+                cost_blocking_down=arr(rr.cost_blocking_down, rr.n_cost), cost_blocking_up=arr(rr.cost_blocking_up, rr.n_cost),
+                rhs_down=arr(rr.rhs_down, rr.n_rhs), rhs_up=arr(rr.rhs_up, rr.n_rhs),
+                rhs_blocking_down=arr(rr.rhs_blocking_down, rr.n_rhs), rhs_blocking_up=arr(rr.rhs_blocking_up, rr.n_rhs),
+                inverse_residual=float(rr.inverse_residual), **res.solution._basis)
+    return res
 
 
 def _start_struct(start):

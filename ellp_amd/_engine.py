@@ -260,6 +260,12 @@ def lib():
     L.ellp_batch_postsolve.argtypes = [C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
     L.ellp_batch_postsolve_info.restype = None
     L.ellp_batch_postsolve_info.argtypes = [C.POINTER(C.c_uint64)]
+    L.ellp_batch_solve_info.restype = None
+    L.ellp_batch_solve_info.argtypes = [C.POINTER(C.c_uint64)]
+    L.ellp_batch_basis_start.restype = C.c_int
+    L.ellp_batch_basis_start.argtypes = [C.c_int64, C.c_void_p, C.c_int, C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.ellp_batch_basis_start_info.restype = None
+    L.ellp_batch_basis_start_info.argtypes = [C.POINTER(C.c_uint64)]
     L.ellp_basis_start.restype = C.c_int
     L.ellp_basis_start.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                    C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StartInfo), C.c_char_p, C.c_size_t]
@@ -500,6 +506,14 @@ def batch_solve_with_initial(kind, flat_problems, opts=None):
     return [(status[k], stats[k], items[k].err.decode()) for k in range(n)]
 
 
+def batch_solve_info():
+    """ellp_batch_solve_info: the calling thread's calls of ellp_batch_solve_with_initial: how many so far, the items and the
+    kind of the last one."""
+    out = (C.c_uint64 * 4)()
+    lib().ellp_batch_solve_info(out)
+    return {"calls": int(out[0]), "items": int(out[1]), "kind": int(out[2])}
+
+
 class BatchPostOut(C.Structure):
     """ellp_batch_post_out (include/ellp_hip.h)"""
     _fields_ = [("y", C.c_void_p), ("d", C.c_void_p), ("r", C.c_void_p), ("kkt", C.POINTER(Kkt))]
@@ -541,6 +555,52 @@ def batch_postsolve_info():
     on the batched kernel, items on the single path (inside the call), chunks."""
     out = (C.c_uint64 * 4)()
     lib().ellp_batch_postsolve_info(out)
+    return {"launches": int(out[0]), "batched": int(out[1]), "single": int(out[2]), "chunks": int(out[3])}
+
+
+def batch_basis_start(flat_problems, mode=START_KEEP_LABELS, opts=None, fill=0.0):
+    """ellp_batch_basis_start: the point of the basis of every FlatProblem (as basis_start reads it: B, N and Nb; n_c == n) in
+    one batched call, with the bits of basis_start(fp, mode) per problem.  Returns one (status, x, y, d, Nb, info_dict) per
+    problem; status is OPTIMAL, ERR_ARG or ERR_SINGULAR, and where it is not OPTIMAL x, y, d are as they were made (every
+    entry `fill`), Nb is the copy of the given labels (the call does not touch either) and info_dict holds only the message.
+    The problems themselves are not changed.  Raises EllpHipError if the call as a whole is refused (mode, device)."""
+    fps = list(flat_problems)
+    n = len(fps)
+    items = (BatchItem * max(n, 1))()
+    infos = (StartInfo * max(n, 1))()
+    arrays = []
+    for it, fp in zip(items, fps):
+        x, y, d = np.full(max(fp.n, 0), fill), np.full(max(fp.m, 0), fill), np.full(max(fp.n, 0), fill)
+        Nb = fp.Nb.copy()
+        arrays.append((x, y, d, Nb))
+        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
+        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
+        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(x)
+        it.B_index, it.n_B = _p(fp.B), fp.nB
+        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(Nb), fp.nN
+        it.y, it.d = _p(y), _p(d)
+    status = (C.c_int * max(n, 1))()
+    o = opts or default_opts()
+    err = C.create_string_buffer(512)
+    s = lib().ellp_batch_basis_start(n, items, int(mode), C.byref(o), infos, status, err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    out = []
+    for k in range(n):
+        if status[k] == OPTIMAL:
+            info = infos[k].as_dict()
+            info["message"] = ""
+        else:
+            info = {"message": items[k].err.decode()}
+        out.append((status[k], *arrays[k], info))
+    return out
+
+
+def batch_basis_start_info():
+    """ellp_batch_basis_start_info: the calling thread's last ellp_batch_basis_start: kernel launches of the batched path,
+    items on the batched kernel, items on the single path (inside the call), chunks."""
+    out = (C.c_uint64 * 4)()
+    lib().ellp_batch_basis_start_info(out)
     return {"launches": int(out[0]), "batched": int(out[1]), "single": int(out[2]), "chunks": int(out[3])}
 
 

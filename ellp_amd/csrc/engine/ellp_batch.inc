@@ -658,9 +658,20 @@ static ellp_status batch_solve_impl(int kind, int64_t count, ellp_batch_item *it
     return ELLP_OPTIMAL;
 }
 
+// the calling thread's calls of ellp_batch_solve_with_initial (ellp_batch_solve_info): how many so far, the last one's items and kind
+static thread_local uint64_t g_batch_solve_info[4] = {0, 0, 0, 0};
+
+extern "C" void ellp_batch_solve_info(uint64_t *out4) {
+    if (!out4) return;
+    for (int k = 0; k < 4; ++k) out4[k] = g_batch_solve_info[k];
+}
+
 extern "C" ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, ellp_batch_item *items, const ellp_opts *opts_in,
                                                      ellp_status *status_out, ellp_stats *stats_out, char *errbuf,
                                                      size_t errlen) {
+    g_batch_solve_info[0] += 1;
+    g_batch_solve_info[1] = count > 0 ? (uint64_t)count : 0;
+    g_batch_solve_info[2] = (uint64_t)kind;
     return batch_solve_impl(kind, count, items, opts_in, status_out, stats_out, nullptr, errbuf, errlen);
 }
 

@@ -42,10 +42,12 @@ struct PostBatchArgs {
     PostReportArgs rep;  // the item as the report sees it (m, n, n_c, nN, c_B, c_tail, x, b, the index sets)
 };
 
-// bytes of dynamic LDS k_post_batch needs (0: does not fit); the cap is small_lds_bytes'
-inline size_t bpost_lds_bytes(int64_t m) {
+// bytes of dynamic LDS k_post_batch needs (0: does not fit); the cap is small_lds_bytes'.  extra: vectors of m doubles a
+// kernel built on it keeps besides (k_start_batch, ellp_bstart.inc)
+inline size_t bpost_lds_bytes(int64_t m, int extra = 0) {
     if (m > SMALL_MAX_M || m < 1) return 0;
     size_t b = sizeof(double) * (size_t)(m * m)             // LU
+               + sizeof(double) * (size_t)(extra * m)
                + sizeof(double) * BPOST_ROWS                // y, zero beyond m
                + sizeof(double) * (size_t)(5 * m)           // c_B, rho, den, the vector of a solve, singleton values
                + sizeof(double) * 2 * BPOST_ROWS * 2        // r: the two basic blocks
@@ -88,11 +90,12 @@ __device__ __forceinline__ void bpost_btran(const double *LU, int m, double *v, 
 }
 
 // k_post_pass + k_post_dfold over the stored columns C (one row tile), and the block sums of r: BASIC keeps them per block
-// in rbas (the last pass over A_B counts), else they are merged into the fold (fs, fc) of thread i = row i at once
+// in rbas (the last pass over A_B counts), else they are merged into the fold (fs, fc) of thread i = row i at once, and
+// kept per block in rkeep (global memory, as rbas is laid out) where that is given
 template <bool BASIC>
 __device__ __forceinline__ void bpost_pass(const double *C, const int64_t *index, const double *cpos, const double *x, double *d, int m,
                                            int64_t ld, int64_t ncols, const double *ysh, double *rho, double *den, double *rbas,
-                                           double *rsh, double &fs, double &fc, int tid) {
+                                           double *rsh, double *rkeep, double &fs, double &fc, int tid) {
     const int lane = tid & 63, wave = tid >> 6;
     const bool ok0 = 2 * lane < m, ok1 = 2 * lane + 1 < m;
     const double yv0 = ysh[2 * lane], yv1 = ysh[2 * lane + 1];
@@ -149,42 +152,59 @@ __device__ __forceinline__ void bpost_pass(const double *C, const int64_t *index
                 rbas[(blk * BPOST_ROWS + tid) * 2 + 1] = c;
             } else {
                 post_merge(fs, fc, -s, -c);
+                if (rkeep) {
+                    rkeep[(blk * BPOST_ROWS + tid) * 2] = s;
+                    rkeep[(blk * BPOST_ROWS + tid) * 2 + 1] = c;
+                }
             }
         }
         __syncthreads();
     }
 }
 
-__global__ __launch_bounds__(BPOST_NT) void k_post_batch(const PostBatchArgs *args) {
-    extern __shared__ __align__(16) unsigned char smem[];
+// the carve of the dynamic LDS: bpost_lds_bytes(m, extra), the extra vectors between rsh and the integers
+struct BpostSh {
+    double *LU, *ysh, *cB, *rho, *den, *sv, *sval, *rbas, *rsh, *extra;
+    int32_t *srow, *pa, *pb, *lop;
+};
+__device__ __forceinline__ BpostSh bpost_carve(unsigned char *smem, int m, int extra) {
+    BpostSh s;
+    s.LU = reinterpret_cast<double *>(smem);
+    s.ysh = s.LU + m * m;
+    s.cB = s.ysh + BPOST_ROWS;
+    s.rho = s.cB + m;
+    s.den = s.rho + m;
+    s.sv = s.den + m;
+    s.sval = s.sv + m;
+    s.rbas = s.sval + m;
+    s.rsh = s.rbas + 2 * BPOST_ROWS * 2;
+    s.extra = s.rsh + 4 * BPOST_ROWS * 2;
+    s.srow = reinterpret_cast<int32_t *>(s.extra + extra * m);
+    s.pa = s.srow + m;
+    s.pb = s.pa + m;
+    s.lop = s.pb + m;
+    return s;
+}
+
+// Steps 1 and 2 of an item, shared by k_post_batch and k_start_batch: the basis into LDS, its singleton columns, its LU,
+// y = B^-T c_B and the refinement loop of y (post_solve_y's).  false: a zero on U's diagonal, nothing was written.  On
+// return sh.ysh holds y; sh.rho, sh.den, sh.rbas and d on the basis are those of the last pass over A_B (with the x given);
+// *plen the length of the swap list; omega and steps of y
+__device__ __forceinline__ bool bpost_solve_y(const BpostSh &sh, const double *A_B, const PostReportArgs &rep, const double *x, double *d,
+                                              int m, int64_t ld, int *plen, double *s_bc, double &omega, int32_t &steps, int tid) {
     __shared__ double s_wv[8], s_wd[8];
     __shared__ int s_wi[8], s_wp[8];
-    __shared__ double s_bc[2];
     __shared__ double s_omega;
-    __shared__ int s_plen;
-    const PostBatchArgs a = args[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int m = (int)a.rep.m;
-    const int64_t ld = a.ld, nN = a.rep.nN;
-    double *LU = reinterpret_cast<double *>(smem);
-    double *ysh = LU + m * m;
-    double *cB = ysh + BPOST_ROWS;
-    double *rho = cB + m;
-    double *den = rho + m;
-    double *sv = den + m;
-    double *sval = sv + m;
-    double *rbas = sval + m;
-    double *rsh = rbas + 2 * BPOST_ROWS * 2;
-    int32_t *srow = reinterpret_cast<int32_t *>(rsh + 4 * BPOST_ROWS * 2);
-    int32_t *pa = srow + m, *pb = pa + m, *lop = pb + m;
-
+    const int lane = tid & 63;
+    double *LU = sh.LU, *ysh = sh.ysh, *cB = sh.cB, *rho = sh.rho, *den = sh.den, *sv = sh.sv, *sval = sh.sval;
+    int32_t *srow = sh.srow;
     // ---- A_B into LDS by columns (ld = m), c_B, y = 0
     for (int e = tid; e < m * m; e += BPOST_NT) {
         const int j = e / m, i = e - j * m;
-        LU[e] = a.A_B[j * ld + i];
+        LU[e] = A_B[j * ld + i];
     }
     for (int i = tid; i < BPOST_ROWS; i += BPOST_NT) ysh[i] = 0.0;
-    if (tid < m) cB[tid] = a.rep.c_B[tid];
+    if (tid < m) cB[tid] = rep.c_B[tid];
     __syncthreads();
     // ---- the columns with a single nonzero (k_post_singletons): thread j scans column j, from row j on (LDS banks)
     if (tid < m) {
@@ -203,18 +223,14 @@ __global__ __launch_bounds__(BPOST_NT) void k_post_batch(const PostBatchArgs *ar
         sval[tid] = cnt == 1 ? val : 0.0;
     }
     __syncthreads();
-    small_lu<BPOST_NT>(LU, m, pa, pb, &s_plen, lop, s_wv, s_wd, s_wi, s_wp, tid);
-    // a zero on U's diagonal: the item's flag, and nothing else of the item is written
-    const int zero = __syncthreads_or(tid < m && LU[tid * m + tid] == 0.0);
-    if (zero) {
-        if (tid == 0) *a.fail = 1;
-        return;
-    }
-    const int plen = s_plen;
+    small_lu<BPOST_NT>(LU, m, sh.pa, sh.pb, plen, sh.lop, s_wv, s_wd, s_wi, s_wp, tid);
+    // a zero on U's diagonal: the item's flag (set by the caller), and nothing else of the item is written
+    if (__syncthreads_or(tid < m && LU[tid * m + tid] == 0.0)) return false;
+    const int pl = *plen;
     // ---- y = B^-T c_B, the singletons imposed
     if (tid < m) sv[tid] = cB[tid];
     __syncthreads();
-    bpost_btran(LU, m, sv, pa, pb, plen, s_bc, tid);
+    bpost_btran(LU, m, sv, sh.pa, sh.pb, pl, s_bc, tid);
     if (tid < m) ysh[tid] = sv[tid];
     __syncthreads();
     if (tid < m && srow[tid] >= 0) ysh[srow[tid]] = cB[tid] / sval[tid];
@@ -222,9 +238,9 @@ __global__ __launch_bounds__(BPOST_NT) void k_post_batch(const PostBatchArgs *ar
     // ---- the pass over the basic columns and the refinement loop, post_solve_y's
     const double two_u = 2.220446049250313e-16;  // 2 u, u = 2^-53
     double last = 0.0, fs = 0.0, fc = 0.0;
-    int32_t steps = 0;
+    steps = 0;
     for (;;) {
-        bpost_pass<true>(a.A_B, a.rep.B_index, cB, a.rep.x, a.d, m, ld, m, ysh, rho, den, rbas, rsh, fs, fc, tid);
+        bpost_pass<true>(A_B, rep.B_index, cB, x, d, m, ld, m, ysh, rho, den, sh.rbas, sh.rsh, nullptr, fs, fc, tid);
         if (tid < 64) {  // k_post_omega
             PostMax mine{0.0, LLONG_MAX_POST};
             for (int i = lane; i < m; i += 64) mine = post_max(mine, PostMax{post_ratio(rho[i], den[i]), (long long)i});
@@ -238,11 +254,11 @@ __global__ __launch_bounds__(BPOST_NT) void k_post_batch(const PostBatchArgs *ar
             if (lane == 0) s_omega = mine.v;
         }
         __syncthreads();
-        const double omega = s_omega;
+        omega = s_omega;
         if (!(omega > two_u) || steps >= 4 || (steps > 0 && !(omega <= 0.5 * last))) break;
         if (tid < m) sv[tid] = rho[tid];
         __syncthreads();
-        bpost_btran(LU, m, sv, pa, pb, plen, s_bc, tid);
+        bpost_btran(LU, m, sv, sh.pa, sh.pb, pl, s_bc, tid);
         if (tid < m) ysh[tid] = ysh[tid] + sv[tid];
         __syncthreads();
         if (tid < m && srow[tid] >= 0) ysh[srow[tid]] = cB[tid] / sval[tid];
@@ -250,22 +266,40 @@ __global__ __launch_bounds__(BPOST_NT) void k_post_batch(const PostBatchArgs *ar
         last = omega;
         steps += 1;
     }
+    return true;
+}
+
+__global__ __launch_bounds__(BPOST_NT) void k_post_batch(const PostBatchArgs *args) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ double s_bc[2];
+    __shared__ int s_plen;
+    const PostBatchArgs a = args[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int m = (int)a.rep.m;
+    const int64_t ld = a.ld, nN = a.rep.nN;
+    const BpostSh sh = bpost_carve(smem, m, 0);
+    double omega = 0.0, fs = 0.0, fc = 0.0;
+    int32_t steps = 0;
+    if (!bpost_solve_y(sh, a.A_B, a.rep, a.rep.x, a.d, m, ld, &s_plen, s_bc, omega, steps, tid)) {
+        if (tid == 0) *a.fail = 1;
+        return;
+    }
     // ---- r from b, the basic blocks first, then the nonbasic ones as their pass delivers them; d on the way
     if (tid < m) {
         fs = a.rep.b[tid];
         fc = 0.0;
         const int nbb = (m + 63) / 64;
-        for (int k = 0; k < nbb; ++k) post_merge(fs, fc, -rbas[(k * BPOST_ROWS + tid) * 2], -rbas[(k * BPOST_ROWS + tid) * 2 + 1]);
+        for (int k = 0; k < nbb; ++k) post_merge(fs, fc, -sh.rbas[(k * BPOST_ROWS + tid) * 2], -sh.rbas[(k * BPOST_ROWS + tid) * 2 + 1]);
     }
-    bpost_pass<false>(a.A_N, a.rep.N_index, a.c_N, a.rep.x, a.d, m, ld, nN, ysh, rho, den, rbas, rsh, fs, fc, tid);
+    bpost_pass<false>(a.A_N, a.rep.N_index, a.c_N, a.rep.x, a.d, m, ld, nN, sh.ysh, sh.rho, sh.den, sh.rbas, sh.rsh, nullptr, fs, fc, tid);
     for (int64_t v = a.rep.n + tid; v < a.rep.n_c; v += BPOST_NT) a.d[v] = a.rep.c_tail[v - a.rep.n];
     if (tid < m) {
         a.r[tid] = fs + fc;
-        a.y[tid] = ysh[tid];
-        a.rho[tid] = rho[tid];
+        a.y[tid] = sh.ysh[tid];
+        a.rho[tid] = sh.rho[tid];
     }
     if (tid == 0) {
-        *a.omega = s_omega;
+        *a.omega = omega;
         *a.steps = steps;
     }
 }
@@ -343,6 +377,22 @@ BpostLayout bpost_layout(const ellp_batch_item *items, BpostPlan *plan, size_t R
     }
     L.total = off;
     return L;
+}
+
+// chunks: consecutive items within the budget (an item alone over it is a chunk of its own); plan[k].bytes is item k's share
+template <typename Plan>
+std::vector<size_t> bpost_cuts(const std::vector<Plan> &plan, size_t budget) {
+    std::vector<size_t> cut{0};
+    size_t acc = BPOST_CHUNK_SLACK;
+    for (size_t k = 0; k < plan.size(); ++k) {
+        if (k > cut.back() && (acc + plan[k].bytes > budget || k - cut.back() >= 65535)) {
+            cut.push_back(k);
+            acc = BPOST_CHUNK_SLACK;
+        }
+        acc += plan[k].bytes;
+    }
+    cut.push_back(plan.size());
+    return cut;
 }
 
 // the calling thread's last ellp_batch_postsolve that passed the checks of the call (ellp_batch_postsolve_info)
@@ -505,18 +555,9 @@ extern "C" ellp_status ellp_batch_postsolve(int64_t count, ellp_batch_item *item
 
     if (!plan.empty()) {
         // ---- chunks: consecutive items within the budget (an item alone over it is a chunk of its own)
-        std::vector<size_t> cut{0};
         size_t max_stage = 0, max_total = 0;
         (void)bpost_layout(items, plan.data(), plan.size());  // every item's share of a slab
-        size_t acc = BPOST_CHUNK_SLACK;
-        for (size_t k = 0; k < plan.size(); ++k) {
-            if (k > cut.back() && (acc + plan[k].bytes > budget || k - cut.back() >= 65535)) {
-                cut.push_back(k);
-                acc = BPOST_CHUNK_SLACK;
-            }
-            acc += plan[k].bytes;
-        }
-        cut.push_back(plan.size());
+        const std::vector<size_t> cut = bpost_cuts(plan, budget);
         for (size_t c = 0; c + 1 < cut.size(); ++c) {
             const BpostLayout L = bpost_layout(items, plan.data() + cut[c], cut[c + 1] - cut[c]);
             max_stage = L.stage_bytes > max_stage ? L.stage_bytes : max_stage;

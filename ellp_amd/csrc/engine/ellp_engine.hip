@@ -4809,4 +4809,5 @@ ellp_status ellp_dual_solve_with_initial(int64_t m, int64_t n, int64_t n_c, cons
 #include "ellp_post.inc"
 #include "ellp_bpost.inc"
 #include "ellp_start.inc"
+#include "ellp_bstart.inc"
 #include "ellp_range.inc"

@@ -40,7 +40,25 @@ struct StartLabelArgs {
     int by_d;
     unsigned long long *changed;
 };
-// position j of N: label and value by kind (TwoSided: the given label, or the sign of d); position i of B: x = +0.0
+// the label and the value of the nonbasic variable v by its kind (TwoSided: the given label, or the sign of d); shared
+// with k_start_batch (ellp_bstart.inc)
+__device__ __forceinline__ void start_label(const uint8_t *kind, const double *lb, const double *ub, const double *d, int by_d, int64_t v,
+                                            int old, int &label, double &val) {
+    label = ELLP_NB_LOWER;
+    val = 0.0;
+    switch (kind[v]) {
+    case ELLP_BOUND_FREE: label = ELLP_NB_FREE; val = 0.0; break;
+    case ELLP_BOUND_LOWER: label = ELLP_NB_LOWER; val = lb[v]; break;
+    case ELLP_BOUND_UPPER: label = ELLP_NB_UPPER; val = ub[v]; break;
+    case ELLP_BOUND_TWOSIDED:
+        if (by_d) label = (d[v] < 0.0) ? ELLP_NB_UPPER : ELLP_NB_LOWER;  // d >= 0 or NaN: Lower
+        else label = (old == ELLP_NB_UPPER) ? ELLP_NB_UPPER : ELLP_NB_LOWER;  // a given Free: Lower
+        val = (label == ELLP_NB_UPPER) ? ub[v] : lb[v];
+        break;
+    default: label = ELLP_NB_LOWER; val = lb[v]; break;  // Fixed
+    }
+}
+// position j of N: label and value by kind; position i of B: x = +0.0
 __global__ __launch_bounds__(256) void k_start_labels(StartLabelArgs a) {
     __shared__ int cnt[256];
     const int tid = threadIdx.x;
@@ -49,19 +67,9 @@ __global__ __launch_bounds__(256) void k_start_labels(StartLabelArgs a) {
     if (j < a.nN) {
         const int64_t v = a.N_index[j];
         const int old = a.Nb[j];
-        int label = ELLP_NB_LOWER;
-        double val = 0.0;
-        switch (a.kind[v]) {
-        case ELLP_BOUND_FREE: label = ELLP_NB_FREE; val = 0.0; break;
-        case ELLP_BOUND_LOWER: label = ELLP_NB_LOWER; val = a.lb[v]; break;
-        case ELLP_BOUND_UPPER: label = ELLP_NB_UPPER; val = a.ub[v]; break;
-        case ELLP_BOUND_TWOSIDED:
-            if (a.by_d) label = (a.d[v] < 0.0) ? ELLP_NB_UPPER : ELLP_NB_LOWER;  // d >= 0 or NaN: Lower
-            else label = (old == ELLP_NB_UPPER) ? ELLP_NB_UPPER : ELLP_NB_LOWER;  // a given Free: Lower
-            val = (label == ELLP_NB_UPPER) ? a.ub[v] : a.lb[v];
-            break;
-        default: label = ELLP_NB_LOWER; val = a.lb[v]; break;  // Fixed
-        }
+        int label;
+        double val;
+        start_label(a.kind, a.lb, a.ub, a.d, a.by_d, v, old, label, val);
         a.x[v] = val;
         a.Nb[j] = (uint8_t)label;
         ch = label != old;
@@ -158,8 +166,10 @@ struct StartVerdictArgs {
     double eps;
     StartVerdict *out;
 };
-// the bound violations of the BASIC positions (the nonbasic ones sit on their bounds by construction), and the two flags
-__global__ __launch_bounds__(1024) void k_start_verdict(StartVerdictArgs a) {
+// the bound violations of the BASIC positions (the nonbasic ones sit on their bounds by construction), and the two flags.
+// One workgroup of 1,024 threads: k_start_verdict runs it for the single call, k_start_report_batch (ellp_bstart.inc) once
+// per item of a batch
+__device__ __forceinline__ void start_verdict(const StartVerdictArgs &a) {
     __shared__ PostMax sh[1024];
     __shared__ double shs[1024], shc[1024];
     const int tid = threadIdx.x;
@@ -195,6 +205,7 @@ __global__ __launch_bounds__(1024) void k_start_verdict(StartVerdictArgs a) {
         *a.out = o;
     }
 }
+__global__ __launch_bounds__(1024) void k_start_verdict(StartVerdictArgs a) { start_verdict(a); }
 
 // t or a residual from the partial sums of the pass: base - (the blocks first .. first + count), in block order
 void start_fold(ellp_engine *e, int64_t first, int64_t count, const double *base, double *out) {
@@ -203,16 +214,10 @@ void start_fold(ellp_engine *e, int64_t first, int64_t count, const double *base
                        count);
 }
 
-}  // namespace
-
-extern "C" {
-
-ellp_status ellp_basis_start(int64_t m, int64_t n, const double *A, const double *c, const double *b, const uint8_t *bound_kind,
-                             const double *lb, const double *ub, const int64_t *B_index, int64_t n_B, const int64_t *N_index,
-                             uint8_t *N_bound, int64_t n_N, int mode, const ellp_opts *opts_in, double *x, double *y, double *d,
-                             ellp_start_info *info, char *errbuf, size_t errlen) {
-    if (errbuf && errlen) errbuf[0] = 0;
-    // every refusal below is answered before any HIP call
+// the refusals of ellp_basis_start, host only (ellp_batch_basis_start makes them per item)
+ellp_status start_host_checks(int64_t m, int64_t n, const double *A, const double *c, const double *b, const uint8_t *bound_kind,
+                              const double *lb, const double *ub, const int64_t *B_index, int64_t n_B, const int64_t *N_index,
+                              const uint8_t *N_bound, int64_t n_N, int mode, const double *x, char *errbuf, size_t errlen) {
     if (mode != ELLP_START_KEEP_LABELS && mode != ELLP_START_LABELS_BY_D) {
         set_err(errbuf, errlen, "basis_start: unknown mode %d", mode);
         return ELLP_ERR_ARG;
@@ -256,9 +261,24 @@ ellp_status ellp_basis_start(int64_t m, int64_t n, const double *A, const double
             set_err(errbuf, errlen, "basis_start: bound_kind[%lld] out of range", (long long)v);
             return ELLP_ERR_ARG;
         }
+    return post_host_checks("basis_start", m, n, n, A, c, b, bound_kind, lb, ub, x, B_index, n_B, N_index, N_bound, n_N, errbuf, errlen);
+}
+
+}  // namespace
+
+extern "C" {
+
+ellp_status ellp_basis_start(int64_t m, int64_t n, const double *A, const double *c, const double *b, const uint8_t *bound_kind,
+                             const double *lb, const double *ub, const int64_t *B_index, int64_t n_B, const int64_t *N_index,
+                             uint8_t *N_bound, int64_t n_N, int mode, const ellp_opts *opts_in, double *x, double *y, double *d,
+                             ellp_start_info *info, char *errbuf, size_t errlen) {
+    if (errbuf && errlen) errbuf[0] = 0;
+    // every refusal is answered before any HIP call
+    ellp_status s = start_host_checks(m, n, A, c, b, bound_kind, lb, ub, B_index, n_B, N_index, N_bound, n_N, mode, x, errbuf, errlen);
+    if (s != ELLP_OPTIMAL) return s;
     const std::vector<double> zeros((size_t)n, 0.0);
     PostOwn own(nullptr, ellp_engine_destroy);
-    ellp_status s = post_host_engine("basis_start", m, n, n, A, c, b, bound_kind, lb, ub, zeros.data(), B_index, n_B, N_index, N_bound, n_N,
+    s = post_host_engine("basis_start", m, n, n, A, c, b, bound_kind, lb, ub, zeros.data(), B_index, n_B, N_index, N_bound, n_N,
                                      opts_in, own, errbuf, errlen);
     if (s != ELLP_OPTIMAL) return s;
     ellp_engine *e = own.get();

@@ -384,6 +384,53 @@ int ellp_solve_batch_ex(const ellp_problem *const *probs, int64_t count, int sol
     return ELLP_OPTIMAL;
 }
 
+int ellp_solve_batch_start(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+                           unsigned flags, const ellp_start *const *starts, ellp_result_rng *out, ellp_start_report *reports) {
+    if (count < 0 || !probs || !starts || !out || !reports || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL) ||
+        (flags & ~ELLP_SOLVE_POSTSOLVE))  // ELLP_SOLVE_RANGING too: there is no batched ranging
+        return ELLP_ERR_ARG;
+    for (int64_t k = 0; k < count; ++k)
+        if (!probs[k]) return ELLP_ERR_ARG;
+    for (int64_t k = 0; k < count; ++k) {
+        std::memset(&out[k], 0, sizeof(out[k]));
+        std::memset(&reports[k], 0, sizeof(reports[k]));
+    }
+    std::vector<ellp::Problem> ps;
+    ps.reserve(static_cast<size_t>(count));
+    std::vector<ellp::StartBasis> sb(static_cast<size_t>(count));
+    std::vector<const ellp::StartBasis *> sp(static_cast<size_t>(count), nullptr);
+    std::vector<ellp::StartReport> rep;
+    std::vector<ellp::BatchOutcome> res;
+    try {
+        for (int64_t k = 0; k < count; ++k) {
+            ps.push_back(probs[k]->prob);
+            if (starts[k]) {
+                sb[static_cast<size_t>(k)] = start_basis(starts[k]);
+                sp[static_cast<size_t>(k)] = &sb[static_cast<size_t>(k)];
+            }
+        }
+        res = ellp::solve_batch(solver, std::move(ps), max_iter, engine_options(opts), (flags & ELLP_SOLVE_POSTSOLVE) != 0, &sp, &rep);
+    } catch (const std::exception &e) {  // host memory: the batch as a whole
+        for (int64_t k = 0; k < count; ++k) {
+            out[k].ex.result.status = ELLP_ERR_DEVICE;
+            put(out[k].ex.result.err, sizeof(out[k].ex.result.err), e.what());
+        }
+        return ELLP_ERR_DEVICE;
+    }
+    for (int64_t k = 0; k < count; ++k) {
+        ellp_result base;
+        fill_result(&base, [&] {
+            if (res[k].error) std::rethrow_exception(res[k].error);
+            return std::move(res[k].result);
+        }, &out[k].ex, &out[k], /*basis_always=*/true);
+        out[k].ex.result = base;
+        reports[k].used = rep[static_cast<size_t>(k)].used ? 1 : 0;
+        reports[k].reason = rep[static_cast<size_t>(k)].reason;
+        reports[k].info = rep[static_cast<size_t>(k)].info;
+    }
+    return ELLP_OPTIMAL;
+}
+
 static void fill_flat(ellp_flat_phase *o, const ellp::StandardForm &sf, const ellp::Point &pt,
                       const std::vector<double> *y, const std::vector<double> *d) {
     auto dupd = [](const std::vector<double> &v) {

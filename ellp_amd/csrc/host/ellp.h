@@ -318,8 +318,15 @@ struct BatchOutcome {
 };
 // postsolve: every Optimal outcome's Solution carries duals(), reduced_costs() and kkt(), from ONE ellp_batch_postsolve call for
 // the whole batch, with the bits of solve() with_postsolve(true); false: not one extra device call
+// starts (one entry per problem, null: none): the warm start of solve_from for a batch.  The points of all
+// mapped starts come from ONE ellp_batch_basis_start call, phase 2 of the usable ones the batch takes runs in ONE
+// ellp_batch_solve_with_initial call of their own (iters_phase1 = 0), a usable one it does not take runs phase 2 alone from
+// the point already made, and the problems without a usable start join the cold batch.  Outcome k is solve_from's (the
+// postsolve by the one batched call); (*reports)[k] its StartReport (untouched defaults for a problem without a start).
+// starts null: the cold batch alone, not one extra device call.  Throws std::invalid_argument on a length mismatch
 std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng,
-                                      bool postsolve = false);
+                                      bool postsolve = false, const std::vector<const StartBasis *> *starts = nullptr,
+                                      std::vector<StartReport> *reports = nullptr);
 
 // src/parse_mps.rs:11-66.  Variables/rows are taken in file order (the reference iterates
 // HashMaps, so its order is unspecified).

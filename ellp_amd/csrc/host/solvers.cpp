@@ -9,6 +9,7 @@
 #include <cstring>
 #include <exception>
 #include <limits>
+#include <stdexcept>
 #include <type_traits>
 
 #include "ellp.h"
@@ -585,11 +586,30 @@ int start_point(const StandardForm &sf, const StartBasis &start, int mode, const
     return START_USED;
 }
 
+// what a warm start makes of phase 2's status, the phase-2 switch of solve(): shared by run_from_start and by solve_batch's
+// batched phase 2 of the started problems
+void end_from_start(int kind, SolutionStatus s2, StandardForm &sf, DualFeasiblePoint &dp, SolverResult &res) {
+    if (kind == ELLP_ENGINE_PRIMAL) {
+        if (s2 == SolutionStatus::Infeasible) throw EllPPanic("primal phase 2 should never be infeasible");
+        if (s2 == SolutionStatus::Unbounded) { res.kind = SolverResult::Unbounded; return; }
+    } else {
+        if (s2 == SolutionStatus::Unbounded) throw EllPPanic("dual phase 2 should never return unbounded");
+        if (s2 == SolutionStatus::Infeasible) { res.kind = SolverResult::Infeasible; return; }
+    }
+    if (s2 == SolutionStatus::MaxIter) {
+        res.kind = SolverResult::MaxIter;
+        res.max_iter_obj = kind == ELLP_ENGINE_DUAL ? sf.dual_obj(dp.y, dp.d) : sf.obj(dp.point.x);
+        return;
+    }
+    res.kind = SolverResult::Optimal;
+    res.solution = Solution{std::move(sf), std::move(dp.point), std::nullopt, std::nullopt};
+}
+
 // phase 2 from the point of a usable start, on a resident engine where the seam sends the problem to the device
-// (plain: the seam's call for a problem without nonbasic columns, as in solve(); map_status: the phase-2 switch of solve())
-template <class Plain, class MapStatus>
+// (plain: the seam's call for a problem without nonbasic columns, as in solve())
+template <class Plain>
 SolverResult run_from_start(int kind, StandardForm sf, DualFeasiblePoint dp, std::uint64_t max_iter, const EngineOptions &engine,
-                            bool postsolve, bool ranging, Plain &&plain, MapStatus &&map_status) {
+                            bool postsolve, bool ranging, Plain &&plain) {
     SolverResult res;
     EngineHandle eng;
     SolutionStatus s2;
@@ -608,17 +628,22 @@ SolverResult run_from_start(int kind, StandardForm sf, DualFeasiblePoint dp, std
     } else {
         s2 = plain(sf, dp, &res.iters_phase2);
     }
-    if (!map_status(s2, res)) return res;
-    if (s2 == SolutionStatus::MaxIter) {
-        res.kind = SolverResult::MaxIter;
-        res.max_iter_obj = kind == ELLP_ENGINE_DUAL ? sf.dual_obj(dp.y, dp.d) : sf.obj(dp.point.x);
-        return res;
-    }
-    res.kind = SolverResult::Optimal;
-    res.solution = Solution{std::move(sf), std::move(dp.point), std::nullopt, std::nullopt};
+    end_from_start(kind, s2, sf, dp, res);
+    if (res.kind != SolverResult::Optimal || !res.solution) return res;
     if (ranging) attach_ranging(*res.solution, eng.e, engine);
     else if (postsolve) attach_postsolve(*res.solution, eng.e, engine);
     return res;
+}
+
+SolverResult primal_from_point(const PrimalSimplexSolver &single, StandardForm sf, DualFeasiblePoint dp, std::uint64_t max_iter,
+                               const EngineOptions &engine, bool postsolve, bool ranging) {
+    return run_from_start(ELLP_ENGINE_PRIMAL, std::move(sf), std::move(dp), max_iter, engine, postsolve, ranging,
+                          [&single](const StandardForm &f, DualFeasiblePoint &p, std::uint64_t *it) { return single.solve_with_initial(f, p.point, it); });
+}
+SolverResult dual_from_point(const DualSimplexSolver &single, StandardForm sf, DualFeasiblePoint dp, std::uint64_t max_iter,
+                             const EngineOptions &engine, bool postsolve, bool ranging) {
+    return run_from_start(ELLP_ENGINE_DUAL, std::move(sf), std::move(dp), max_iter, engine, postsolve, ranging,
+                          [&single](const StandardForm &f, DualFeasiblePoint &p, std::uint64_t *it) { return single.solve_with_initial(f, p, it); });
 }
 
 }  // namespace
@@ -637,13 +662,7 @@ SolverResult PrimalSimplexSolver::solve_from(Problem prob, const StartBasis &sta
     rep.reason = start_point(*sfo, start, ELLP_START_KEEP_LABELS, engine_, dp, rep.info);
     if (rep.reason != START_USED) return solve(std::move(prob));
     rep.used = true;
-    return run_from_start(ELLP_ENGINE_PRIMAL, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_,
-                          [this](const StandardForm &sf, DualFeasiblePoint &p, std::uint64_t *it) { return solve_with_initial(sf, p.point, it); },
-                          [](SolutionStatus s, SolverResult &res) {
-                              if (s == SolutionStatus::Infeasible) throw EllPPanic("primal phase 2 should never be infeasible");
-                              if (s == SolutionStatus::Unbounded) { res.kind = SolverResult::Unbounded; return false; }
-                              return true;
-                          });
+    return primal_from_point(*this, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_);
 }
 
 SolverResult DualSimplexSolver::solve_from(Problem prob, const StartBasis &start, StartReport *report) const {
@@ -660,13 +679,7 @@ SolverResult DualSimplexSolver::solve_from(Problem prob, const StartBasis &start
     rep.reason = start_point(*sfo, start, ELLP_START_LABELS_BY_D, engine_, dp, rep.info);
     if (rep.reason != START_USED) return solve(std::move(prob));
     rep.used = true;
-    return run_from_start(ELLP_ENGINE_DUAL, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_,
-                          [this](const StandardForm &sf, DualFeasiblePoint &p, std::uint64_t *it) { return solve_with_initial(sf, p, it); },
-                          [](SolutionStatus s, SolverResult &res) {
-                              if (s == SolutionStatus::Unbounded) throw EllPPanic("dual phase 2 should never return unbounded");
-                              if (s == SolutionStatus::Infeasible) { res.kind = SolverResult::Infeasible; return false; }
-                              return true;
-                          });
+    return dual_from_point(*this, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_);
 }
 
 }  // namespace ellp
@@ -927,7 +940,8 @@ void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which,
     }
 }
 
-void dual_batch(std::vector<Problem> &probs, std::uint64_t max_iter, const EngineOptions &eng, std::vector<BatchOutcome> &out) {
+void dual_batch(std::vector<Problem> &probs, const std::vector<size_t> &which, std::uint64_t max_iter, const EngineOptions &eng,
+                std::vector<BatchOutcome> &out) {
     const DualSimplexSolver single = DualSimplexSolver(max_iter).with_engine(eng);
     const char *hostpt = std::getenv("ELLP_HOST_DUAL_POINT");
     const bool defer = !(hostpt && hostpt[0] == '1');
@@ -937,15 +951,16 @@ void dual_batch(std::vector<Problem> &probs, std::uint64_t max_iter, const Engin
         std::optional<DualPhase2> p2;
         Seam seam;
     };
-    std::vector<Item> items(probs.size());
+    std::vector<Item> items(which.size());
     auto fallback = [&](Item &it) {
         settle(out[it.slot.out], it.slot, [&] { out[it.slot.out].result = single.solve(probs[it.slot.out]); });
         it.slot.done = true;
     };
     std::vector<Seam *> seams;
     std::vector<Item *> deferred;  // phase-1 start made on the device, in one batched call
-    for (size_t k = 0; k < probs.size(); ++k) {
-        Item &it = items[k];
+    for (size_t w = 0; w < which.size(); ++w) {
+        Item &it = items[w];
+        const size_t k = which[w];
         it.slot.out = k;
         settle(out[k], it.slot, [&] {
             auto p1 = DualPhase1::from_problem(probs[k], defer);
@@ -1189,17 +1204,184 @@ void batch_postsolve(std::vector<BatchOutcome> &out, const EngineOptions &eng) {
     }
 }
 
+// solve_batch(..., starts): the problems that come with a start.  Per problem the steps of solve_from:
+// the standard form, map_start and the reasons of §3.11; then the points of ALL mapped starts from ONE
+// ellp_batch_basis_start call (KEEP_LABELS for the primal solver, LABELS_BY_D for the dual; the verdict is start_point's),
+// and phase 2 of the usable ones the batch takes in ONE ellp_batch_solve_with_initial call of their own.  A usable start
+// the batch does not take runs phase 2 alone, from the point already made.  The problems whose start is not usable are
+// returned in `cold`: they join the cold batch, untouched
+void start_batch(int solver, std::vector<Problem> &probs, const std::vector<const StartBasis *> &starts, std::uint64_t max_iter,
+                 const EngineOptions &eng, std::vector<BatchOutcome> &out, std::vector<StartReport> &reports, std::vector<size_t> &cold) {
+    const int kind = solver == ELLP_ENGINE_PRIMAL ? ELLP_ENGINE_PRIMAL : ELLP_ENGINE_DUAL;
+    const int mode = kind == ELLP_ENGINE_PRIMAL ? ELLP_START_KEEP_LABELS : ELLP_START_LABELS_BY_D;
+    const std::optional<std::uint64_t> mi = max_iter;
+    const PrimalSimplexSolver psingle = PrimalSimplexSolver(mi).with_engine(eng);
+    const DualSimplexSolver dsingle = DualSimplexSolver(mi).with_engine(eng);
+    struct Job {
+        Slot slot;
+        std::optional<StandardForm> sf;
+        std::vector<std::int64_t> B, N;
+        std::vector<std::uint8_t> Nb;
+        Flat f;
+        DualFeasiblePoint dp;
+        Seam seam;
+    };
+    std::vector<Job> jobs;
+    jobs.reserve(probs.size());
+    // ---- the standard form and the mapping, on the host
+    for (size_t k = 0; k < probs.size(); ++k) {
+        if (!starts[k]) {
+            cold.push_back(k);
+            continue;
+        }
+        Job j;
+        j.slot.out = k;
+        int reason = START_USED;
+        settle(out[k], j.slot, [&] {
+            auto sfo = StandardForm::from_problem(probs[k]);
+            if (!sfo) {  // as solve_from
+                out[k].result.kind = SolverResult::Infeasible;
+                j.slot.done = true;
+                return;
+            }
+            j.sf = std::move(*sfo);
+            if (j.sf->rows() == 0) reason = START_NO_ROWS;
+            else if ((reason = map_start(*j.sf, *starts[k], j.B, j.N, j.Nb)) == START_USED && j.sf->bounds.size() != j.sf->cols())
+                reason = START_BAD_SIZE;
+        });
+        if (j.slot.done) continue;
+        if (reason != START_USED) {
+            reports[k].reason = reason;
+            cold.push_back(k);
+            continue;
+        }
+        jobs.push_back(std::move(j));
+    }
+    if (jobs.empty()) return;
+    // ---- every point in one call
+    std::vector<ellp_batch_item> items(jobs.size());
+    std::vector<ellp_start_info> infos(jobs.size());
+    for (size_t q = 0; q < jobs.size(); ++q) {
+        Job &j = jobs[q];
+        const StandardForm &sf = *j.sf;
+        Point shape;
+        shape.B.resize(j.B.size());
+        shape.N.resize(j.N.size());
+        j.f = flatten(sf, shape);
+        j.dp.point.x.assign(sf.cols(), 0.0);
+        j.dp.y.assign(sf.rows(), 0.0);
+        j.dp.d.assign(sf.cols(), 0.0);
+        std::memset(&infos[q], 0, sizeof(infos[q]));
+        ellp_batch_item &it = items[q];
+        std::memset(&it, 0, sizeof(it));
+        it.m = static_cast<std::int64_t>(sf.rows());
+        it.n = it.n_c = static_cast<std::int64_t>(sf.cols());
+        it.A = sf.A.a.data();
+        it.c = sf.c.data();
+        it.b = sf.b.data();
+        it.bound_kind = j.f.kind.data();
+        it.lb = j.f.lb.data();
+        it.ub = j.f.ub.data();
+        it.x = j.dp.point.x.data();
+        it.B_index = j.B.data();
+        it.n_B = static_cast<std::int64_t>(j.B.size());
+        it.N_index = j.N.data();
+        it.N_bound = j.Nb.data();
+        it.n_N = static_cast<std::int64_t>(j.N.size());
+        it.y = j.dp.y.data();
+        it.d = j.dp.d.data();
+    }
+    const ellp_opts o0 = make_opts(0, eng);
+    std::vector<ellp_status> st(jobs.size(), ELLP_ERR_DEVICE);
+    char err[512] = {0};
+    const ellp_status rc = ellp_batch_basis_start(static_cast<std::int64_t>(items.size()), items.data(), mode, &o0, infos.data(), st.data(),
+                                                  err, sizeof(err));
+    std::vector<Seam *> seams;
+    std::vector<Job *> seamed;
+    auto alone = [&](Job &j) {  // phase 2 alone, from the point already made
+        const size_t k = j.slot.out;
+        settle(out[k], j.slot, [&] {
+            out[k].result = kind == ELLP_ENGINE_PRIMAL ? primal_from_point(psingle, std::move(*j.sf), std::move(j.dp), max_iter, eng, false, false)
+                                                       : dual_from_point(dsingle, std::move(*j.sf), std::move(j.dp), max_iter, eng, false, false);
+        });
+        j.slot.done = true;
+    };
+    for (size_t q = 0; q < jobs.size(); ++q) {
+        Job &j = jobs[q];
+        const size_t k = j.slot.out;
+        StartReport &rep = reports[k];
+        int reason = START_USED;
+        settle(out[k], j.slot, [&] {  // start_point's verdict
+            if (rc != ELLP_OPTIMAL) to_status(rc, err);  // throws: no device
+            rep.info = infos[q];
+            if (st[q] == ELLP_ERR_SINGULAR) reason = START_SINGULAR;
+            else if (st[q] == ELLP_ERR_ARG) reason = START_BAD_INDEX;
+            else if (st[q] != ELLP_OPTIMAL) to_status(st[q], items[q].err);
+            else if (!(mode == ELLP_START_KEEP_LABELS ? infos[q].primal_feasible : infos[q].dual_feasible)) reason = START_NOT_FEASIBLE;
+        });
+        if (j.slot.done) continue;
+        if (reason != START_USED) {
+            rep.reason = reason;
+            cold.push_back(k);
+            continue;
+        }
+        rep.used = true;
+        j.dp.point.B.resize(j.B.size());
+        j.dp.point.N.resize(j.N.size());
+        j.f.B = j.B;
+        j.f.N = j.N;
+        j.f.Nb = j.Nb;
+        unflatten(j.f, j.dp.point);
+        const size_t nN = j.dp.point.N.size();
+        const bool takes = kind == ELLP_ENGINE_PRIMAL ? primal_batchable(*j.sf, nN, eng) : (batchable(*j.sf, nN) || dual_mid_batchable(*j.sf, nN, eng));
+        if (!takes) {
+            alone(j);
+            continue;
+        }
+        j.seam.sf = &*j.sf;
+        j.seam.pt = &j.dp.point;
+        j.seam.dp = kind == ELLP_ENGINE_DUAL ? &j.dp : nullptr;
+        seams.push_back(&j.seam);
+        seamed.push_back(&j);
+    }
+    std::sort(cold.begin(), cold.end());
+    // ---- phase 2 of the usable starts the batch takes, in one call of their own
+    const bool ran = run_seams(kind, seams, max_iter, eng);
+    for (Job *jp : seamed) {
+        Job &j = *jp;
+        if (!ran || j.seam.status == ELLP_ERR_ARG) {  // refused as a whole (options, device) or not taken (LDS): the single path
+            alone(j);
+            continue;
+        }
+        SolverResult &res = out[j.slot.out].result;
+        settle(out[j.slot.out], j.slot, [&] {
+            const SolutionStatus s2 = to_status(j.seam.status, j.seam.err.c_str());
+            res.iters_phase2 = j.seam.stats.iters;
+            end_from_start(kind, s2, *j.sf, j.dp, res);
+        });
+        j.slot.done = true;
+    }
+}
+
 }  // namespace
 
 std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng,
-                                      bool postsolve) {
+                                      bool postsolve, const std::vector<const StartBasis *> *starts, std::vector<StartReport> *reports) {
     std::vector<BatchOutcome> out(probs.size());
-    if (solver == ELLP_ENGINE_PRIMAL) {
-        std::vector<size_t> all(probs.size());
-        for (size_t k = 0; k < all.size(); ++k) all[k] = k;
-        primal_batch(probs, all, max_iter, eng, out);
+    std::vector<size_t> cold;
+    if (starts) {
+        if (starts->size() != probs.size()) throw std::invalid_argument("solve_batch: one start (or none) per problem");
+        std::vector<StartReport> local;
+        std::vector<StartReport> &rep = reports ? *reports : local;
+        rep.assign(probs.size(), StartReport{});
+        start_batch(solver, probs, *starts, max_iter, eng, out, rep, cold);
     } else {
-        dual_batch(probs, max_iter, eng, out);
+        cold.resize(probs.size());
+        for (size_t k = 0; k < cold.size(); ++k) cold[k] = k;
+    }
+    if (!cold.empty()) {
+        if (solver == ELLP_ENGINE_PRIMAL) primal_batch(probs, cold, max_iter, eng, out);
+        else dual_batch(probs, cold, max_iter, eng, out);
     }
     if (postsolve) batch_postsolve(out, eng);
     return out;

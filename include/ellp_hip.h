@@ -233,6 +233,10 @@ ellp_status ellp_batch_solve_with_initial(int kind, int64_t count, ellp_batch_it
                                           ellp_status *status_out, ellp_stats *stats_out, char *errbuf,
                                           size_t errbuf_len);
 
+/* Diagnostics of the calling thread's calls of ellp_batch_solve_with_initial: out4[0] how many it has made so far, [1] the
+ * items and [2] the kind of the last one, [3] 0.  Counted at entry, whatever the call then returns. */
+void ellp_batch_solve_info(uint64_t *out4);
+
 /*
  * Both phases of many primal solves in one batched call: what PrimalSimplexSolver::solve does between building phase 1 and
  * reading the result (primal_simplex_solver.rs:32-93), per item, on the kernels and with the workgroup sizes of
@@ -670,6 +674,29 @@ ellp_status ellp_basis_start(int64_t m, int64_t n, const double *A, const double
                              int mode, const ellp_opts *opts,
                              double *x /* out, n */, double *y /* out, m */, double *d /* out, n */,
                              ellp_start_info *info, char *errbuf, size_t errbuf_len);
+
+/*
+ * The starting points of many small LPs in one call.  Items are ellp_batch_item with n_c = n; per item
+ * x (n doubles) is out, y (m) and d (n) are out and may be NULL, N_bound is in/out, infos[i] (infos may be NULL) is the
+ * item's ellp_start_info.  Every output of every item is, bit for bit, what ellp_basis_start returns for that item alone,
+ * whatever batch it sits in, at whatever position and however the batch is chunked.  An item of up to 128 rows and 65,536
+ * nonbasic columns is done by one workgroup (k_start_batch: the basis and its LU in LDS, both refinement loops and their
+ * stop rules on the device) and reported by one more (k_start_report_batch): two launches, one upload and one read-back
+ * per chunk whatever the item count; any other valid item is run inside the call through ellp_basis_start.  Per item:
+ * status_out[i] and items[i].err, with the checks, messages, order and statuses of ellp_basis_start (ELLP_ERR_ARG before any
+ * HIP call, also for n_c != n; ELLP_ERR_SINGULAR with every output of the item, N_bound included, untouched); a failing
+ * item changes nothing for the others.  The call as a whole: ELLP_ERR_ARG (count < 0; items or status_out NULL; an unknown
+ * mode), ELLP_ERR_DEVICE, or ELLP_OPTIMAL; every check runs before any HIP call.  Chunks (budget ELLP_BATCH_MAX_BYTES, at
+ * most 65,535 items), the pinned staging buffer, the slab and the buffer pool are those of ellp_batch_solve_with_initial.
+ * Of opts the batched kernels read device and eps.
+ */
+ellp_status ellp_batch_basis_start(int64_t count, ellp_batch_item *items, int mode, const ellp_opts *opts,
+                                   ellp_start_info *infos /* may be NULL */, ellp_status *status_out,
+                                   char *errbuf, size_t errbuf_len);
+
+/* Diagnostics of the calling thread's last ellp_batch_basis_start that passed the checks of the call: out4[0] kernel launches
+ * of the batched path, [1] items on the batched kernel, [2] items on the single path, [3] chunks. */
+void ellp_batch_basis_start_info(uint64_t *out4);
 
 /*
  * Sensitivity ranging: over what change of one cost coefficient the basis stays optimal, and over what change of one

@@ -145,6 +145,21 @@ int ellp_solve_batch(const ellp_problem *const *probs, int64_t count, int solver
 int ellp_solve_batch_ex(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
                         int postsolve, ellp_result_ex *out);
 
+/* ellp_solve_batch_ex with warm starts: starts[k] is problem k's start as ellp_solve_start takes it, or NULL
+ * for none.  Per problem the standard form is built and the start mapped as ellp_solve_start maps it, with its reasons
+ * unchanged; the points of ALL mapped starts are made in ONE ellp_batch_basis_start call (ELLP_START_KEEP_LABELS for the
+ * primal solver, ELLP_START_LABELS_BY_D for the dual), and phase 2 of the usable starts the batch takes runs in ONE
+ * ellp_batch_solve_with_initial call of their own (iters_phase1 = 0).  A usable start the batch does not take runs phase 2
+ * alone, from the point already made; the problems whose start is not usable, and those without one, are solved by the
+ * cold batch of ellp_solve_batch.  out[k] is what ellp_solve_start(probs[k], ..., starts[k], ...) fills in, reports[k] its
+ * report (zeros for a problem without a start), and on Optimal the basis fields of EVERY out[k] are filled, started or not,
+ * so that batches chain.  flags: 0 or ELLP_SOLVE_POSTSOLVE (one ellp_batch_postsolve call for the whole batch).
+ * ELLP_ERR_ARG: count < 0, probs, starts, out or reports NULL, a NULL problem, an unknown solver, an unknown flag or
+ * ELLP_SOLVE_RANGING (there is no batched ranging); ELLP_ERR_DEVICE (host memory; every out[k] says so) or 0.  Free each
+ * out[k] with ellp_result_rng_free.  ellp_solve_batch and ellp_solve_batch_ex are unchanged. */
+int ellp_solve_batch_start(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+                           unsigned flags, const ellp_start *const *starts, ellp_result_rng *out, ellp_start_report *reports);
+
 /* Test/diagnostic tap: the flattened phase-1 problem (exactly the arrays that solve() hands to
  * ellp_*_solve_with_initial) so the host setup can be checked without a GPU.  All arrays are
  * owned by the struct (ellp_flat_phase_free).  Returns 0, 1 if the setup already proves
