@@ -169,6 +169,9 @@ def host_lib():
     L.ellp_solve_batch_start.restype = C.c_int
     L.ellp_solve_batch_start.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_uint, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
+    L.ellp_solve_batch_flags.restype = C.c_int
+    L.ellp_solve_batch_flags.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_uint, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
     L.ellp_solve_batch.restype = C.c_int
     L.ellp_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_void_p]
     L.ellp_debug_phase1.restype = C.c_int
@@ -427,7 +430,7 @@ class _Solver:
         finally:
             host_lib().ellp_result_rng_free(C.byref(rr))
 
-    def solve_batch(self, problems, starts=None, postsolve=False):
+    def solve_batch(self, problems, starts=None, postsolve=False, ranging=False):
         """solve() of every problem in `problems`: the device loops of all problems the LU-per-iteration kernels take run
         in batched launches, one workgroup per problem; the others are solved one by one.  The primal solver sends a
         problem to the device once and runs both of its phases there (ellp_batch_primal_solve): the workgroup that ends
@@ -454,9 +457,20 @@ class _Solver:
         batch.  With starts given — even if every entry is None — every Optimal entry has basis(), so batches chain:
         r1 = solve_batch(ps, starts=[None] * n); solve_batch(ps2, starts=[r.solution if r.kind == "optimal" else None
         for r in r1]).  A length mismatch raises ValueError.  starts=None: the call path without starts, not one extra
-        device call."""
+        device call.
+
+        ranging=True (implies the postsolve): every Optimal entry's Solution also has cost_ranging(), rhs_ranging() and
+        basis(), besides duals(), reduced_costs() and kkt(), with the bits of solve(p, ranging=True) — with starts, of
+        solve(p, start=s, ranging=True) — from ONE batched call for the whole batch (ellp_batch_ranging: five launches per
+        chunk for the problems up to 128 rows, whatever their number; _engine.batch_ranging_info() reports its launches,
+        items and chunks) and no batched postsolve call: the ranging's own duals, reduced costs and report are the
+        postsolve.  Where solve(p, ranging=True) would raise, the entry is that exception.  solve_batch(ps2, starts=r1,
+        ranging=True) gives a re-solved batch with its ranges in one call.  Off by default, and off takes the paths above
+        unchanged, with not one extra device call."""
         problems = list(problems)
         n = len(problems)
+        if ranging:
+            return self._solve_batch_start(problems, None if starts is None else list(starts), True, ranging=True)
         if starts is not None:
             return self._solve_batch_start(problems, list(starts), postsolve)
         if n == 0:
@@ -506,8 +520,13 @@ class _Solver:
         return out
 
 
-    def _solve_batch_start(self, problems, starts, postsolve):
+    def _solve_batch_start(self, problems, starts, postsolve, ranging=False):
+        """the batch through ellp_solve_batch_start, or with ranging=True through ellp_solve_batch_flags (starts may then be
+        None: no problem has a start)"""
         n = len(problems)
+        given = starts is not None
+        if not given:
+            starts = [None] * n
         if len(starts) != n:
             raise ValueError(f"solve_batch: {len(starts)} starts for {n} problems")
         for s in starts:
@@ -520,8 +539,11 @@ class _Solver:
         sptr = (C.POINTER(_Start) * n)(*[None if st is None else C.pointer(st[0]) for st in structs])
         rrs, reps = (_ResultRng * n)(), (_StartReport * n)()
         L = host_lib()
-        s = L.ellp_solve_batch_start(handles, n, self._KIND, self.max_iter, C.byref(self._opts) if self._opts is not None else None,
-                                     1 if postsolve else 0, sptr, rrs, reps)
+        o = C.byref(self._opts) if self._opts is not None else None
+        if ranging:
+            s = L.ellp_solve_batch_flags(handles, n, self._KIND, self.max_iter, o, 3, sptr if given else None, rrs, reps if given else None)
+        else:
+            s = L.ellp_solve_batch_start(handles, n, self._KIND, self.max_iter, o, 1 if postsolve else 0, sptr, rrs, reps)
         del structs
         if s == _engine.ERR_ARG:
             raise ValueError("solve_batch: invalid arguments")

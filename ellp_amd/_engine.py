@@ -260,6 +260,10 @@ def lib():
     L.ellp_batch_postsolve.argtypes = [C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
     L.ellp_batch_postsolve_info.restype = None
     L.ellp_batch_postsolve_info.argtypes = [C.POINTER(C.c_uint64)]
+    L.ellp_batch_ranging.restype = C.c_int
+    L.ellp_batch_ranging.argtypes = [C.c_int64, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.ellp_batch_ranging_info.restype = None
+    L.ellp_batch_ranging_info.argtypes = [C.POINTER(C.c_uint64)]
     L.ellp_batch_solve_info.restype = None
     L.ellp_batch_solve_info.argtypes = [C.POINTER(C.c_uint64)]
     L.ellp_batch_basis_start.restype = C.c_int
@@ -555,6 +559,70 @@ def batch_postsolve_info():
     on the batched kernel, items on the single path (inside the call), chunks."""
     out = (C.c_uint64 * 4)()
     lib().ellp_batch_postsolve_info(out)
+    return {"launches": int(out[0]), "batched": int(out[1]), "single": int(out[2]), "chunks": int(out[3])}
+
+
+class BatchRangeOut(C.Structure):
+    """ellp_batch_range_out (include/ellp_hip.h)"""
+    _fields_ = [("out", RangingOut), ("W", C.c_void_p)]
+
+
+def batch_ranging(flat_problems, opts=None, want_W=False):
+    """ellp_batch_ranging: the ranging of every FlatProblem (the arrays a solve_with_initial call left) in one batched call,
+    with the bits of ranging(fp) per problem.  Returns one (status, Ranging, W, msg) per problem; status is OPTIMAL, ERR_ARG
+    or ERR_SINGULAR, and where it is not OPTIMAL Ranging and W are None.  W (want_W=True, else None): B^-1 as the ranging
+    formed it, (m, m) by rows.  Raises EllpHipError if the call as a whole is refused (device)."""
+    return [(s, rg if s == OPTIMAL else None, W if s == OPTIMAL else None, msg)
+            for s, rg, W, msg in _batch_ranging_raw(flat_problems, opts, want_W)]
+
+
+def _batch_ranging_raw(flat_problems, opts=None, want_W=False, fill=0.0, wanted=None):
+    """batch_ranging with the output arrays handed back whatever the status (for the tests: a failing item leaves them as
+    they were made, every entry `fill`).  wanted: per problem None (everything) or the names of Ranging.ARRAYS / "info" asked for; an
+    empty list with want_W=False asks for nothing."""
+    fps = list(flat_problems)
+    n = len(fps)
+    items = (BatchItem * max(n, 1))()
+    outs = (BatchRangeOut * max(n, 1))()
+    keep = []
+    for k, (it, fp) in enumerate(zip(items, fps)):
+        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
+        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
+        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
+        it.B_index, it.n_B = _p(fp.B), fp.nB
+        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(fp.Nb), fp.nN
+        rg = Ranging(max(fp.m, 0), max(fp.n_c, 0))
+        for name in Ranging.ARRAYS:
+            a = getattr(rg, name)
+            a[...] = fill if a.dtype != np.int64 else (int(fill) if fill == fill else -7)
+        want = None if wanted is None else wanted[k]
+        o = rg._out()
+        if want is not None:
+            for name in Ranging.ARRAYS:
+                if name not in want:
+                    setattr(o, name, None)
+            if "info" not in want:
+                o.info = None
+        W = np.full((max(fp.m, 0), max(fp.m, 0)), fill) if want_W else None
+        outs[k].out = o
+        outs[k].W = None if W is None else W.ctypes.data
+        keep.append((rg, W))
+    status = (C.c_int * max(n, 1))()
+    o = opts or default_opts()
+    err = C.create_string_buffer(512)
+    s = lib().ellp_batch_ranging(n, items, C.byref(o), outs, status, err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    return [(status[k], keep[k][0]._done() if status[k] == OPTIMAL else keep[k][0], keep[k][1], items[k].err.decode())
+            for k in range(n)]
+
+
+def batch_ranging_info():
+    """ellp_batch_ranging_info: the calling thread's last ellp_batch_ranging: kernel launches of the batched path (5 per
+    chunk, whatever the item count and the items' shapes: k_brange_front, k_brange_solve, k_brange_tab, k_brange_fold,
+    k_post_report_batch), items on the batched kernels, items on the single path (inside the call), chunks."""
+    out = (C.c_uint64 * 4)()
+    lib().ellp_batch_ranging_info(out)
     return {"launches": int(out[0]), "batched": int(out[1]), "single": int(out[2]), "chunks": int(out[3])}
 
 

@@ -269,20 +269,17 @@ __device__ __forceinline__ bool bpost_solve_y(const BpostSh &sh, const double *A
     return true;
 }
 
-__global__ __launch_bounds__(BPOST_NT) void k_post_batch(const PostBatchArgs *args) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ double s_bc[2];
-    __shared__ int s_plen;
-    const PostBatchArgs a = args[blockIdx.x];
-    const int tid = threadIdx.x;
+// The whole item of k_post_batch on the carve sh: false, with the item's flag set and nothing else written, on a zero on
+// U's diagonal.  On return the factors are in sh.LU, the swap list in (sh.pa, sh.pb, *s_plen) and the singleton columns in
+// (sh.srow, sh.sval), which k_brange_front (ellp_brange.inc) keeps for the ranging
+__device__ __forceinline__ bool bpost_item(const PostBatchArgs &a, const BpostSh &sh, int *s_plen, double *s_bc, int tid) {
     const int m = (int)a.rep.m;
     const int64_t ld = a.ld, nN = a.rep.nN;
-    const BpostSh sh = bpost_carve(smem, m, 0);
     double omega = 0.0, fs = 0.0, fc = 0.0;
     int32_t steps = 0;
-    if (!bpost_solve_y(sh, a.A_B, a.rep, a.rep.x, a.d, m, ld, &s_plen, s_bc, omega, steps, tid)) {
+    if (!bpost_solve_y(sh, a.A_B, a.rep, a.rep.x, a.d, m, ld, s_plen, s_bc, omega, steps, tid)) {
         if (tid == 0) *a.fail = 1;
-        return;
+        return false;
     }
     // ---- r from b, the basic blocks first, then the nonbasic ones as their pass delivers them; d on the way
     if (tid < m) {
@@ -302,6 +299,15 @@ __global__ __launch_bounds__(BPOST_NT) void k_post_batch(const PostBatchArgs *ar
         *a.omega = omega;
         *a.steps = steps;
     }
+    return true;
+}
+
+__global__ __launch_bounds__(BPOST_NT) void k_post_batch(const PostBatchArgs *args) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ double s_bc[2];
+    __shared__ int s_plen;
+    const PostBatchArgs a = args[blockIdx.x];
+    (void)bpost_item(a, bpost_carve(smem, (int)a.rep.m, 0), &s_plen, s_bc, threadIdx.x);
 }
 
 __global__ __launch_bounds__(1024) void k_post_report_batch(const PostBatchArgs *args) {
@@ -398,6 +404,66 @@ std::vector<size_t> bpost_cuts(const std::vector<Plan> &plan, size_t budget) {
 // the calling thread's last ellp_batch_postsolve that passed the checks of the call (ellp_batch_postsolve_info)
 thread_local uint64_t g_batch_post_info[4] = {0, 0, 0, 0};
 
+// One item into the staging buffer h, as its plan lays it out, and its arguments in the slab dv.  Shared by
+// ellp_batch_postsolve and ellp_batch_ranging (ellp_brange.inc), whose plan extends this one
+PostBatchArgs bpost_stage_item(unsigned char *h, unsigned char *dv, const BpostPlan &p, const ellp_batch_item &it) {
+    const int64_t m = it.m, nN = it.n_N, ld = p.ld;
+    memset(h + p.o_fail, 0, sizeof(int));
+    double *AB = reinterpret_cast<double *>(h + p.o_AB), *AN = reinterpret_cast<double *>(h + p.o_AN);
+    double *cB = reinterpret_cast<double *>(h + p.o_cB), *cN = reinterpret_cast<double *>(h + p.o_cN);
+    for (int64_t j = 0; j < m; ++j) {
+        memcpy(AB + j * ld, it.A + it.B_index[j] * m, sizeof(double) * (size_t)m);
+        memset(AB + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
+        cB[j] = it.c[it.B_index[j]];
+    }
+    if (nN == 0) memset(AN, 0, sizeof(double) * (size_t)ld);
+    for (int64_t j = 0; j < nN; ++j) {
+        memcpy(AN + j * ld, it.A + it.N_index[j] * m, sizeof(double) * (size_t)m);
+        memset(AN + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
+        cN[j] = it.c[it.N_index[j]];
+    }
+    if (p.ntail > 0) memcpy(h + p.o_ct, it.c + it.n, sizeof(double) * (size_t)p.ntail);
+    memcpy(h + p.o_x, it.x, sizeof(double) * (size_t)it.n_c);
+    memcpy(h + p.o_b, it.b, sizeof(double) * (size_t)m);
+    memcpy(h + p.o_lb, it.lb, sizeof(double) * (size_t)it.n_c);
+    memcpy(h + p.o_ub, it.ub, sizeof(double) * (size_t)it.n_c);
+    memcpy(h + p.o_kind, it.bound_kind, (size_t)it.n_c);
+    memcpy(h + p.o_B, it.B_index, sizeof(int64_t) * (size_t)m);
+    if (nN > 0) {
+        memcpy(h + p.o_N, it.N_index, sizeof(int64_t) * (size_t)nN);
+        memcpy(h + p.o_Nb, it.N_bound, (size_t)nN);
+    }
+    PostBatchArgs a{};
+    a.A_B = reinterpret_cast<const double *>(dv + p.o_AB);
+    a.A_N = reinterpret_cast<const double *>(dv + p.o_AN);
+    a.c_N = reinterpret_cast<const double *>(dv + p.o_cN);
+    a.y = reinterpret_cast<double *>(dv + p.o_y);
+    a.d = reinterpret_cast<double *>(dv + p.o_d);
+    a.r = reinterpret_cast<double *>(dv + p.o_r);
+    a.rho = reinterpret_cast<double *>(dv + p.o_rho);
+    a.omega = reinterpret_cast<double *>(dv + p.o_omega);
+    a.steps = reinterpret_cast<int32_t *>(dv + p.o_steps);
+    a.fail = reinterpret_cast<int *>(dv + p.o_fail);
+    a.ld = ld;
+    PostReportArgs &ra = a.rep;
+    ra.r = a.r; ra.d = a.d; ra.rho = a.rho; ra.y = a.y; ra.omega = a.omega;
+    ra.b = reinterpret_cast<const double *>(dv + p.o_b);
+    ra.x = reinterpret_cast<const double *>(dv + p.o_x);
+    ra.lb = reinterpret_cast<const double *>(dv + p.o_lb);
+    ra.ub = reinterpret_cast<const double *>(dv + p.o_ub);
+    ra.c_B = reinterpret_cast<const double *>(dv + p.o_cB);
+    ra.c_N = a.c_N;
+    ra.c_tail = reinterpret_cast<const double *>(dv + p.o_ct);
+    ra.kind = reinterpret_cast<const uint8_t *>(dv + p.o_kind);
+    ra.Nb = reinterpret_cast<const uint8_t *>(dv + p.o_Nb);
+    ra.B_index = reinterpret_cast<const int64_t *>(dv + p.o_B);
+    ra.N_index = reinterpret_cast<const int64_t *>(dv + p.o_N);
+    ra.m = m; ra.n = it.n; ra.n_c = it.n_c; ra.nN = nN;
+    ra.steps = 0;  // the batch reads a.steps on the device
+    ra.out = reinterpret_cast<ellp_kkt *>(dv + p.o_kkt);
+    return a;
+}
+
 // One chunk: staging, one upload, the two launches, one read-back, the per-item results
 ellp_status bpost_run_chunk(ellp_batch_item *items, const ellp_batch_post_out *outs, BpostPlan *plan, size_t R, BatchCleanup &cl,
                             ellp_status *status_out, char *errbuf, size_t errlen) {
@@ -409,62 +475,7 @@ ellp_status bpost_run_chunk(ellp_batch_item *items, const ellp_batch_post_out *o
     size_t lds = 0;
     for (size_t k = 0; k < R; ++k) {
         const BpostPlan &p = plan[k];
-        const ellp_batch_item &it = items[p.item];
-        const int64_t m = it.m, nN = it.n_N, ld = p.ld;
-        memset(h + p.o_fail, 0, sizeof(int));
-        double *AB = reinterpret_cast<double *>(h + p.o_AB), *AN = reinterpret_cast<double *>(h + p.o_AN);
-        double *cB = reinterpret_cast<double *>(h + p.o_cB), *cN = reinterpret_cast<double *>(h + p.o_cN);
-        for (int64_t j = 0; j < m; ++j) {
-            memcpy(AB + j * ld, it.A + it.B_index[j] * m, sizeof(double) * (size_t)m);
-            memset(AB + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
-            cB[j] = it.c[it.B_index[j]];
-        }
-        if (nN == 0) memset(AN, 0, sizeof(double) * (size_t)ld);
-        for (int64_t j = 0; j < nN; ++j) {
-            memcpy(AN + j * ld, it.A + it.N_index[j] * m, sizeof(double) * (size_t)m);
-            memset(AN + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
-            cN[j] = it.c[it.N_index[j]];
-        }
-        if (p.ntail > 0) memcpy(h + p.o_ct, it.c + it.n, sizeof(double) * (size_t)p.ntail);
-        memcpy(h + p.o_x, it.x, sizeof(double) * (size_t)it.n_c);
-        memcpy(h + p.o_b, it.b, sizeof(double) * (size_t)m);
-        memcpy(h + p.o_lb, it.lb, sizeof(double) * (size_t)it.n_c);
-        memcpy(h + p.o_ub, it.ub, sizeof(double) * (size_t)it.n_c);
-        memcpy(h + p.o_kind, it.bound_kind, (size_t)it.n_c);
-        memcpy(h + p.o_B, it.B_index, sizeof(int64_t) * (size_t)m);
-        if (nN > 0) {
-            memcpy(h + p.o_N, it.N_index, sizeof(int64_t) * (size_t)nN);
-            memcpy(h + p.o_Nb, it.N_bound, (size_t)nN);
-        }
-        PostBatchArgs a{};
-        a.A_B = reinterpret_cast<const double *>(dv + p.o_AB);
-        a.A_N = reinterpret_cast<const double *>(dv + p.o_AN);
-        a.c_N = reinterpret_cast<const double *>(dv + p.o_cN);
-        a.y = reinterpret_cast<double *>(dv + p.o_y);
-        a.d = reinterpret_cast<double *>(dv + p.o_d);
-        a.r = reinterpret_cast<double *>(dv + p.o_r);
-        a.rho = reinterpret_cast<double *>(dv + p.o_rho);
-        a.omega = reinterpret_cast<double *>(dv + p.o_omega);
-        a.steps = reinterpret_cast<int32_t *>(dv + p.o_steps);
-        a.fail = reinterpret_cast<int *>(dv + p.o_fail);
-        a.ld = ld;
-        PostReportArgs &ra = a.rep;
-        ra.r = a.r; ra.d = a.d; ra.rho = a.rho; ra.y = a.y; ra.omega = a.omega;
-        ra.b = reinterpret_cast<const double *>(dv + p.o_b);
-        ra.x = reinterpret_cast<const double *>(dv + p.o_x);
-        ra.lb = reinterpret_cast<const double *>(dv + p.o_lb);
-        ra.ub = reinterpret_cast<const double *>(dv + p.o_ub);
-        ra.c_B = reinterpret_cast<const double *>(dv + p.o_cB);
-        ra.c_N = a.c_N;
-        ra.c_tail = reinterpret_cast<const double *>(dv + p.o_ct);
-        ra.kind = reinterpret_cast<const uint8_t *>(dv + p.o_kind);
-        ra.Nb = reinterpret_cast<const uint8_t *>(dv + p.o_Nb);
-        ra.B_index = reinterpret_cast<const int64_t *>(dv + p.o_B);
-        ra.N_index = reinterpret_cast<const int64_t *>(dv + p.o_N);
-        ra.m = m; ra.n = it.n; ra.n_c = it.n_c; ra.nN = nN;
-        ra.steps = 0;  // the batch reads a.steps on the device
-        ra.out = reinterpret_cast<ellp_kkt *>(dv + p.o_kkt);
-        h_args[k] = a;
+        h_args[k] = bpost_stage_item(h, dv, p, items[p.item]);
         if (p.lds > lds) lds = p.lds;
     }
     // the outputs' region goes up too (the fail flags are its only part that is read before it is written)

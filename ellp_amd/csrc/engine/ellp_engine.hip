@@ -4811,3 +4811,4 @@ ellp_status ellp_dual_solve_with_initial(int64_t m, int64_t n, int64_t n_c, cons
 #include "ellp_start.inc"
 #include "ellp_bstart.inc"
 #include "ellp_range.inc"
+#include "ellp_brange.inc"

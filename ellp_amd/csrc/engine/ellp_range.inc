@@ -111,15 +111,14 @@ __device__ __forceinline__ void rng_rhs_cand(double w, double x, double lb, doub
     if (cd) qd = d;
 }
 
-// ---- W = B^-1 by rows: R right-hand sides e_{i0}, .., e_{i0 + R - 1} per workgroup (512 threads: thread = (k slot, r))
+// ---- W = B^-1 by rows: R right-hand sides e_{i0}, .., e_{i0 + R - 1} per workgroup (512 threads: thread = (k slot, r)).
+// range_solve_rows: on return x ([m][R], LDS; acc: as much again) holds the rows as [k][r], visible to every thread.  false: a
+// zero on U's diagonal (the same for every thread), x is then not to be read.  Shared by k_range_solve and k_brange_solve
+// (ellp_brange.inc)
 template <int R>
-__global__ __launch_bounds__(512) void k_range_solve(const double *M, const int64_t *piv, int64_t m, double *W, int64_t ldw, int *fail) {
-    extern __shared__ __align__(16) unsigned char rng_smem[];
-    double *x = reinterpret_cast<double *>(rng_smem);  // [m][R]: the solution
-    double *acc = x + m * R;                           // [m][R]: sum_{k < i} U[k][i] x_k
+__device__ __forceinline__ bool range_solve_rows(const double *M, const int64_t *piv, int64_t m, int64_t i0, double *x, double *acc, int tid) {
     constexpr int KS = 512 / R;
-    const int tid = threadIdx.x, r = tid % R, ks = tid / R;
-    const int64_t i0 = (int64_t)blockIdx.x * R;
+    const int r = tid % R, ks = tid / R;
     for (int64_t t = tid; t < m * R; t += 512) {
         x[t] = 0.0;
         acc[t] = 0.0;
@@ -128,10 +127,7 @@ __global__ __launch_bounds__(512) void k_range_solve(const double *M, const int6
     // U^T: x_i = (b_i - acc_i) / U_ii, then acc_k += U[i][k] x_i for every later k (k_lu_solve mode 1; b = e_{i0 + r})
     for (int64_t i = 0; i < m; ++i) {
         const double diag = M[i * m + i];
-        if (diag == 0.0) {  // the same for every thread
-            if (tid == 0) *fail = 1;
-            return;
-        }
+        if (diag == 0.0) return false;
         double xi = ((i == i0 + r) ? 1.0 : 0.0) - acc[i * R + r];
         xi = xi / diag;
         if (ks == 0) x[i * R + r] = xi;
@@ -158,10 +154,28 @@ __global__ __launch_bounds__(512) void k_range_solve(const double *M, const int6
             }
         }
     __syncthreads();
+    return true;
+}
+// the rows of range_solve_rows from LDS to W
+template <int R>
+__device__ __forceinline__ void range_store_rows(const double *x, int64_t m, int64_t i0, double *W, int64_t ldw, int tid) {
     for (int64_t t = tid; t < m * R; t += 512) {
         const int64_t rr = t / m, k = t - rr * m;
         if (i0 + rr < m) W[(i0 + rr) * ldw + k] = x[k * R + rr];
     }
+}
+template <int R>
+__global__ __launch_bounds__(512) void k_range_solve(const double *M, const int64_t *piv, int64_t m, double *W, int64_t ldw, int *fail) {
+    extern __shared__ __align__(16) unsigned char rng_smem[];
+    double *x = reinterpret_cast<double *>(rng_smem);  // [m][R]: the solution
+    double *acc = x + m * R;                           // [m][R]: sum_{k < i} U[k][i] x_k
+    const int tid = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * R;
+    if (!range_solve_rows<R>(M, piv, m, i0, x, acc, tid)) {
+        if (tid == 0) *fail = 1;
+        return;
+    }
+    range_store_rows<R>(x, m, i0, W, ldw, tid);
 }
 
 // A basic column with a single nonzero, column j = a e_k, states a W[i][k] = delta_ij on its own: W[j][k] = fl(1 / a) and an
@@ -175,10 +189,13 @@ __global__ __launch_bounds__(256) void k_range_snap(double *W, const int64_t *si
 }
 
 // ---- max |I - A_B W|: 64 x 64 tiles, a thread 4 x 4 entries, every entry one sum over k = 0 .. m-1 in ascending order
-__global__ __launch_bounds__(256) void k_range_resid(const double *A_B, const double *W, int64_t m, int64_t ld, int64_t ldw, double *tilemax) {
+// the maximum of tile (ti, tj) by one workgroup of 256 threads; the value is thread 0's.  Shared by k_range_resid and
+// k_brange_fold (ellp_brange.inc): a caller that takes several tiles needs no barrier between them (every tile has one
+// between thread 0's read of s_red and the next write of it)
+__device__ __forceinline__ double range_resid_tile(const double *A_B, const double *W, int64_t m, int64_t ld, int64_t ldw, int64_t ti, int64_t tj) {
     __shared__ double sa[16][64], sb[16][64], s_red[4];
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
-    const int64_t i0 = (int64_t)blockIdx.y * 64, j0 = (int64_t)blockIdx.x * 64;
+    const int64_t i0 = ti * 64, j0 = tj * 64;
     double s[4][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -220,7 +237,11 @@ __global__ __launch_bounds__(256) void k_range_resid(const double *A_B, const do
     for (int o = 32; o > 0; o >>= 1) worst = nanmax(worst, __shfl_xor(worst, o));
     if ((tid & 63) == 0) s_red[tid >> 6] = worst;
     __syncthreads();
-    if (tid == 0) tilemax[blockIdx.y * gridDim.x + blockIdx.x] = nanmax(nanmax(s_red[0], s_red[1]), nanmax(s_red[2], s_red[3]));
+    return tid == 0 ? nanmax(nanmax(s_red[0], s_red[1]), nanmax(s_red[2], s_red[3])) : 0.0;
+}
+__global__ __launch_bounds__(256) void k_range_resid(const double *A_B, const double *W, int64_t m, int64_t ld, int64_t ldw, double *tilemax) {
+    const double t = range_resid_tile(A_B, W, m, ld, ldw, blockIdx.y, blockIdx.x);
+    if (threadIdx.x == 0) tilemax[blockIdx.y * gridDim.x + blockIdx.x] = t;
 }
 __global__ __launch_bounds__(256) void k_range_resmax(const double *tilemax, int64_t ntiles, double *out) {
     __shared__ double s_red[4];
@@ -248,15 +269,17 @@ struct RngTabArgs {
     double eps;
 };
 
+// tile (row block by, column block bx) by one workgroup of 512 threads.  Shared by k_range_tab and k_brange_tab
+// (ellp_brange.inc), which takes a and bx per workgroup from a table
 template <int STORE>
-__global__ __launch_bounds__(512) void k_range_tab(RngTabArgs a) {
+__device__ __forceinline__ void range_tab_tile(const RngTabArgs &a, int64_t bx, int64_t by) {
     constexpr int BM = 128, BN = 128, BK = 16;
     __shared__ __align__(16) double sA[2][BK][BM];
     __shared__ __align__(16) double sB[2][BK][BN];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 2, wc = wave & 3;  // the wave's 64 x 32 piece
     const int64_t m = a.m;
-    const int64_t i0 = (int64_t)blockIdx.y * BM, j0 = (int64_t)blockIdx.x * BN;
+    const int64_t i0 = by * BM, j0 = bx * BN;
 
     mfma_d4 acc[4][2];
 #pragma unroll
@@ -381,12 +404,16 @@ __global__ __launch_bounds__(512) void k_range_tab(RngTabArgs a) {
             up = rng_pick<1>(up, RngRec{s_v[w * BM + tid], s_p[w * BM + tid]});
             dn = rng_pick<0>(dn, RngRec{s_v[(4 + w) * BM + tid], s_p[(4 + w) * BM + tid]});
         }
-        const int64_t o = (int64_t)blockIdx.x * a.nrows + i0 + tid;
+        const int64_t o = bx * a.nrows + i0 + tid;
         a.pu[o] = up.v;
         a.ppu[o] = up.p;
         a.pd[o] = dn.v;
         a.ppd[o] = dn.p;
     }
+}
+template <int STORE>
+__global__ __launch_bounds__(512) void k_range_tab(RngTabArgs a) {
+    range_tab_tile<STORE>(a, blockIdx.x, blockIdx.y);
 }
 
 // the blocking variable of a limit: -1 when it is infinite
@@ -404,9 +431,7 @@ struct RngCfoldArgs {
     int64_t *cblk;
     int64_t m, n_c, nblk;
 };
-__global__ __launch_bounds__(256) void k_range_cfold(RngCfoldArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.m) return;
+__device__ __forceinline__ void range_cfold_row(const RngCfoldArgs &a, int64_t i) {
     RngRec up{INFINITY, RNG_NOPOS}, dn{-INFINITY, RNG_NOPOS};
     for (int64_t k = 0; k < a.nblk; ++k) {
         up = rng_pick<1>(up, RngRec{a.pu[k * a.m + i], a.ppu[k * a.m + i]});
@@ -418,6 +443,10 @@ __global__ __launch_bounds__(256) void k_range_cfold(RngCfoldArgs a) {
     a.cblk[var] = rng_blocking(dn, a.N_index);
     a.cblk[a.n_c + var] = rng_blocking(up, a.N_index);
 }
+__global__ __launch_bounds__(256) void k_range_cfold(RngCfoldArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < a.m) range_cfold_row(a, i);
+}
 
 // the nonbasic variables (by position) and the costs without a column
 struct RngCnbArgs {
@@ -428,9 +457,7 @@ struct RngCnbArgs {
     int64_t *cblk;
     int64_t nN, n, n_c;
 };
-__global__ __launch_bounds__(256) void k_range_cnb(RngCnbArgs a) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= a.nN + (a.n_c - a.n)) return;
+__device__ __forceinline__ void range_cnb_one(const RngCnbArgs &a, int64_t t) {
     int64_t var;
     double up = INFINITY, dn = -INFINITY;
     if (t < a.nN) {
@@ -452,6 +479,10 @@ __global__ __launch_bounds__(256) void k_range_cnb(RngCnbArgs a) {
     a.cost[a.n_c + var] = up;
     a.cblk[var] = (dn == -INFINITY) ? -1 : var;
     a.cblk[a.n_c + var] = (up == INFINITY) ? -1 : var;
+}
+__global__ __launch_bounds__(256) void k_range_cnb(RngCnbArgs a) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < a.nN + (a.n_c - a.n)) range_cnb_one(a, t);
 }
 
 // ---- the right-hand sides: 64 columns of W per workgroup, wave w takes the rows w, w + 4, ..

@@ -384,16 +384,12 @@ int ellp_solve_batch_ex(const ellp_problem *const *probs, int64_t count, int sol
     return ELLP_OPTIMAL;
 }
 
-int ellp_solve_batch_start(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+// ellp_solve_batch_start and ellp_solve_batch_flags after their checks: starts and reports may be NULL (no starts)
+static int solve_batch_rng(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
                            unsigned flags, const ellp_start *const *starts, ellp_result_rng *out, ellp_start_report *reports) {
-    if (count < 0 || !probs || !starts || !out || !reports || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL) ||
-        (flags & ~ELLP_SOLVE_POSTSOLVE))  // ELLP_SOLVE_RANGING too: there is no batched ranging
-        return ELLP_ERR_ARG;
-    for (int64_t k = 0; k < count; ++k)
-        if (!probs[k]) return ELLP_ERR_ARG;
     for (int64_t k = 0; k < count; ++k) {
         std::memset(&out[k], 0, sizeof(out[k]));
-        std::memset(&reports[k], 0, sizeof(reports[k]));
+        if (reports) std::memset(&reports[k], 0, sizeof(reports[k]));
     }
     std::vector<ellp::Problem> ps;
     ps.reserve(static_cast<size_t>(count));
@@ -404,12 +400,13 @@ int ellp_solve_batch_start(const ellp_problem *const *probs, int64_t count, int 
     try {
         for (int64_t k = 0; k < count; ++k) {
             ps.push_back(probs[k]->prob);
-            if (starts[k]) {
+            if (starts && starts[k]) {
                 sb[static_cast<size_t>(k)] = start_basis(starts[k]);
                 sp[static_cast<size_t>(k)] = &sb[static_cast<size_t>(k)];
             }
         }
-        res = ellp::solve_batch(solver, std::move(ps), max_iter, engine_options(opts), (flags & ELLP_SOLVE_POSTSOLVE) != 0, &sp, &rep);
+        res = ellp::solve_batch(solver, std::move(ps), max_iter, engine_options(opts), (flags & ELLP_SOLVE_POSTSOLVE) != 0,
+                                starts ? &sp : nullptr, starts ? &rep : nullptr, (flags & ELLP_SOLVE_RANGING) != 0);
     } catch (const std::exception &e) {  // host memory: the batch as a whole
         for (int64_t k = 0; k < count; ++k) {
             out[k].ex.result.status = ELLP_ERR_DEVICE;
@@ -424,11 +421,33 @@ int ellp_solve_batch_start(const ellp_problem *const *probs, int64_t count, int 
             return std::move(res[k].result);
         }, &out[k].ex, &out[k], /*basis_always=*/true);
         out[k].ex.result = base;
-        reports[k].used = rep[static_cast<size_t>(k)].used ? 1 : 0;
-        reports[k].reason = rep[static_cast<size_t>(k)].reason;
-        reports[k].info = rep[static_cast<size_t>(k)].info;
+        if (reports && starts) {
+            reports[k].used = rep[static_cast<size_t>(k)].used ? 1 : 0;
+            reports[k].reason = rep[static_cast<size_t>(k)].reason;
+            reports[k].info = rep[static_cast<size_t>(k)].info;
+        }
     }
     return ELLP_OPTIMAL;
+}
+
+int ellp_solve_batch_start(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+                           unsigned flags, const ellp_start *const *starts, ellp_result_rng *out, ellp_start_report *reports) {
+    if (count < 0 || !probs || !starts || !out || !reports || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL) ||
+        (flags & ~ELLP_SOLVE_POSTSOLVE))  // ELLP_SOLVE_RANGING too: that is ellp_solve_batch_flags
+        return ELLP_ERR_ARG;
+    for (int64_t k = 0; k < count; ++k)
+        if (!probs[k]) return ELLP_ERR_ARG;
+    return solve_batch_rng(probs, count, solver, max_iter, opts, flags, starts, out, reports);
+}
+
+int ellp_solve_batch_flags(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+                           unsigned flags, const ellp_start *const *starts, ellp_result_rng *out, ellp_start_report *reports) {
+    if (count < 0 || !probs || !out || (starts && !reports) || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL) ||
+        (flags & ~(ELLP_SOLVE_POSTSOLVE | ELLP_SOLVE_RANGING)))
+        return ELLP_ERR_ARG;
+    for (int64_t k = 0; k < count; ++k)
+        if (!probs[k]) return ELLP_ERR_ARG;
+    return solve_batch_rng(probs, count, solver, max_iter, opts, flags, starts, out, reports);
 }
 
 static void fill_flat(ellp_flat_phase *o, const ellp::StandardForm &sf, const ellp::Point &pt,

@@ -324,9 +324,12 @@ struct BatchOutcome {
 // the point already made, and the problems without a usable start join the cold batch.  Outcome k is solve_from's (the
 // postsolve by the one batched call); (*reports)[k] its StartReport (untouched defaults for a problem without a start).
 // starts null: the cold batch alone, not one extra device call.  Throws std::invalid_argument on a length mismatch
+// ranging (implies the postsolve): every Optimal outcome's Solution also carries its Ranging, with the bits of solve()
+// with_ranging(true) (of solve_from where starts are given), from ONE ellp_batch_ranging call for the whole batch and no
+// ellp_batch_postsolve call; false: not one extra device call
 std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng,
                                       bool postsolve = false, const std::vector<const StartBasis *> *starts = nullptr,
-                                      std::vector<StartReport> *reports = nullptr);
+                                      std::vector<StartReport> *reports = nullptr, bool ranging = false);
 
 // src/parse_mps.rs:11-66.  Variables/rows are taken in file order (the reference iterates
 // HashMaps, so its order is unspecified).

@@ -204,41 +204,74 @@ void attach_postsolve(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
     map_postsolve(sol, y, d, ps.kkt);
 }
 
+// The arrays of one ranging of a standard form, as ellp_ranging_out names them: filled by a ranging call (attach_ranging, or
+// for many solutions at once by solve_batch's one ellp_batch_ranging call), then mapped to the Problem by map_ranging
+struct RangeArrays {
+    std::vector<double> cd, cu, rd, ru, y, d;
+    std::vector<std::int64_t> cbd, cbu, rbd, rbu;
+    ellp_ranging_info info{};
+    RangeArrays(size_t m, size_t nc)
+        : cd(nc, -std::numeric_limits<double>::infinity()), cu(nc, std::numeric_limits<double>::infinity()), rd(m, 0.0), ru(m, 0.0),
+          y(m, 0.0), d(nc, 0.0), cbd(nc, -1), cbu(nc, -1), rbd(m, -1), rbu(m, -1) {}
+    ellp_ranging_out out() {
+        ellp_ranging_out o{};
+        o.cost_down = cd.data(); o.cost_up = cu.data(); o.cost_blocking_down = cbd.data(); o.cost_blocking_up = cbu.data();
+        o.rhs_down = rd.data(); o.rhs_up = ru.data(); o.rhs_blocking_down = rbd.data(); o.rhs_blocking_up = rbu.data();
+        o.info = &info;
+        o.y = y.data(); o.d = d.data();
+        return o;
+    }
+};
+
+// ra to the Problem's variables and constraints: the costs of the first nv columns, the rows by row_origin, a dropped row
+// (0.0, 0.0, -1).  With rows the ranging's own y, d and report become the Solution's postsolve (no second LU)
+void map_ranging(Solution &sol, const RangeArrays &ra) {
+    const StandardForm &sf = sol.std_form;
+    const size_t m = sf.rows(), nv = sf.prob.variables.size();
+    Ranging rg;
+    if (m > 0) {
+        rg.inverse_residual = ra.info.inverse_residual;
+        map_postsolve(sol, ra.y, ra.d, ra.info.kkt);
+    }
+    if (sf.row_origin.size() != m) throw EllPPanic("assertion failed: std_form.row_origin.len() == std_form.rows()");
+    const auto head = [nv](const auto &v) { return std::decay_t<decltype(v)>(v.begin(), v.begin() + static_cast<std::ptrdiff_t>(nv)); };
+    rg.cost_down = head(ra.cd); rg.cost_up = head(ra.cu); rg.cost_blocking_down = head(ra.cbd); rg.cost_blocking_up = head(ra.cbu);
+    const size_t ncon = sf.prob.constraints.size();
+    rg.rhs_down.assign(ncon, 0.0); rg.rhs_up.assign(ncon, 0.0); rg.rhs_blocking_down.assign(ncon, -1); rg.rhs_blocking_up.assign(ncon, -1);
+    for (size_t k = 0; k < m; ++k) {
+        const size_t o = sf.row_origin[k];
+        rg.rhs_down[o] = ra.rd[k]; rg.rhs_up[o] = ra.ru[k]; rg.rhs_blocking_down[o] = ra.rbd[k]; rg.rhs_blocking_up[o] = ra.rbu[k];
+    }
+    sol.rng = std::move(rg);
+}
+
 // with_ranging(true): the cost and right-hand-side ranges of an Optimal solution, from the engine that ran phase 2 where there
 // is one and it takes the call (ellp_engine_ranging), else from phase 2's arrays (ellp_ranging).  The ranging runs the
 // postsolve itself, so its y, d and report are taken from the same call and become the Solution's postsolve (no second LU).
 // Without rows both are answered here: every variable is nonbasic with d = c, and there is no right-hand side.
 void attach_ranging(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
     const StandardForm &sf = sol.std_form;
-    const size_t m = sf.rows(), nc = sf.bounds.size(), nv = sf.prob.variables.size();
+    const size_t m = sf.rows(), nc = sf.bounds.size();
     const double inf = std::numeric_limits<double>::infinity();
-    std::vector<double> cd(nc, -inf), cu(nc, inf), rd(m, 0.0), ru(m, 0.0);
-    std::vector<std::int64_t> cbd(nc, -1), cbu(nc, -1), rbd(m, -1), rbu(m, -1);
-    Ranging rg;
+    RangeArrays ra(m, nc);
     if (m == 0) {
         attach_postsolve(sol, e, eng);
         for (const Nonbasic &nb : sol.point.N) {
             const size_t v = nb.index;
             const double dv = sf.c[v];
             if (sf.bounds[v].kind == Bound::Fixed) continue;
-            if (nb.bound == NonbasicBound::Lower) cd[v] = 0.0 - std::max(dv, 0.0);
-            else if (nb.bound == NonbasicBound::Upper) cu[v] = 0.0 - std::min(dv, 0.0);
+            if (nb.bound == NonbasicBound::Lower) ra.cd[v] = 0.0 - std::max(dv, 0.0);
+            else if (nb.bound == NonbasicBound::Upper) ra.cu[v] = 0.0 - std::min(dv, 0.0);
             else {
-                cu[v] = std::max(-dv, 0.0) + 0.0;
-                cd[v] = std::min(-dv, 0.0) + 0.0;
+                ra.cu[v] = std::max(-dv, 0.0) + 0.0;
+                ra.cd[v] = std::min(-dv, 0.0) + 0.0;
             }
-            if (cd[v] != -inf) cbd[v] = static_cast<std::int64_t>(v);
-            if (cu[v] != inf) cbu[v] = static_cast<std::int64_t>(v);
+            if (ra.cd[v] != -inf) ra.cbd[v] = static_cast<std::int64_t>(v);
+            if (ra.cu[v] != inf) ra.cbu[v] = static_cast<std::int64_t>(v);
         }
     } else {
         char err[512] = {0};
-        ellp_ranging_info info{};
-        ellp_ranging_out out{};
-        out.cost_down = cd.data(); out.cost_up = cu.data(); out.cost_blocking_down = cbd.data(); out.cost_blocking_up = cbu.data();
-        out.rhs_down = rd.data(); out.rhs_up = ru.data(); out.rhs_blocking_down = rbd.data(); out.rhs_blocking_up = rbu.data();
-        out.info = &info;
-        std::vector<double> y(m, 0.0), d(nc, 0.0);
-        out.y = y.data(); out.d = d.data();
+        ellp_ranging_out out = ra.out();
         ellp_status s = ELLP_ERR_ARG;
         if (e) s = ellp_engine_ranging(e, &out, err, sizeof(err));
         if (s == ELLP_ERR_ARG) {
@@ -250,25 +283,8 @@ void attach_ranging(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
                              err, sizeof(err));
         }
         if (s != ELLP_OPTIMAL) to_status(s, err);  // throws, as attach_postsolve
-        rg.inverse_residual = info.inverse_residual;
-        if (sf.row_origin.size() != m) throw EllPPanic("assertion failed: std_form.row_origin.len() == std_form.rows()");
-        Postsolve ps;
-        ps.kkt = info.kkt;
-        ps.duals.assign(sf.prob.constraints.size(), 0.0);
-        for (size_t k = 0; k < m; ++k) ps.duals[sf.row_origin[k]] = y[k];
-        ps.reduced_costs.assign(d.begin(), d.begin() + static_cast<std::ptrdiff_t>(nv));
-        sol.post = std::move(ps);
     }
-    if (sf.row_origin.size() != m) throw EllPPanic("assertion failed: std_form.row_origin.len() == std_form.rows()");
-    const auto head = [nv](const auto &v) { return std::decay_t<decltype(v)>(v.begin(), v.begin() + static_cast<std::ptrdiff_t>(nv)); };
-    rg.cost_down = head(cd); rg.cost_up = head(cu); rg.cost_blocking_down = head(cbd); rg.cost_blocking_up = head(cbu);
-    const size_t ncon = sf.prob.constraints.size();
-    rg.rhs_down.assign(ncon, 0.0); rg.rhs_up.assign(ncon, 0.0); rg.rhs_blocking_down.assign(ncon, -1); rg.rhs_blocking_up.assign(ncon, -1);
-    for (size_t k = 0; k < m; ++k) {
-        const size_t o = sf.row_origin[k];
-        rg.rhs_down[o] = rd[k]; rg.rhs_up[o] = ru[k]; rg.rhs_blocking_down[o] = rbd[k]; rg.rhs_blocking_up[o] = rbu[k];
-    }
-    sol.rng = std::move(rg);
+    map_ranging(sol, ra);
 }
 
 }  // namespace
@@ -1204,6 +1220,76 @@ void batch_postsolve(std::vector<BatchOutcome> &out, const EngineOptions &eng) {
     }
 }
 
+// solve_batch(..., ranging): the ranges, and with them the duals, reduced costs and report, of every Optimal outcome from ONE
+// ellp_batch_ranging call for all of them and no ellp_batch_postsolve call (the items over 128 rows take the single call's
+// steps inside it); without rows attach_ranging answers on the host.  An item's refusal or singular basis becomes that
+// outcome's exception, the one solve() with_ranging(true) throws.  No Optimal outcome with rows: not one device call.
+void batch_ranging(std::vector<BatchOutcome> &out, const EngineOptions &eng) {
+    struct Job {
+        size_t k;
+        Flat f;
+        RangeArrays ra;
+    };
+    auto fail = [&](size_t k) {
+        out[k].error = std::current_exception();
+        out[k].result = SolverResult{};
+    };
+    std::vector<Job> jobs;
+    for (size_t k = 0; k < out.size(); ++k) {
+        if (out[k].error || out[k].result.kind != SolverResult::Optimal || !out[k].result.solution) continue;
+        Solution &sol = *out[k].result.solution;
+        if (sol.std_form.rows() == 0) {
+            try {
+                attach_ranging(sol, nullptr, eng);
+            } catch (...) {
+                fail(k);
+            }
+            continue;
+        }
+        jobs.push_back(Job{k, flatten(sol.std_form, sol.point), RangeArrays(sol.std_form.rows(), sol.std_form.bounds.size())});
+    }
+    if (jobs.empty()) return;
+    std::vector<ellp_batch_item> items(jobs.size());
+    std::vector<ellp_batch_range_out> outs(jobs.size());
+    for (size_t q = 0; q < jobs.size(); ++q) {
+        Job &j = jobs[q];
+        Solution &sol = *out[j.k].result.solution;
+        const StandardForm &sf = sol.std_form;
+        ellp_batch_item &it = items[q];
+        std::memset(&it, 0, sizeof(it));
+        it.m = static_cast<std::int64_t>(sf.rows());
+        it.n = static_cast<std::int64_t>(sf.cols());
+        it.n_c = static_cast<std::int64_t>(sf.bounds.size());
+        it.A = sf.A.a.data();
+        it.c = sf.c.data();
+        it.b = sf.b.data();
+        it.bound_kind = j.f.kind.data();
+        it.lb = j.f.lb.data();
+        it.ub = j.f.ub.data();
+        it.x = sol.point.x.data();
+        it.B_index = j.f.B.data();
+        it.n_B = static_cast<std::int64_t>(j.f.B.size());
+        it.N_index = j.f.N.data();
+        it.N_bound = j.f.Nb.data();
+        it.n_N = static_cast<std::int64_t>(j.f.N.size());
+        outs[q] = ellp_batch_range_out{j.ra.out(), nullptr};
+    }
+    const ellp_opts o = make_opts(0, eng);
+    std::vector<ellp_status> st(jobs.size(), ELLP_ERR_DEVICE);
+    char err[512] = {0};
+    const ellp_status rc = ellp_batch_ranging(static_cast<std::int64_t>(items.size()), items.data(), &o, outs.data(), st.data(), err, sizeof(err));
+    for (size_t q = 0; q < jobs.size(); ++q) {
+        Job &j = jobs[q];
+        try {
+            if (rc != ELLP_OPTIMAL) to_status(rc, err);                 // throws, as attach_ranging
+            else if (st[q] != ELLP_OPTIMAL) to_status(st[q], items[q].err);
+            map_ranging(*out[j.k].result.solution, j.ra);
+        } catch (...) {
+            fail(j.k);
+        }
+    }
+}
+
 // solve_batch(..., starts): the problems that come with a start.  Per problem the steps of solve_from:
 // the standard form, map_start and the reasons of §3.11; then the points of ALL mapped starts from ONE
 // ellp_batch_basis_start call (KEEP_LABELS for the primal solver, LABELS_BY_D for the dual; the verdict is start_point's),
@@ -1366,7 +1452,8 @@ void start_batch(int solver, std::vector<Problem> &probs, const std::vector<cons
 }  // namespace
 
 std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, std::uint64_t max_iter, const EngineOptions &eng,
-                                      bool postsolve, const std::vector<const StartBasis *> *starts, std::vector<StartReport> *reports) {
+                                      bool postsolve, const std::vector<const StartBasis *> *starts, std::vector<StartReport> *reports,
+                                      bool ranging) {
     std::vector<BatchOutcome> out(probs.size());
     std::vector<size_t> cold;
     if (starts) {
@@ -1383,7 +1470,8 @@ std::vector<BatchOutcome> solve_batch(int solver, std::vector<Problem> probs, st
         if (solver == ELLP_ENGINE_PRIMAL) primal_batch(probs, cold, max_iter, eng, out);
         else dual_batch(probs, cold, max_iter, eng, out);
     }
-    if (postsolve) batch_postsolve(out, eng);
+    if (ranging) batch_ranging(out, eng);  // its y, d and report are the postsolve
+    else if (postsolve) batch_postsolve(out, eng);
     return out;
 }
 

@@ -757,6 +757,40 @@ ellp_status ellp_ranging(int64_t m, int64_t n, int64_t n_c, const double *A, con
                          const int64_t *B_index, int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N,
                          const ellp_opts *opts, const ellp_ranging_out *out, char *errbuf, size_t errbuf_len);
 
+/*
+ * The ranging of many small LPs in one call: the items are those of ellp_batch_postsolve (the arrays a
+ * solve_with_initial call left; x, B_index, N_index and N_bound are read), outs[i] says where item i's results go.  Every
+ * output of every item — the eight range arrays, d, y, info->inverse_residual and info->kkt — is, bit for bit, what
+ * ellp_ranging returns for that item alone (any NaN equals any NaN), whatever batch it sits in, at whatever position and
+ * however the batch is chunked.  An item of up to 128 rows and 65,536 nonbasic columns goes through the batched kernels,
+ * FIVE launches per chunk whatever the item count and the items' shapes: k_brange_front (one workgroup per item: the
+ * batched postsolve's item, its factors kept), k_brange_solve (W = B^-1, 16 rows per workgroup, the singleton columns
+ * snapped), k_brange_tab (the tableau pass on the matrix cores, one workgroup per item and block of 128 columns),
+ * k_brange_fold (one workgroup per item: the fold of the blocks, the nonbasic costs, the right-hand sides,
+ * inverse_residual) and k_post_report_batch (the KKT report).  Any other valid item is run inside the call by the steps of
+ * ellp_ranging.  W (optional, m x m row-major): B^-1 as the ranging formed it, row i what ellp_engine_tableau_rows returns as
+ * rho for position i.  Per item: status_out[i] and items[i].err, the checks, messages and statuses of ellp_ranging
+ * (ELLP_ERR_ARG before any HIP call, also where nothing is wanted: every pointer of out NULL and W NULL; ELLP_ERR_SINGULAR
+ * with the item's outputs untouched); a failing item changes nothing for the others.  The call as a whole: ELLP_ERR_ARG
+ * (count < 0; items, outs or status_out NULL), ELLP_ERR_DEVICE, or ELLP_OPTIMAL; every check runs before any HIP call.
+ * Chunks (budget ELLP_BATCH_MAX_BYTES, at most 65,535 items), the pinned staging buffer, the slab and the buffer pool are
+ * those of ellp_batch_solve_with_initial: one upload and one read-back per chunk; what an item does not ask for is not
+ * read back (the two halves of a down / up pair come back together; W only where it is asked for).  Of opts the batched
+ * kernels read device and eps.
+ */
+typedef struct ellp_batch_range_out {
+    ellp_ranging_out out;   /* every pointer may be NULL; all NULL and W NULL: the item's ELLP_ERR_ARG */
+    double *W;              /* optional, m x m row-major */
+} ellp_batch_range_out;
+
+ellp_status ellp_batch_ranging(int64_t count, ellp_batch_item *items, const ellp_opts *opts,
+                               const ellp_batch_range_out *outs, ellp_status *status_out,
+                               char *errbuf, size_t errbuf_len);
+
+/* Diagnostics of the calling thread's last ellp_batch_ranging that passed the checks of the call: out4[0] kernel launches
+ * of the batched path (5 per chunk), [1] items on the batched kernels, [2] items on the single path, [3] chunks. */
+void ellp_batch_ranging_info(uint64_t *out4);
+
 /* Chosen rows of the tableau and of W behind them, as the ranging forms them (the same kernel with a storing epilogue: the
  * same bits): alpha[p * n_N + j] = rho_i . a_{N[j]} and rho[p * m + k] = W[i][k] for i = positions[p], p < k.  rho may be
  * NULL.  Refusals as above, and a position outside [0, m), k < 1 or positions / alpha NULL: ELLP_ERR_ARG before any HIP call.

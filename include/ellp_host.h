@@ -155,10 +155,26 @@ int ellp_solve_batch_ex(const ellp_problem *const *probs, int64_t count, int sol
  * report (zeros for a problem without a start), and on Optimal the basis fields of EVERY out[k] are filled, started or not,
  * so that batches chain.  flags: 0 or ELLP_SOLVE_POSTSOLVE (one ellp_batch_postsolve call for the whole batch).
  * ELLP_ERR_ARG: count < 0, probs, starts, out or reports NULL, a NULL problem, an unknown solver, an unknown flag or
- * ELLP_SOLVE_RANGING (there is no batched ranging); ELLP_ERR_DEVICE (host memory; every out[k] says so) or 0.  Free each
+ * ELLP_SOLVE_RANGING (the batched ranging is ellp_solve_batch_flags'); ELLP_ERR_DEVICE (host memory; every out[k] says so) or 0.  Free each
  * out[k] with ellp_result_rng_free.  ellp_solve_batch and ellp_solve_batch_ex are unchanged. */
 int ellp_solve_batch_start(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
                            unsigned flags, const ellp_start *const *starts, ellp_result_rng *out, ellp_start_report *reports);
+
+/* ellp_solve_batch_start with the flags of ellp_solve_flags, and with starts optional.  starts NULL: no
+ * problem has a start (reports may then be NULL and is not written); otherwise starts[k] may be NULL as above and reports is
+ * needed.  flags: ELLP_SOLVE_POSTSOLVE and ELLP_SOLVE_RANGING (implies the postsolve).  Without ELLP_SOLVE_RANGING the call is
+ * exactly ellp_solve_batch_start where starts is given, and exactly ellp_solve_batch_ex with the basis fields of every
+ * Optimal out[k] filled where it is NULL.  With it every Optimal out[k] is, bit for bit, what
+ * ellp_solve_flags(probs[k], ..., ELLP_SOLVE_POSTSOLVE | ELLP_SOLVE_RANGING, ...) fills in — with starts, what
+ * ellp_solve_start(probs[k], ..., starts[k], ...) fills in — and the whole batch makes ONE ellp_batch_ranging call
+ * (ellp_hip.h) and no ellp_batch_postsolve call: the ranging's own y, d and report are the postsolve.  A problem without
+ * rows is answered on the host; a row the rank check dropped has (0, 0, -1).  Where the single call fails (a singular
+ * basis, a refusal) out[k] carries that status and message.  ELLP_ERR_ARG before any device work: count < 0, probs or out
+ * NULL, starts given without reports, a NULL problem, an unknown solver or an unknown flag bit; ELLP_ERR_DEVICE (host
+ * memory; every out[k] says so) or 0.  Free each out[k] with ellp_result_rng_free. */
+int ellp_solve_batch_flags(const ellp_problem *const *probs, int64_t count, int solver, uint64_t max_iter, const ellp_opts *opts,
+                           unsigned flags, const ellp_start *const *starts /* may be NULL: no starts */, ellp_result_rng *out,
+                           ellp_start_report *reports /* may be NULL when starts is */);
 
 /* Test/diagnostic tap: the flattened phase-1 problem (exactly the arrays that solve() hands to
  * ellp_*_solve_with_initial) so the host setup can be checked without a GPU.  All arrays are
