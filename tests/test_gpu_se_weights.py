@@ -12,8 +12,9 @@ res = inverse_residual() (plus the rounding gamma_m max_i (|W||B|)_i. of that me
     | |W a|^2 - |x|^2 |  <=  2 res |x|_1^2 + m res^2 |x|_1^2 .
 
 ELLP_SE_BTRAN=1 forms v = B^-T d with the k_btran_part / _reduce GEMV in place of k_se_vreduce over k_update2's row
-blocks: the runs with it here are the only coverage the path that engines with ld > 4096 must take gets (no case of that
-size is added: a step there costs what 100 of these do).
+blocks: the runs with it here cover, step by step, the path that engines with ld > 4096 must take; an engine of that size
+itself (se_vpart = 0 by the plan, 4,097 rows) is held to the definition of the weights over 16 pivots by
+tests/test_gpu_large_pivots.py, case primal-p1-4097-se.
 
 Measured on an MI355X, the largest |G_dev - G_model| / dG: exact starts 0.17 (2 x 2; 0.13 and less from 16 rows up); every
 update of both phases at 16 / 17 / 39 / 64 / 65 / 70 rows 0.38 / 0.50 / 0.66 / 0.73 / 0.58 / 0.54 (the same with every column
