@@ -25,6 +25,7 @@ K_COUNT = 12
 TAP_U, TAP_R, TAP_D, TAP_BINV, TAP_KEY, TAP_ALPHA, TAP_STATE = range(7)
 TAP_SE_GAMMA = 7  # steepest-edge weights by nonbasic position, as the LAST pricing launch left them (include/ellp_hip.h)
 TAP_RESYNC_T, TAP_RESYNC_CAND = 8, 9  # t = b - A_N x_N and cand = B^-1 t of the last x_B resync, m doubles each
+TAP_REBUILD_PERM = 10  # test hook: pivot row of each basic column in the last rebuild of B^-1, m doubles; ERR_ARG after the shortcut
 
 
 class Opts(C.Structure):

@@ -2461,7 +2461,9 @@ __global__ __launch_bounds__(1024) void k_ref_pick(RefArgs a) {
         const long long p = bi;
         // primal: any |U_ii| < EPS is Err("A_B is not invertible") (primal…:175-179); the dual loop
         // has no such guard — only an exactly zero pivot makes its lu.solve() fail (dual…:294)
-        if (p < 0 || bv != bv || bv == 0.0 || bv < a.eps) {
+        // An infinite |alpha_p| is refused like a NaN (the blocked form turns it into one): an Inf in the LAST basic column
+        // met no later step that could fail, and the rebuild returned a W of NaNs with the engine running.
+        if (p < 0 || bv != bv || bv == INFINITY || bv == 0.0 || bv < a.eps) {
             st->status = ELLP_ERR_SINGULAR;
         } else {
             a.used[p] = 1;
@@ -2998,6 +3000,7 @@ struct ellp_engine : EnginePlan {  // the fields creation decides are the plan's
     int64_t *bl_Pm = nullptr, *bl_nzrow = nullptr;
     int32_t *bl_nzcnt = nullptr;
     uint64_t rebuild_shortcuts = 0;
+    bool perm_valid = false;  // perm holds the pivot rows of the last rebuild (false: none yet, or it took the permutation shortcut)
     double *aq_save = nullptr, *bmin = nullptr;  // two-launch pipeline: parked entering column, row-block minima of lambda
     bool hst_fresh = false;  // h_st is the device state as the previous call (an ellp_engine_run) left it: no read-back needed
     bool obj_fresh = false;  // h_st->obj is c . x of the state in h_st (primal; see ellp_engine_run / fill_stats)
@@ -3930,6 +3933,15 @@ int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap) {
         src = e->se_gamma;
         count = e->nN;
         break;
+    case ELLP_TAP_REBUILD_PERM: {  // the int64 pivot rows, converted on the host
+        if (!e->perm_valid || !e->perm || cap < e->m) return ELLP_ERR_ARG;
+        std::vector<int64_t> hp((size_t)e->m);
+        if (hipMemcpyAsync(hp.data(), e->perm, sizeof(int64_t) * hp.size(), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess)
+            return ELLP_ERR_DEVICE;
+        for (int64_t k = 0; k < e->m; ++k) dst[k] = (double)hp[(size_t)k];
+        return e->m;
+    }
     case ELLP_TAP_KEY:
         if (e->world != 1) return ELLP_ERR_ARG;
         src = e->X + 2 * e->nbs;

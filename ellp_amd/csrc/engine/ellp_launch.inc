@@ -216,6 +216,7 @@ void launch_refactor_columnwise(ellp_engine *e) {
     Prof p(e, ELLP_K_REFACTOR);
     RefArgs a{e->W, e->W2, e->d, e->A_B, e->used, e->perm, e->st, e->m, e->ld, e->upd_rows,
               e->kind == ELLP_ENGINE_PRIMAL ? e->eps : 0.0};
+    e->perm_valid = true;
     hipLaunchKernelGGL(k_ref_begin, dim3(1), dim3(1), 0, e->stream, a);
     hipLaunchKernelGGL(k_ref_init, dim3(1024), dim3(256), 0, e->stream, a);
     for (int64_t k = 0; k < e->m; ++k) {
@@ -265,6 +266,7 @@ void launch_refactor(ellp_engine *e) {
     e->refactors += 1;
     e->since_refactor = 0;
     e->u_valid = false;
+    e->perm_valid = false;
     // ---- shortcut: one nonzero per column, distinct rows
     hipLaunchKernelGGL(k_bl_probe, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, e->stream, a, e->bl_nzval, e->bl_nzrow, e->bl_nzcnt);
     hipLaunchKernelGGL(k_bl_perm_check, dim3(1), dim3(1024), 0, e->stream, a, e->bl_nzval, e->bl_nzrow, e->bl_nzcnt);
@@ -281,6 +283,7 @@ void launch_refactor(ellp_engine *e) {
         return;
     }
     // ---- general case
+    e->perm_valid = true;
     RefArgs ra{e->W, e->W2, e->d, e->A_B, e->used, e->perm, e->st, e->m, e->ld, e->upd_rows, a.eps};
     hipLaunchKernelGGL(k_ref_init, dim3(1024), dim3(256), 0, e->stream, ra);
     const auto [bl_nt, nbw_max] = bl_factor_variant(m);

@@ -112,7 +112,7 @@ __device__ __forceinline__ void bl_perm_check_body(BlArgs a, const double *nzval
         } else {
             if (atomicAdd(&a.used[nzrow[k]], 1) != 0) bad = 1;
             const double v = fabs(nzval[k]);
-            if (v != v || v == 0.0 || v < a.eps) sing = 1;
+            if (v != v || v == INFINITY || v == 0.0 || v < a.eps) sing = 1;  // 1 / Inf would be a finite, singular W
         }
     }
     bad = __syncthreads_or(bad);
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(1024) void k_bl_perm_check(BlArgs a, const double *
         } else {
             if (atomicAdd(&a.used[nzrow[k]], 1) != 0) bad = 1;
             const double v = fabs(nzval[k]);
-            if (v != v || v == 0.0 || v < a.eps) sing = 1;
+            if (v != v || v == INFINITY || v == 0.0 || v < a.eps) sing = 1;  // 1 / Inf would be a finite, singular W
         }
     }
     bad = __syncthreads_or(bad);

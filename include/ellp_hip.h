@@ -526,7 +526,12 @@ enum { ELLP_TAP_U = 0, ELLP_TAP_R = 1, ELLP_TAP_D = 2, ELLP_TAP_BINV = 3, ELLP_T
                                 (at creation and after ellp_engine_rephase: to the point the engine stands on).  ELLP_ERR_ARG on
                                 an engine without the flag. */,
        ELLP_TAP_RESYNC_T = 8 /* t = b - A_N x_N as the last x_B resync (or the primal phase-1 start) formed it, m doubles */,
-       ELLP_TAP_RESYNC_CAND = 9 /* cand = B^-1 t of the last x_B resync, adopted or not, m doubles */ };
+       ELLP_TAP_RESYNC_CAND = 9 /* cand = B^-1 t of the last x_B resync, adopted or not, m doubles */,
+       ELLP_TAP_REBUILD_PERM = 10 /* test hook: the pivot rows of the last rebuild of B^-1, m doubles (cap >= m): entry k is the
+                                     row the elimination pivoted on for basic column k, blocked or column by column.  After a
+                                     rebuild that ended in ELLP_ERR_SINGULAR the entries from the refused column on are not
+                                     those of that rebuild.  ELLP_ERR_ARG when the last rebuild took the permutation shortcut
+                                     (which does not eliminate) and when no rebuild has run. */ };
 int64_t ellp_engine_tap(ellp_engine *e, int what, double *dst, int64_t cap);
 
 /* One Newton-Schulz step W <- W + W (I - A_B W) on the resident inverse (two f64 GEMMs); this

@@ -1,8 +1,11 @@
 """The blocked rebuild of B^-1 (ellp_amd/csrc/engine/ellp_rebuild.inc): the same
 Gauss-Jordan elimination with partial pivoting as the column-by-column rebuild of round 1 (whose pivots
 are partial-pivot LU's U_kk, so that the reference's singularity guard primal…:175-179 applies), done 64
-columns at a time.  Checked against numpy's inverse, against the column-by-column rebuild, on every
-sub-panel width and on sizes around the tile edges, on singular bases, and on the permutation shortcut."""
+columns at a time.  Checked against numpy's inverse within a multiple of the condition number, against the
+column-by-column rebuild, on sizes around the tile edges (the 8- and 4-column sub-panels only at m = 2100 and
+4100, the 512-thread kernels only), on singular bases far below the guard, and on the permutation shortcut.
+The exact checks - every k_bl_factor instantiation, the pivot rows, the guard at its edge, NaN and Inf - are
+in tests/test_gpu_rebuild_model.py."""
 import os
 
 import numpy as np
