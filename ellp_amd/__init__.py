@@ -109,6 +109,12 @@ class _StartReport(C.Structure):
     _fields_ = [("used", C.c_int), ("reason", C.c_int), ("info", _engine.StartInfo)]
 
 
+class _ResultCert(C.Structure):
+    """ellp_result_cert (include/ellp_host.h)"""
+    _fields_ = [("kind", C.c_int), ("reason", C.c_char * 128), ("n", C.c_int64), ("vec", C.POINTER(C.c_double)),
+                ("info", _engine.CertInfo)]
+
+
 class _FlatPhase(C.Structure):
     _fields_ = ([(k, C.c_int64) for k in ("m", "n", "n_c", "n_B", "n_N")] +
                 [(k, C.POINTER(C.c_double)) for k in ("A", "c", "b", "lb", "ub", "x", "y", "d")] +
@@ -161,6 +167,10 @@ def host_lib():
     L.ellp_solve_start.restype = C.c_int
     L.ellp_solve_start.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_uint, C.POINTER(_Start),
                                    C.POINTER(_ResultRng), C.POINTER(_StartReport)]
+    L.ellp_solve_cert.restype = C.c_int
+    L.ellp_solve_cert.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(Opts), C.c_uint, C.POINTER(_Start),
+                                  C.POINTER(_ResultRng), C.POINTER(_StartReport), C.POINTER(_ResultCert)]
+    L.ellp_result_cert_free.argtypes = [C.POINTER(_ResultCert)]
     L.ellp_debug_map_start.restype = C.c_int
     L.ellp_debug_map_start.argtypes = [C.c_void_p, C.POINTER(_Start), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int64]
@@ -336,6 +346,10 @@ class SolverResult:
 
     def __init__(self, kind, solution=None, obj=None, iters=(0, 0)):
         self.kind, self.solution, self.obj, self.iters = kind, solution, obj, iters
+        # solve(..., certificate=True): a dict with kind ("farkas" / "ray"), y (one per constraint, the signs of duals()) or ray
+        # (one per variable), reason and the device's report (ellp_cert_info); None where there is none, certificate_reason
+        # then says which case it is
+        self.certificate, self.certificate_reason = None, None
 
     def __repr__(self):
         if self.kind == self.Optimal:
@@ -361,8 +375,29 @@ class _Solver:
     def default(cls):
         return cls()
 
-    def solve(self, prob, start=None, postsolve=False, ranging=False):
-        """postsolve=True: an Optimal result's Solution also has duals(), reduced_costs() and kkt() (one more pass on the
+    def _solve_cert(self, prob, start, flags):
+        st, keep = _start_struct(start) if start is not None else (None, None)
+        rr, rep, rc = _ResultRng(), _StartReport(), _ResultCert()
+        host_lib().ellp_solve_cert(prob._h, self._KIND, self.max_iter, C.byref(self._opts) if self._opts is not None else None,
+                                   flags | 4, C.byref(st) if st is not None else None, C.byref(rr), C.byref(rep), C.byref(rc))
+        del keep
+        try:
+            res = _started_result(rr, rep if start is not None else None, basis=start is not None)
+            res.certificate_reason = rc.reason.decode()
+            if rc.kind:
+                vec = np.ctypeslib.as_array(rc.vec, shape=(rc.n,)).copy() if rc.n else np.zeros(0)
+                res.certificate = dict(rc.info.as_dict(), reason=res.certificate_reason, **{"y" if rc.kind == 1 else "ray": vec})
+            return res
+        finally:
+            host_lib().ellp_result_cert_free(C.byref(rc))
+            host_lib().ellp_result_rng_free(C.byref(rr))
+
+    def solve(self, prob, start=None, postsolve=False, ranging=False, certificate=False):
+        """certificate=True: an Infeasible or Unbounded result carries its proof in .certificate (a Farkas vector or a ray with the
+        device's report on it; None with .certificate_reason where the ending is one that has none).  Off by default, and off
+        means not one extra device call.
+
+        postsolve=True: an Optimal result's Solution also has duals(), reduced_costs() and kkt() (one more pass on the
         device after the solve; off by default, and off means not one extra device call).  ranging=True (implies the
         postsolve): also cost_ranging(), rhs_ranging() and basis().
 
@@ -372,6 +407,8 @@ class _Solver:
         the solve is exactly the cold one.  Each solver runs its own method only: after a changed right-hand side use the
         dual solver, after a changed cost the primal solver.  The result has .start = dict(used, reason, ...) (reasons:
         include/ellp_host.h), and an Optimal Solution's basis() works without ranging=True, so re-solves chain."""
+        if certificate:
+            return self._solve_cert(prob, start, (3 if ranging else 0) | (1 if postsolve else 0))
         if start is not None:
             return self._solve_start(prob, start, (3 if ranging else 0) | (1 if postsolve else 0))
         if ranging:
@@ -560,9 +597,10 @@ class _Solver:
         return out
 
 
-def _started_result(rr, rep):
+def _started_result(rr, rep, basis=True):
     """SolverResult from a filled ellp_result_rng of ellp_solve_start / ellp_solve_batch_start: .start from the report (None: the
-    problem had no start), and on Optimal the postsolve, the basis and the ranging that came with it"""
+    problem had no start), and on Optimal the postsolve, the basis and the ranging that came with it (basis False: a result of
+    ellp_solve_cert without a start, which carries the basis only with the ranging)"""
     res = _to_result(rr.ex.result)
     if rep is not None:
         res.start = dict(rep.info.as_dict(), used=bool(rep.used), reason=int(rep.reason))
@@ -571,6 +609,8 @@ def _started_result(rr, rep):
         arr = lambda p, n: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=p._type_)
         if rx.has_postsolve:
             res.solution._post = (arr(rx.duals, rx.n_duals), arr(rx.reduced_costs, rx.n_reduced_costs), rx.kkt.as_dict())
+        if not basis and not rr.has_ranging:
+            return res
         res.solution._basis = dict(B=arr(rr.B_index, rr.n_B), N=arr(rr.N_index, rr.n_N), Nb=arr(rr.N_bound, rr.n_N),
                                    x=arr(rr.x_std, rr.n_x_std), row_origin=arr(rr.row_origin, rr.n_B))
         if rr.has_ranging:

@@ -77,6 +77,24 @@ class StartInfo(C.Structure):
         return d
 
 
+CERT_FARKAS_COSTS, CERT_FARKAS_ROW, CERT_RAY_COLUMN = 0, 1, 2
+CERT_KIND_NAME = {0: None, 1: "farkas", 2: "ray"}
+
+
+class CertInfo(C.Structure):
+    """ellp_cert_info (include/ellp_hip.h): what a certificate call found and how good a proof it is"""
+    _fields_ = [("kind", C.c_int32), ("found", C.c_int32), ("source", C.c_int64), ("qualifying", C.c_int64),
+                ("gap", C.c_double), ("y_b", C.c_double), ("sup", C.c_double), ("dir_violation", C.c_double),
+                ("residual", C.c_double), ("c_r", C.c_double), ("bound_dir_violation", C.c_double), ("norm", C.c_double),
+                ("worst_dir_var", C.c_int64), ("worst_row", C.c_int64), ("worst_bound_var", C.c_int64),
+                ("refine_steps", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["kind"] = CERT_KIND_NAME.get(d["kind"])
+        return d
+
+
 # int fn(void *user, void *host_buffer, int64_t segment_bytes, int world)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
 
@@ -274,8 +292,53 @@ def lib():
     L.ellp_basis_start.restype = C.c_int
     L.ellp_basis_start.argtypes = [C.c_int64, C.c_int64] + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                    C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(StartInfo), C.c_char_p, C.c_size_t]
+    cert_tail = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CertInfo), C.c_char_p, C.c_size_t]
+    L.ellp_engine_certificate.restype = C.c_int
+    L.ellp_engine_certificate.argtypes = [C.c_void_p] + cert_tail
+    L.ellp_certificate.restype = C.c_int
+    L.ellp_certificate.argtypes = _PROBLEM_ARGS + [C.POINTER(Opts)] + cert_tail
+    L.ellp_certificate_info.restype = None
+    L.ellp_certificate_info.argtypes = [C.POINTER(C.c_uint64)]
     _lib = L
     return L
+
+
+def _cert_args(m, n, source, n_check, chk, vec):
+    """the trailing arguments of the two certificate calls: (source, n_check, chk_kind, chk_lb, chk_ub, vec, info) and what
+    keeps the arrays alive"""
+    n_check = int(n if n_check is None else n_check)
+    if chk is None:
+        keep = (None, None, None)
+    else:
+        keep = (np.ascontiguousarray(chk[0], dtype=np.uint8), _f64(chk[1]), _f64(chk[2]))
+        if min(a.size for a in keep) < n_check:
+            raise ValueError("certificate: chk arrays shorter than n_check")
+    if vec is None:
+        vec = np.zeros(max(m if source != CERT_RAY_COLUMN else n_check, 1))
+    return n_check, keep, vec, CertInfo()
+
+
+def certificate(fp, source, n_check=None, chk=None, opts=None, vec=None):
+    """ellp_certificate on the basis, labels and point a FlatProblem holds: (vec or None, info_dict).  source: CERT_FARKAS_COSTS,
+    CERT_FARKAS_ROW (vec: m entries by row) or CERT_RAY_COLUMN (vec: n_check entries by variable); n_check: the leading columns
+    the report is made on (default all); chk = (kind, lb, ub): the bounds it is made against (default the problem's own);
+    vec: an array to fill (left as it is unless info["found"]).  Raises EllpHipError on any status but OPTIMAL."""
+    o = opts or default_opts()
+    n_check, keep, vec, info = _cert_args(fp.m, fp.n, source, n_check, chk, vec)
+    err = C.create_string_buffer(512)
+    s = lib().ellp_certificate(*fp._args(), C.byref(o), int(source), n_check, _p(keep[0]), _p(keep[1]), _p(keep[2]), _p(vec),
+                               C.byref(info), err, 512)
+    if s != OPTIMAL:
+        raise EllpHipError(s, err.value.decode())
+    return (vec if info.found else None), info.as_dict()
+
+
+def certificate_info():
+    """ellp_certificate_info: calls of the two certificate entry points so far in this process, and the kernel launches and
+    refinement steps of the last one"""
+    out = (C.c_uint64 * 4)()
+    lib().ellp_certificate_info(out)
+    return {"calls": int(out[0]), "launches": int(out[1]), "refine_steps": int(out[2])}
 
 
 def qr_transposed(A, device=-1):
@@ -856,6 +919,18 @@ class Engine:
         if s not in (OPTIMAL, UNBOUNDED, MAXITER):
             raise EllpHipError(s, err.value.decode())
         return rg._done()
+
+    def certificate(self, source, n_check=None, chk=None, vec=None):
+        """ellp_engine_certificate on the basis, labels and point the engine stands on: (vec or None, info_dict), the
+        arguments of certificate().  The engine's state is not touched."""
+        fp = self.fp
+        n_check, keep, vec, info = _cert_args(fp.m, fp.n, source, n_check, chk, vec)
+        err = C.create_string_buffer(512)
+        s = lib().ellp_engine_certificate(self._h, int(source), n_check, _p(keep[0]), _p(keep[1]), _p(keep[2]), _p(vec),
+                                          C.byref(info), err, 512)
+        if s != OPTIMAL:
+            raise EllpHipError(s, err.value.decode())
+        return (vec if info.found else None), info.as_dict()
 
     def tableau_rows(self, positions, want_rho=True):
         """ellp_engine_tableau_rows: (alpha, rho) — alpha[p] = row positions[p] of the tableau B^-1 A_N by nonbasic position,

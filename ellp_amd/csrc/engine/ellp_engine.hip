@@ -3098,6 +3098,16 @@ struct ellp_engine : EnginePlan {  // the fields creation decides are the plan's
     int64_t *rng_cblk = nullptr, *rng_rblk = nullptr;  // blocking down, up
     double *rng_res = nullptr;                        // the tile maxima of |I - A_B W|, then the maximum
     int *rng_fail = nullptr;
+    // certificates (ellp_cert.inc): its workspace, made at the first call on top of the two above
+    bool cert_ready = false;
+    double *cert_x = nullptr, *cert_xb = nullptr, *cert_t = nullptr, *cert_res = nullptr, *cert_dx = nullptr;  // a point of its own
+    double *cert_xpart = nullptr, *cert_omega = nullptr, *cert_rsval = nullptr;
+    int64_t *cert_rspos = nullptr;
+    double *cert_vec = nullptr, *cert_rhs = nullptr, *cert_zero = nullptr;  // the vector, +-e_r, zeros (never written)
+    uint8_t *cert_bits = nullptr, *cert_ckind = nullptr;                   // the searches' flag bytes; the bounds to verify against
+    double *cert_clb = nullptr, *cert_cub = nullptr;
+    int64_t *cert_pick = nullptr;       // first position, count, NaN flag, side
+    double *cert_ver = nullptr;         // the report's numbers (CertVerify)
     double *c_tail = nullptr;  // n_c > n: the costs without a column (primal phase 1 with free variables), for the postsolve
     uint64_t hy_uncertified = 0;
     // the LP is a "box problem" — every bound TwoSided or Fixed and b = 0: the shape of DualPhase1's LP (dual_problem.rs:89-131),
@@ -4824,3 +4834,4 @@ ellp_status ellp_dual_solve_with_initial(int64_t m, int64_t n, int64_t n_c, cons
 #include "ellp_bstart.inc"
 #include "ellp_range.inc"
 #include "ellp_brange.inc"
+#include "ellp_cert.inc"

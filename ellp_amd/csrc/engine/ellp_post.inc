@@ -34,6 +34,9 @@ namespace {
 
 constexpr int POST_TR = 512;  // rows per tile
 constexpr long long LLONG_MAX_POST = 0x7fffffffffffffffLL;  // "no index yet" of a maximum
+// kernels enqueued so far by post_launch_pass, start_fold, start_solve_x and the certificates' own stages, each counted where
+// it is launched (ellp_certificate_info reports the difference over a call; diagnostics, not thread safe)
+uint64_t g_post_launches = 0;
 
 // s + e = a + b exactly (Knuth)
 __device__ __forceinline__ void post_two_sum(double a, double b, double &s, double &e) {
@@ -445,7 +448,16 @@ hipError_t post_workspace(ellp_engine *e) {
     return hipSuccess;
 }
 
-void post_launch_pass(ellp_engine *e, bool basic) {
+// what a pass or a solve takes in place of the engine's own vectors (ellp_cert.inc): the costs by position, the vector in
+// y's place, the point; refactor false: post_luw already holds the LU of A_B
+struct PostOver {
+    const double *cB, *cN;
+    double *y;
+    const double *x;
+    bool refactor;
+};
+
+void post_launch_pass(ellp_engine *e, bool basic, const PostOver *ov = nullptr) {
     const int64_t m = e->m, nN = e->nN;
     const int64_t ncols = basic ? m : nN;
     if (ncols <= 0) return;
@@ -453,8 +465,8 @@ void post_launch_pass(ellp_engine *e, bool basic) {
     PostPassArgs a{};
     a.C = basic ? e->A_B : e->A_N;
     a.index = basic ? e->B_index : e->N_index;
-    a.y = e->post_y;
-    a.x = e->x;
+    a.y = ov ? ov->y : e->post_y;
+    a.x = ov ? ov->x : e->x;
     a.dpart = e->post_dpart;
     a.rpart = e->post_rpart;
     a.m = m;
@@ -466,7 +478,7 @@ void post_launch_pass(ellp_engine *e, bool basic) {
     hipLaunchKernelGGL(k_post_pass, dim3((unsigned)post_blocks(ncols), (unsigned)ntiles), dim3(256), 0, e->stream, a);
     PostDfoldArgs f{};
     f.dpart = e->post_dpart;
-    f.cpos = basic ? e->c_B : e->c_N;
+    f.cpos = basic ? (ov ? ov->cB : e->c_B) : (ov ? ov->cN : e->c_N);
     f.index = a.index;
     f.d = e->post_d;
     f.rho = basic ? e->post_rho : nullptr;
@@ -475,6 +487,7 @@ void post_launch_pass(ellp_engine *e, bool basic) {
     f.dstride = a.dstride;
     f.ntiles = ntiles;
     hipLaunchKernelGGL(k_post_dfold, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, e->stream, f);
+    g_post_launches += 2;
 }
 
 // ELLP_POST_PROFILE=1 (measurements, tools/postsolve_time.py): the stages of a postsolve bracketed with HIP events; one line on
@@ -520,19 +533,22 @@ struct PostProf {
 
 // the fresh LU of A_B and the refined y (post_y; rho, den and omega of it; the basic part of d and of the partial sums of r
 // from the last pass over A_B); *steps: the refinement steps taken.  Shared by the postsolve and ellp_basis_start
-ellp_status post_solve_y(ellp_engine *e, PostProf &prof, int32_t *steps_out, char *errbuf, size_t errlen) {
+ellp_status post_solve_y(ellp_engine *e, PostProf &prof, int32_t *steps_out, char *errbuf, size_t errlen, const PostOver *ov = nullptr) {
     const int64_t m = e->m, ld = e->ld;
+    const double *cB = ov ? ov->cB : e->c_B;
+    double *yv = ov ? ov->y : e->post_y;
     const size_t lds = 2 * sizeof(double) * (size_t)m;
     const unsigned mb = (unsigned)((m + 255) / 256);
     HIPCHK(hipMemsetAsync(e->post_fail, 0, sizeof(int), e->stream));
-    prof.begin(PostProf::LU);
-    hipLaunchKernelGGL(k_rows_from_cols, dim3((unsigned)((m + 31) / 32), (unsigned)((m + 31) / 32)), dim3(256), 0, e->stream, e->A_B,
-                       e->post_luw.M, m, ld);
-    ellp_lu_rows_factor(&e->post_luw, e->stream);
-    prof.end();
+    if (!ov || ov->refactor) {
+        prof.begin(PostProf::LU);
+        hipLaunchKernelGGL(k_rows_from_cols, dim3((unsigned)((m + 31) / 32), (unsigned)((m + 31) / 32)), dim3(256), 0, e->stream, e->A_B,
+                           e->post_luw.M, m, ld);
+        ellp_lu_rows_factor(&e->post_luw, e->stream);
+        prof.end();
+    }
     prof.begin(PostProf::SOLVE);
-    hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds, e->stream, e->post_luw.M, e->post_luw.piv, m, e->c_B, e->post_y, 1,
-                       e->post_fail);
+    hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds, e->stream, e->post_luw.M, e->post_luw.piv, m, cB, yv, 1, e->post_fail);
     prof.end();
     int fail = 0;
     HIPCHK(hipMemcpyAsync(&fail, e->post_fail, sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -544,14 +560,14 @@ ellp_status post_solve_y(ellp_engine *e, PostProf &prof, int32_t *steps_out, cha
     }
     prof.begin(PostProf::REST);
     hipLaunchKernelGGL(k_post_singletons, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, e->stream, e->A_B, m, ld, e->post_srow, e->post_sval);
-    hipLaunchKernelGGL(k_post_snap, dim3(mb), dim3(256), 0, e->stream, e->post_y, e->c_B, e->post_srow, e->post_sval, m);
+    hipLaunchKernelGGL(k_post_snap, dim3(mb), dim3(256), 0, e->stream, yv, cB, e->post_srow, e->post_sval, m);
     prof.end();
     const double two_u = 2.220446049250313e-16;  // 2 u, u = 2^-53
     double omega = 0.0, last = 0.0;
     int32_t steps = 0;
     for (;;) {
         prof.begin(PostProf::PASS);
-        post_launch_pass(e, true);
+        post_launch_pass(e, true, ov);
         prof.end();
         hipLaunchKernelGGL(k_post_omega, dim3(1), dim3(1024), 0, e->stream, e->post_rho, e->post_den, m, e->post_omega);
         HIPCHK(hipMemcpyAsync(&omega, e->post_omega, sizeof(double), hipMemcpyDeviceToHost, e->stream));
@@ -562,8 +578,8 @@ ellp_status post_solve_y(ellp_engine *e, PostProf &prof, int32_t *steps_out, cha
         hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds, e->stream, e->post_luw.M, e->post_luw.piv, m, e->post_rho,
                            e->post_dy, 1, e->post_fail);
         prof.end();
-        hipLaunchKernelGGL(k_post_axpy, dim3(mb), dim3(256), 0, e->stream, e->post_y, e->post_dy, m);
-        hipLaunchKernelGGL(k_post_snap, dim3(mb), dim3(256), 0, e->stream, e->post_y, e->c_B, e->post_srow, e->post_sval, m);
+        hipLaunchKernelGGL(k_post_axpy, dim3(mb), dim3(256), 0, e->stream, yv, e->post_dy, m);
+        hipLaunchKernelGGL(k_post_snap, dim3(mb), dim3(256), 0, e->stream, yv, cB, e->post_srow, e->post_sval, m);
         last = omega;
         steps += 1;
     }

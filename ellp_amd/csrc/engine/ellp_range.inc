@@ -267,7 +267,14 @@ struct RngTabArgs {
     double *out;            // STORE 1: nrows x nN
     int64_t m, ld, ldw, nrows, nN;
     double eps;
+    // STORE 2, 3 (ellp_cert.inc): the point, the bounds and the basis the ray's row test reads; the flag bytes
+    const double *cx, *clb, *cub;
+    const int64_t *cB;
+    uint8_t *cbits;
 };
+// the epilogues of the certificate's searches (ellp_cert.inc): STORE 2 the Farkas row flags, STORE 3 the ray's column flags
+template <int STORE>
+__device__ __forceinline__ void cert_tab_epilogue(const RngTabArgs &a, const mfma_d4 (&acc)[4][2], int *scratch, int64_t bx, int64_t by);
 
 // tile (row block by, column block bx) by one workgroup of 512 threads.  Shared by k_range_tab and k_brange_tab
 // (ellp_brange.inc), which takes a and bx per workgroup from a table
@@ -343,6 +350,10 @@ __device__ __forceinline__ void range_tab_tile(const RngTabArgs &a, int64_t bx, 
     }
 
     // ---- epilogue: element v of acc[r][c] is row i0 + wr * 64 + r * 16 + fk + 4 v, column j0 + wc * 32 + c * 16 + fr
+    if constexpr (STORE >= 2) {  // sA is free: the last stage's readers are past the loop's final barrier
+        cert_tab_epilogue<STORE>(a, acc, reinterpret_cast<int *>(&sA[0][0][0]), bx, by);
+        return;
+    }
     if (STORE) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)

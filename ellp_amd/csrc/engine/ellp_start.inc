@@ -212,6 +212,60 @@ void start_fold(ellp_engine *e, int64_t first, int64_t count, const double *base
     const int64_t m = e->m;
     hipLaunchKernelGGL(k_post_rfold, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, e->stream, e->post_rpart + first * m * 2, base, out, m,
                        count);
+    g_post_launches += 1;
+}
+
+// Step 5, stated once: xb = B^-1 t with the LU in post_luw, written into x at B_index — the solve, the singleton-row snap, and
+// refinement while omega_x > 2u, fewer than 4 steps were taken and the last step at least halved omega (the rule of y's
+// refinement).  ov: whose point the residual pass reads (null: the engine's own x, which must then be w.x).  Shared by
+// ellp_basis_start and the certificates (ellp_cert.inc)
+struct StartXWork {
+    double *t, *xb, *res, *dx, *xpart, *xomega, *x;
+    int64_t *rs_pos;
+    double *rs_val;
+};
+ellp_status start_solve_x(ellp_engine *e, const StartXWork &w, const PostOver *ov, PostProf &prof, double *omega_out, int32_t *steps_out,
+                          char *errbuf, size_t errlen) {
+    const int64_t m = e->m, ld = e->ld;
+    const size_t lds = 2 * sizeof(double) * (size_t)m;
+    const unsigned mb = (unsigned)((m + 255) / 256);
+    const int nchunks = (int)((m + START_XC - 1) / START_XC);
+    const int64_t bB = post_blocks(m);
+    prof.begin(PostProf::SOLVE);
+    hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds, e->stream, e->post_luw.M, e->post_luw.piv, m, w.t, w.xb, 0, e->post_fail);
+    prof.end();
+    hipLaunchKernelGGL(k_start_axpy, dim3(mb), dim3(256), 0, e->stream, w.xb, (const double *)nullptr, w.x, e->B_index, m);
+    hipLaunchKernelGGL(k_start_rowsing, dim3(mb), dim3(256), 0, e->stream, e->A_B, m, ld, w.rs_pos, w.rs_val);
+    hipLaunchKernelGGL(k_start_snap, dim3(mb), dim3(256), 0, e->stream, w.xb, w.x, w.t, e->B_index, w.rs_pos, w.rs_val, m);
+    g_post_launches += 4;
+    const double two_u = 2.220446049250313e-16;
+    double omega = 0.0, last = 0.0;
+    int32_t xsteps = 0;
+    for (;;) {
+        prof.begin(PostProf::PASS);
+        post_launch_pass(e, true, ov);  // the partial sums of A_B x_B (y is unchanged: rho, den and d on the basis keep their bits)
+        prof.end();
+        prof.begin(PostProf::REST);
+        start_fold(e, 0, bB, w.t, w.res);
+        hipLaunchKernelGGL(k_start_xden, dim3(mb, (unsigned)nchunks), dim3(256), 0, e->stream, e->A_B, w.xb, w.xpart, m, ld);
+        hipLaunchKernelGGL(k_start_omega, dim3(1), dim3(1024), 0, e->stream, w.res, w.t, w.xpart, m, nchunks, w.xomega);
+        g_post_launches += 2;
+        prof.end();
+        HIPCHK(hipMemcpyAsync(&omega, w.xomega, sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (!(omega > two_u) || xsteps >= 4 || (xsteps > 0 && !(omega <= 0.5 * last))) break;
+        prof.begin(PostProf::SOLVE);
+        hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds, e->stream, e->post_luw.M, e->post_luw.piv, m, w.res, w.dx, 0, e->post_fail);
+        prof.end();
+        hipLaunchKernelGGL(k_start_axpy, dim3(mb), dim3(256), 0, e->stream, w.xb, (const double *)w.dx, w.x, e->B_index, m);
+        hipLaunchKernelGGL(k_start_snap, dim3(mb), dim3(256), 0, e->stream, w.xb, w.x, w.t, e->B_index, w.rs_pos, w.rs_val, m);
+        g_post_launches += 3;
+        last = omega;
+        xsteps += 1;
+    }
+    *omega_out = omega;
+    *steps_out = xsteps;
+    return ELLP_OPTIMAL;
 }
 
 // the refusals of ellp_basis_start, host only (ellp_batch_basis_start makes them per item)
@@ -307,8 +361,6 @@ ellp_status ellp_basis_start(int64_t m, int64_t n, const double *A, const double
     int32_t ysteps = 0;
     s = post_solve_y(e, prof, &ysteps, errbuf, errlen);
     if (s != ELLP_OPTIMAL) return s;  // ELLP_ERR_SINGULAR: nothing was written
-    const size_t lds = 2 * sizeof(double) * (size_t)m;
-    const unsigned mb = (unsigned)((m + 255) / 256);
     const int64_t wide = m > n_N ? m : n_N;
     const int64_t bB = post_blocks(m), bN = post_blocks(n_N);
     StartLabelArgs la{};
@@ -330,35 +382,11 @@ ellp_status ellp_basis_start(int64_t m, int64_t n, const double *A, const double
     start_fold(e, bB, bN, e->b_dev, t);
     prof.end();
     // 5: x_B and its refinement
-    prof.begin(PostProf::SOLVE);
-    hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds, e->stream, e->post_luw.M, e->post_luw.piv, m, t, xb, 0, e->post_fail);
-    prof.end();
-    hipLaunchKernelGGL(k_start_axpy, dim3(mb), dim3(256), 0, e->stream, xb, (const double *)nullptr, e->x, e->B_index, m);
-    hipLaunchKernelGGL(k_start_rowsing, dim3(mb), dim3(256), 0, e->stream, e->A_B, m, ld, rs_pos, rs_val);
-    hipLaunchKernelGGL(k_start_snap, dim3(mb), dim3(256), 0, e->stream, xb, e->x, t, e->B_index, rs_pos, rs_val, m);
-    const double two_u = 2.220446049250313e-16;
-    double omega = 0.0, last = 0.0;
+    double omega = 0.0;
     int32_t xsteps = 0;
-    for (;;) {
-        prof.begin(PostProf::PASS);
-        post_launch_pass(e, true);  // the partial sums of A_B x_B (y is unchanged: rho, den and d on the basis keep their bits)
-        prof.end();
-        prof.begin(PostProf::REST);
-        start_fold(e, 0, bB, t, res);
-        hipLaunchKernelGGL(k_start_xden, dim3(mb, (unsigned)nchunks), dim3(256), 0, e->stream, e->A_B, xb, xpart, m, ld);
-        hipLaunchKernelGGL(k_start_omega, dim3(1), dim3(1024), 0, e->stream, res, t, xpart, m, nchunks, xomega);
-        prof.end();
-        HIPCHK(hipMemcpyAsync(&omega, xomega, sizeof(double), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (!(omega > two_u) || xsteps >= 4 || (xsteps > 0 && !(omega <= 0.5 * last))) break;  // the rule of y's refinement
-        prof.begin(PostProf::SOLVE);
-        hipLaunchKernelGGL(k_lu_solve, dim3(1), dim3(1024), lds, e->stream, e->post_luw.M, e->post_luw.piv, m, res, dx, 0, e->post_fail);
-        prof.end();
-        hipLaunchKernelGGL(k_start_axpy, dim3(mb), dim3(256), 0, e->stream, xb, (const double *)dx, e->x, e->B_index, m);
-        hipLaunchKernelGGL(k_start_snap, dim3(mb), dim3(256), 0, e->stream, xb, e->x, t, e->B_index, rs_pos, rs_val, m);
-        last = omega;
-        xsteps += 1;
-    }
+    const StartXWork xw{t, xb, res, dx, xpart, xomega, e->x, rs_pos, rs_val};
+    s = start_solve_x(e, xw, nullptr, prof, &omega, &xsteps, errbuf, errlen);
+    if (s != ELLP_OPTIMAL) return s;
     // 6: the report of the finished point and the verdict
     prof.begin(PostProf::REST);
     start_fold(e, 0, bB + bN, e->b_dev, e->post_r);

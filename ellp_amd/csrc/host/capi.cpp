@@ -105,12 +105,21 @@ ellp::EngineOptions engine_options(const ellp_opts *opts) {
 }
 // *out from what `run` returns or throws
 template <class F>
-int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr, ellp_result_rng *rng = nullptr, bool basis_always = false) {
+int fill_result(ellp_result *out, F &&run, ellp_result_ex *ex = nullptr, ellp_result_rng *rng = nullptr, bool basis_always = false,
+                ellp_result_cert *cert = nullptr) {
     std::memset(out, 0, sizeof(*out));
     try {
         ellp::SolverResult r = run();
         out->iters_phase1 = r.iters_phase1;
         out->iters_phase2 = r.iters_phase2;
+        if (cert && r.cert) {
+            cert->kind = static_cast<int>(r.cert->kind);
+            put(cert->reason, sizeof(cert->reason), r.cert->reason.c_str());
+            cert->n = static_cast<int64_t>(r.cert->vec.size());
+            cert->vec = new double[r.cert->vec.size() ? r.cert->vec.size() : 1];
+            std::memcpy(cert->vec, r.cert->vec.data(), sizeof(double) * r.cert->vec.size());
+            cert->info = r.cert->info;
+        }
         switch (r.kind) {
         case ellp::SolverResult::Optimal: {
             out->status = ELLP_OPTIMAL;
@@ -281,6 +290,53 @@ int ellp_solve_start(const ellp_problem *p, int solver, uint64_t max_iter, const
         report->info = rep.info;
     }
     return s;
+}
+
+int ellp_solve_cert(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, unsigned flags, const ellp_start *start,
+                    ellp_result_rng *out, ellp_start_report *report, ellp_result_cert *cert) {
+    if (report) std::memset(report, 0, sizeof(*report));
+    if (cert) std::memset(cert, 0, sizeof(*cert));
+    if (!out) return ELLP_ERR_ARG;
+    std::memset(out, 0, sizeof(*out));
+    if (!p || !cert || (solver != ELLP_SOLVER_PRIMAL && solver != ELLP_SOLVER_DUAL) ||
+        (flags & ~(ELLP_SOLVE_POSTSOLVE | ELLP_SOLVE_RANGING | ELLP_SOLVE_CERTIFICATE))) {
+        out->ex.result.status = ELLP_ERR_ARG;
+        put(out->ex.result.err, sizeof(out->ex.result.err), "ellp_solve_cert: no problem, no cert, an unknown solver or an unknown flag");
+        return ELLP_ERR_ARG;
+    }
+    const unsigned rest = flags & ~ELLP_SOLVE_CERTIFICATE;
+    if (!(flags & ELLP_SOLVE_CERTIFICATE))  // exactly the existing entry points
+        return start ? ellp_solve_start(p, solver, max_iter, opts, rest, start, out, report) : ellp_solve_flags(p, solver, max_iter, opts, rest, out);
+    const ellp::EngineOptions eo = engine_options(opts);
+    const std::optional<std::uint64_t> mi =
+        max_iter == ELLP_MAX_ITER_NONE ? std::nullopt : std::optional<std::uint64_t>(max_iter);
+    const bool post = (flags & ELLP_SOLVE_POSTSOLVE) != 0, rng = (flags & ELLP_SOLVE_RANGING) != 0;
+    ellp::StartReport rep;
+    ellp::StartBasis sb;
+    if (start) sb = start_basis(start);
+    ellp_result base;
+    const int s = fill_result(&base, [&] {
+        ellp::PrimalSimplexSolver ps(mi);
+        ellp::DualSimplexSolver ds(mi);
+        ps.with_engine(eo).with_postsolve(post).with_ranging(rng).with_certificate(true);
+        ds.with_engine(eo).with_postsolve(post).with_ranging(rng).with_certificate(true);
+        if (start) return solver == ELLP_SOLVER_PRIMAL ? ps.solve_from(p->prob, sb, &rep) : ds.solve_from(p->prob, sb, &rep);
+        return solver == ELLP_SOLVER_PRIMAL ? ps.solve(p->prob) : ds.solve(p->prob);
+    }, &out->ex, out, /*basis_always=*/start != nullptr, cert);
+    out->ex.result = base;
+    if (report && start) {
+        report->used = rep.used ? 1 : 0;
+        report->reason = rep.reason;
+        report->info = rep.info;
+    }
+    return s;
+}
+
+void ellp_result_cert_free(ellp_result_cert *c) {
+    if (!c) return;
+    delete[] c->vec;
+    c->vec = nullptr;
+    c->n = 0;
 }
 
 int ellp_debug_map_start(const ellp_problem *p, const ellp_start *start, int64_t *rows, int64_t *cols, int64_t *B_out, int64_t *N_out,

@@ -207,11 +207,23 @@ struct Solution {  // src/solver.rs:35-54
     const ellp_kkt &kkt() const { return postsolve().kkt; }
 };
 
+// extension (with_certificate(true)): the proof an Infeasible or Unbounded result carries (ellp_engine_certificate /
+// ellp_certificate, include/ellp_hip.h has the definitions).  Farkas: vec has one entry per constraint of the Problem, with the
+// sign convention of duals() (0.0 for a row the rank check dropped); Ray: one per variable of the Problem.  info is the device's
+// report on the standard form the vector was made on.  kind None: there is no certificate, and reason says which case it is
+struct Certificate {
+    enum Kind { None = 0, Farkas = 1, Ray = 2 } kind = None;
+    std::string reason;
+    std::vector<double> vec;
+    ellp_cert_info info{};
+};
+
 struct SolverResult {  // src/solver.rs:6-12
     enum Kind { Optimal, Infeasible, Unbounded, MaxIter } kind = Infeasible;
     std::optional<Solution> solution;  // Optimal
     double max_iter_obj = 0.0;         // MaxIter { obj }
     std::uint64_t iters_phase1 = 0, iters_phase2 = 0;  // extension: iteration counts of the device loops
+    std::optional<Certificate> cert;   // set by a solver made with_certificate(true), whatever the result
 };
 
 // solvers/trivial/solve_trivial_problem.rs:5-96
@@ -270,6 +282,9 @@ public:
     // extension, off by default (off: not one extra device call): an Optimal Solution carries ranging(); implies the postsolve, which
     // comes out of the same device call (one LU, not two)
     PrimalSimplexSolver &with_ranging(bool on) { ranging_ = on; if (on) postsolve_ = true; return *this; }
+    // extension, off by default (off: not one extra device call): the result carries a Certificate — a Farkas vector where phase 1
+    // ends Optimal with a positive objective, a ray where phase 2 ends Unbounded, else kind None with the reason
+    PrimalSimplexSolver &with_certificate(bool on) { certificate_ = on; return *this; }
 
     SolverResult solve(Problem prob) const;  // :32-93
     // extension: phase 2 directly from the point of `start` where that point is primal feasible (ellp_basis_start, KEEP_LABELS),
@@ -284,6 +299,7 @@ private:
     EngineOptions engine_;
     bool postsolve_ = false;
     bool ranging_ = false;
+    bool certificate_ = false;
 };
 
 class DualSimplexSolver {  // src/solvers/dual/dual_simplex_solver.rs:16-108
@@ -294,6 +310,9 @@ public:
     DualSimplexSolver &with_engine(const EngineOptions &o) { engine_ = o; return *this; }
     DualSimplexSolver &with_postsolve(bool on) { postsolve_ = on; return *this; }
     DualSimplexSolver &with_ranging(bool on) { ranging_ = on; if (on) postsolve_ = true; return *this; }
+    // extension, off by default: a Farkas vector where phase 2 ends Infeasible; the fall-back into the primal solver passes the
+    // option on and returns that result's certificate
+    DualSimplexSolver &with_certificate(bool on) { certificate_ = on; return *this; }
 
     SolverResult solve(Problem prob) const;
     // extension: phase 2 directly from the point of `start` where it is dual feasible (ellp_basis_start, LABELS_BY_D); else
@@ -307,6 +326,7 @@ private:
     EngineOptions engine_;
     bool postsolve_ = false;
     bool ranging_ = false;
+    bool certificate_ = false;
 };
 
 // Many problems solved by one solver (solver: ELLP_SOLVER_PRIMAL / ELLP_SOLVER_DUAL) in lock step, the device loops of a

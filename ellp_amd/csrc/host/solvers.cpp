@@ -287,6 +287,73 @@ void attach_ranging(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
     map_ranging(sol, ra);
 }
 
+// with_certificate(true): no certificate, and why (reason: one of the cases of DESIGN.md §3.12)
+void no_certificate(SolverResult &res, const char *reason) {
+    Certificate c;
+    c.reason = reason;
+    res.cert = std::move(c);
+}
+
+// with_certificate(true): the Farkas vector or the ray of the basis, labels and point (sf, pt) an Infeasible / Unbounded ending
+// stands on, from the resident engine where there is one and it takes the call, else from the arrays (as attach_postsolve).
+// n_check leading columns are verified against chk (null: sf's own bounds).  The vector goes to the Problem: a Farkas y to the
+// constraints by row_origin (a dropped row: 0.0), a ray to the variables.  A basis the device calls singular, or a NaN, gives
+// no certificate and says so in reason; the result itself stays what it was.
+void attach_certificate(SolverResult &res, const StandardForm &sf, const Point &pt, ellp_engine *e, const EngineOptions &eng, int source,
+                        size_t n_check, const std::vector<Bound> *chk, const char *reason) {
+    const size_t m = sf.rows(), nc = sf.bounds.size();
+    if (m == 0) return no_certificate(res, "no rows: decided by the trivial solver");
+    Certificate c;
+    std::vector<double> vec(source == ELLP_CERT_RAY_COLUMN ? n_check : m, 0.0), clb, cub;
+    std::vector<std::uint8_t> ckind;
+    if (chk) {
+        for (size_t i = 0; i < n_check; ++i) {
+            const Bound &bd = (*chk)[i];
+            ckind.push_back(static_cast<std::uint8_t>(bd.kind));
+            clb.push_back(bd.lb);
+            cub.push_back(bd.kind == Bound::Fixed ? bd.lb : bd.ub);
+        }
+    }
+    char err[512] = {0};
+    ellp_status s = ELLP_ERR_ARG;
+    const std::int64_t nchk = static_cast<std::int64_t>(n_check);
+    if (e) s = ellp_engine_certificate(e, source, nchk, chk ? ckind.data() : nullptr, chk ? clb.data() : nullptr, chk ? cub.data() : nullptr,
+                                       vec.data(), &c.info, err, sizeof(err));
+    if (s == ELLP_ERR_ARG) {  // no resident engine, or one the call refuses: the arrays go up once more
+        Flat f = flatten(sf, pt);
+        const ellp_opts o = make_opts(0, eng);
+        s = ellp_certificate(static_cast<std::int64_t>(m), static_cast<std::int64_t>(sf.cols()), static_cast<std::int64_t>(nc), sf.A.a.data(),
+                             sf.c.data(), sf.b.data(), f.kind.data(), f.lb.data(), f.ub.data(), pt.x.data(), f.B.data(),
+                             static_cast<std::int64_t>(f.B.size()), f.N.data(), f.Nb.data(), static_cast<std::int64_t>(f.N.size()), &o, source, nchk,
+                             chk ? ckind.data() : nullptr, chk ? clb.data() : nullptr, chk ? cub.data() : nullptr, vec.data(), &c.info, err,
+                             sizeof(err));
+    }
+    if (s == ELLP_ERR_SINGULAR || s == ELLP_ERR_NAN) return no_certificate(res, s == ELLP_ERR_NAN ? "the certificate call met a NaN" : "the certificate call found the basis singular");
+    if (s != ELLP_OPTIMAL) to_status(s, err);  // throws: no device, or arrays the call refuses
+    if (!c.info.found) return no_certificate(res, "search found none");
+    c.reason = reason;
+    if (source == ELLP_CERT_RAY_COLUMN) {
+        c.kind = Certificate::Ray;
+        const size_t nv = sf.prob.variables.size();
+        c.vec.assign(nv, 0.0);
+        for (size_t v = 0; v < nv && v < n_check; ++v) c.vec[v] = vec[v];
+    } else {
+        c.kind = Certificate::Farkas;
+        if (sf.row_origin.size() != m) throw EllPPanic("assertion failed: std_form.row_origin.len() == std_form.rows()");
+        c.vec.assign(sf.prob.constraints.size(), 0.0);
+        for (size_t k = 0; k < m; ++k) c.vec[sf.row_origin[k]] = vec[k];
+    }
+    res.cert = std::move(c);
+}
+
+// the bounds of StandardForm::from_problem behind a primal phase-1 form: the Problem's own on its variables (phase 1 fixes
+// dependent free ones at 0), the form's on the slacks
+std::vector<Bound> original_bounds(const StandardForm &sf, size_t n_orig) {
+    std::vector<Bound> out(sf.bounds.begin(), sf.bounds.begin() + static_cast<std::ptrdiff_t>(n_orig));
+    for (size_t i = 0; i < sf.prob.variables.size() && i < n_orig; ++i) out[i] = sf.prob.variables[i].bound;
+    return out;
+}
+
 }  // namespace
 
 // primal_simplex_solver.rs:32-93.  The two solve_with_initial calls of the reference become two
@@ -296,9 +363,15 @@ void attach_ranging(Solution &sol, ellp_engine *e, const EngineOptions &eng) {
 SolverResult PrimalSimplexSolver::solve(Problem prob) const {
     SolverResult res;
     auto p1 = PrimalPhase1::from_problem(std::move(prob));
-    if (!p1) { res.kind = SolverResult::Infeasible; return res; }
+    if (!p1) {
+        res.kind = SolverResult::Infeasible;
+        if (certificate_) no_certificate(res, "infeasibility decided by the set-up");
+        return res;
+    }
     PrimalPhase1 phase_1 = std::move(*p1);
     const bool resident = phase_1.std_form.rows() > 0 && !phase_1.point.N.empty();
+    // the columns of StandardForm::from_problem: the phase-1 columns stand behind them
+    const size_t n_orig = phase_1.phase_1_vars.empty() ? phase_1.std_form.bounds.size() : phase_1.phase_1_vars.front();
     EngineHandle eng;
     Flat f1;
     SolutionStatus s1;
@@ -322,14 +395,26 @@ SolverResult PrimalSimplexSolver::solve(Problem prob) const {
     case SolutionStatus::Optimal: {
         const double obj = phase_1.obj();
         if (!(obj > -EPS)) throw EllPPanic("assertion failed: obj > -EPS");
-        if (!(obj < EPS)) { res.kind = SolverResult::Infeasible; return res; }
+        if (!(obj < EPS)) {
+            res.kind = SolverResult::Infeasible;
+            if (certificate_) {  // phase-1 costs are zero on the problem's columns: y = B^-T c_B is the proof
+                const std::vector<Bound> chk = original_bounds(phase_1.std_form, n_orig);
+                attach_certificate(res, phase_1.std_form, phase_1.point, resident ? eng.e : nullptr, engine_, ELLP_CERT_FARKAS_COSTS, n_orig, &chk,
+                                   "primal phase 1 optimal with a positive objective");
+            }
+            return res;
+        }
         break;
     }
-    case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; return res;
+    case SolutionStatus::Infeasible:
+        res.kind = SolverResult::Infeasible;
+        if (certificate_) no_certificate(res, "primal phase 1 ended with a loop status");
+        return res;
     case SolutionStatus::Unbounded: throw EllPPanic("primal phase 1 should never be unbounded");
     case SolutionStatus::MaxIter:
         res.kind = SolverResult::MaxIter;
         res.max_iter_obj = std::numeric_limits<double>::infinity();
+        if (certificate_) no_certificate(res, "MaxIter");
         return res;
     }
     PrimalPhase2 phase_2 = PrimalPhase2::from_phase1(std::move(phase_1));
@@ -350,12 +435,19 @@ SolverResult PrimalSimplexSolver::solve(Problem prob) const {
         res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point), std::nullopt, std::nullopt};
         if (ranging_) attach_ranging(*res.solution, resident ? eng.e : nullptr, engine_);  // the engine that ran phase 2, before it goes
         else if (postsolve_) attach_postsolve(*res.solution, resident ? eng.e : nullptr, engine_);
+        if (certificate_) no_certificate(res, "Optimal");
         return res;
     case SolutionStatus::Infeasible: throw EllPPanic("primal phase 2 should never be infeasible");
-    case SolutionStatus::Unbounded: res.kind = SolverResult::Unbounded; return res;
+    case SolutionStatus::Unbounded:
+        res.kind = SolverResult::Unbounded;
+        if (certificate_)
+            attach_certificate(res, phase_2.std_form, phase_2.point, resident ? eng.e : nullptr, engine_, ELLP_CERT_RAY_COLUMN, n_orig, nullptr,
+                               "primal phase 2 unbounded");
+        return res;
     case SolutionStatus::MaxIter:
         res.kind = SolverResult::MaxIter;
         res.max_iter_obj = phase_2.obj();
+        if (certificate_) no_certificate(res, "MaxIter");
         return res;
     }
     return res;
@@ -412,7 +504,11 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
     // ELLP_HOST_DUAL_POINT=1 (diagnostics): the starting point of phase 1 is made on the host, as the reference makes it
     const char *hostpt = std::getenv("ELLP_HOST_DUAL_POINT");
     auto p1 = DualPhase1::from_problem(std::move(prob), /*defer_point=*/!(hostpt && hostpt[0] == '1'));
-    if (!p1) { res.kind = SolverResult::Infeasible; return res; }
+    if (!p1) {
+        res.kind = SolverResult::Infeasible;
+        if (certificate_) no_certificate(res, "infeasibility decided by the set-up");
+        return res;
+    }
     DualPhase1 phase_1 = std::move(*p1);
     const StandardForm &sf1 = phase_1.std_form;
     const bool deferred = phase_1.point_deferred;  // rows > 128, N not empty: the device makes y, d, x (:162-214)
@@ -452,7 +548,7 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
         if (!(obj < EPS)) throw EllPPanic("assertion failed: obj < EPS");
         if (!(obj > -EPS)) {
             // dual infeasible: classify with the primal solver, default max_iter (dual…:51-66)
-            SolverResult r = PrimalSimplexSolver().with_engine(engine_).solve(std::move(orig_for_fallback));
+            SolverResult r = PrimalSimplexSolver().with_engine(engine_).with_certificate(certificate_).solve(std::move(orig_for_fallback));
             if (r.kind == SolverResult::Optimal)
                 throw EllPPanic("assertion failed: matches!(result, Infeasible | Unbounded | MaxIter)");
             return r;
@@ -464,6 +560,7 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
     case SolutionStatus::MaxIter:
         res.kind = SolverResult::MaxIter;
         res.max_iter_obj = std::numeric_limits<double>::infinity();
+        if (certificate_) no_certificate(res, "MaxIter");
         return res;
     }
     DualPhase2 phase_2;
@@ -510,12 +607,19 @@ SolverResult DualSimplexSolver::solve(Problem prob) const {
         res.solution = Solution{std::move(phase_2.std_form), std::move(phase_2.point.point), std::nullopt, std::nullopt};
         if (ranging_) attach_ranging(*res.solution, eng.e, engine_);  // eng.e: set only where it ran phase 2
         else if (postsolve_) attach_postsolve(*res.solution, eng.e, engine_);
+        if (certificate_) no_certificate(res, "Optimal");
         return res;
-    case SolutionStatus::Infeasible: res.kind = SolverResult::Infeasible; return res;
+    case SolutionStatus::Infeasible:
+        res.kind = SolverResult::Infeasible;
+        if (certificate_)
+            attach_certificate(res, phase_2.std_form, phase_2.point.point, eng.e, engine_, ELLP_CERT_FARKAS_ROW, phase_2.std_form.cols(), nullptr,
+                               "dual phase 2 infeasible");
+        return res;
     case SolutionStatus::Unbounded: throw EllPPanic("dual phase 2 should never return unbounded");
     case SolutionStatus::MaxIter:
         res.kind = SolverResult::MaxIter;
         res.max_iter_obj = phase_2.obj();
+        if (certificate_) no_certificate(res, "MaxIter");
         return res;
     }
     return res;
@@ -625,7 +729,7 @@ void end_from_start(int kind, SolutionStatus s2, StandardForm &sf, DualFeasibleP
 // (plain: the seam's call for a problem without nonbasic columns, as in solve())
 template <class Plain>
 SolverResult run_from_start(int kind, StandardForm sf, DualFeasiblePoint dp, std::uint64_t max_iter, const EngineOptions &engine,
-                            bool postsolve, bool ranging, Plain &&plain) {
+                            bool postsolve, bool ranging, bool certificate, Plain &&plain) {
     SolverResult res;
     EngineHandle eng;
     SolutionStatus s2;
@@ -644,7 +748,15 @@ SolverResult run_from_start(int kind, StandardForm sf, DualFeasiblePoint dp, std
     } else {
         s2 = plain(sf, dp, &res.iters_phase2);
     }
+    const bool ending = (kind == ELLP_ENGINE_PRIMAL && s2 == SolutionStatus::Unbounded) || (kind == ELLP_ENGINE_DUAL && s2 == SolutionStatus::Infeasible);
+    if (certificate && ending) {  // before end_from_start: sf and the point are still here
+        res.kind = kind == ELLP_ENGINE_PRIMAL ? SolverResult::Unbounded : SolverResult::Infeasible;
+        attach_certificate(res, sf, dp.point, eng.e, engine, kind == ELLP_ENGINE_PRIMAL ? ELLP_CERT_RAY_COLUMN : ELLP_CERT_FARKAS_ROW, sf.cols(), nullptr,
+                           kind == ELLP_ENGINE_PRIMAL ? "primal phase 2 unbounded" : "dual phase 2 infeasible");
+        return res;
+    }
     end_from_start(kind, s2, sf, dp, res);
+    if (certificate) no_certificate(res, res.kind == SolverResult::Optimal ? "Optimal" : "MaxIter");
     if (res.kind != SolverResult::Optimal || !res.solution) return res;
     if (ranging) attach_ranging(*res.solution, eng.e, engine);
     else if (postsolve) attach_postsolve(*res.solution, eng.e, engine);
@@ -652,13 +764,13 @@ SolverResult run_from_start(int kind, StandardForm sf, DualFeasiblePoint dp, std
 }
 
 SolverResult primal_from_point(const PrimalSimplexSolver &single, StandardForm sf, DualFeasiblePoint dp, std::uint64_t max_iter,
-                               const EngineOptions &engine, bool postsolve, bool ranging) {
-    return run_from_start(ELLP_ENGINE_PRIMAL, std::move(sf), std::move(dp), max_iter, engine, postsolve, ranging,
+                               const EngineOptions &engine, bool postsolve, bool ranging, bool certificate = false) {
+    return run_from_start(ELLP_ENGINE_PRIMAL, std::move(sf), std::move(dp), max_iter, engine, postsolve, ranging, certificate,
                           [&single](const StandardForm &f, DualFeasiblePoint &p, std::uint64_t *it) { return single.solve_with_initial(f, p.point, it); });
 }
 SolverResult dual_from_point(const DualSimplexSolver &single, StandardForm sf, DualFeasiblePoint dp, std::uint64_t max_iter,
-                             const EngineOptions &engine, bool postsolve, bool ranging) {
-    return run_from_start(ELLP_ENGINE_DUAL, std::move(sf), std::move(dp), max_iter, engine, postsolve, ranging,
+                             const EngineOptions &engine, bool postsolve, bool ranging, bool certificate = false) {
+    return run_from_start(ELLP_ENGINE_DUAL, std::move(sf), std::move(dp), max_iter, engine, postsolve, ranging, certificate,
                           [&single](const StandardForm &f, DualFeasiblePoint &p, std::uint64_t *it) { return single.solve_with_initial(f, p, it); });
 }
 
@@ -672,13 +784,14 @@ SolverResult PrimalSimplexSolver::solve_from(Problem prob, const StartBasis &sta
     if (!sfo) {  // as solve()
         SolverResult res;
         res.kind = SolverResult::Infeasible;
+        if (certificate_) no_certificate(res, "infeasibility decided by the set-up");
         return res;
     }
     DualFeasiblePoint dp;
     rep.reason = start_point(*sfo, start, ELLP_START_KEEP_LABELS, engine_, dp, rep.info);
     if (rep.reason != START_USED) return solve(std::move(prob));
     rep.used = true;
-    return primal_from_point(*this, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_);
+    return primal_from_point(*this, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_, certificate_);
 }
 
 SolverResult DualSimplexSolver::solve_from(Problem prob, const StartBasis &start, StartReport *report) const {
@@ -689,13 +802,14 @@ SolverResult DualSimplexSolver::solve_from(Problem prob, const StartBasis &start
     if (!sfo) {
         SolverResult res;
         res.kind = SolverResult::Infeasible;
+        if (certificate_) no_certificate(res, "infeasibility decided by the set-up");
         return res;
     }
     DualFeasiblePoint dp;
     rep.reason = start_point(*sfo, start, ELLP_START_LABELS_BY_D, engine_, dp, rep.info);
     if (rep.reason != START_USED) return solve(std::move(prob));
     rep.used = true;
-    return dual_from_point(*this, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_);
+    return dual_from_point(*this, std::move(*sfo), std::move(dp), max_iter_, engine_, postsolve_, ranging_, certificate_);
 }
 
 }  // namespace ellp

@@ -805,6 +805,81 @@ ellp_status ellp_engine_tableau_rows(ellp_engine *e, const int64_t *positions, i
                                      double *rho /* k x m */, char *errbuf, size_t errbuf_len);
 
 /*
+ * Certificates: a Farkas vector for an infeasible LP, a ray for an unbounded one, each with a report of
+ * how good a proof it is.  Standard form: A x = b (m x n), bounds (kind, lb, ub) per variable, minimise c . x.
+ *
+ * Farkas vector y in R^m, z = A^T y.  For variable j: sup_j = z_j ub_j if z_j > 0, z_j lb_j if z_j < 0, 0 if z_j == 0; where
+ * the bound needed is infinite (kind Free, Lower with z_j > 0, Upper with z_j < 0) j contributes 0 to the sum and |z_j| to
+ * dir_violation (a NaN-propagating maximum, worst_dir_var its first index).  gap = y . b - sum_j sup_j.  Every feasible x
+ * has y . b = sum z_j x_j <= sum sup_j, so gap > 0 with dir_violation == 0 proves infeasibility; a positive dir_violation
+ * says how far the proof leans on a tolerance.
+ *
+ * Ray r in R^n: residual = max_i |(A r)_i|, c_r = c . r, bound_dir_violation = max |r_j| over the j with r_j > 0 and a finite
+ * upper bound or r_j < 0 and a finite lower bound (Fixed counts on both sides).  c_r < 0 with the other two zero proves
+ * unboundedness from any feasible point.
+ *
+ * The certificate is a function of (the arrays, the basis, the labels) only: every source starts from the postsolve's fresh
+ * LU of A_B in a workspace of its own, nothing is read from what a loop carried.
+ *   ELLP_CERT_FARKAS_COSTS  y = B^-T c_B of the engine's costs, the postsolve's refined y unchanged (the proof a primal
+ *                           phase-1 optimum with a positive objective carries: its costs are zero on the problem's columns).
+ *   ELLP_CERT_FARKAS_ROW    x_B is recomputed as ellp_basis_start(ELLP_START_KEEP_LABELS) makes it; basic position r
+ *                           qualifies when the dual loop's leaving rule finds its variable outside a bound by more than eps
+ *                           and no nonbasic column passes the dual ratio test's filter for that side (the condition under
+ *                           which the dual simplex answers Infeasible); the smallest such r; y = -+B^-T e_r, refined as the
+ *                           postsolve refines y, the sign such that gap is the violation.
+ *   ELLP_CERT_RAY_COLUMN    d from the postsolve; nonbasic position q qualifies when it is a primal entering candidate
+ *                           (|d| >= eps with the sign its label asks for), its own kind is Free, Lower or Upper, and no basic
+ *                           row bounds the step (the primal ratio test gives +inf in every row, at the point the engine
+ *                           stands on); the smallest such q; r_q = +-1 (up from a Lower label, down from an Upper one, a Free
+ *                           one against the sign of d), r_B = -+B^-1 a_q refined to a componentwise backward error <= 2u.
+ * The searches read the whole tableau B^-1 A_N once on the matrix cores (the ranging's pass with another epilogue; alpha_ij has
+ * the bits ellp_engine_tableau_rows returns); every decision is a boolean OR or an integer minimum, so no result depends on a
+ * reduction order.  The report comes from the postsolve's compensated pass (z = A^T y, A r) and compensated sums in a fixed
+ * order: two calls give the same bits.
+ *
+ * n_check in [1, n]: only columns 0 .. n_check - 1 take part in the report (a ray is returned on these, other entries
+ * dropped); chk_kind / chk_lb / chk_ub (n_check each, or all three NULL: the engine's own bounds) are the bounds the report is
+ * made against.  vec: m doubles for a Farkas source, n_check for the ray.
+ * ELLP_OPTIMAL: info is filled; found == 0 leaves vec untouched.  ELLP_ERR_SINGULAR, ELLP_ERR_NAN (a NaN in the tableau, in d
+ * or in x where a decision reads it): vec and info untouched.  ELLP_ERR_ARG before any HIP call: the refusals of
+ * ellp_engine_postsolve / ellp_postsolve, an unknown source, n_check outside [1, n], vec or info NULL, some but not all of
+ * chk_* NULL, a chk_kind out of range.  The engine's state is not touched (an open iteration of the two-launch pipeline is
+ * completed first, as the postsolve does); the workspace is released by ellp_engine_destroy.
+ */
+enum { ELLP_CERT_FARKAS_COSTS = 0, ELLP_CERT_FARKAS_ROW = 1, ELLP_CERT_RAY_COLUMN = 2 };
+enum { ELLP_CERT_KIND_NONE = 0, ELLP_CERT_KIND_FARKAS = 1, ELLP_CERT_KIND_RAY = 2 };
+typedef struct ellp_cert_info {
+    int32_t kind;               /* ELLP_CERT_KIND_*: what the source makes (FARKAS or RAY, also when found == 0) */
+    int32_t found;
+    int64_t source;             /* the row position r or the nonbasic position q the vector came from; -1: none, or the
+                                   cost-based Farkas vector */
+    int64_t qualifying;         /* how many rows or columns qualified (0 for ELLP_CERT_FARKAS_COSTS) */
+    double gap, y_b, sup;       /* Farkas: y . b - sum sup_j, and its two parts; each a compensated sum rounded once */
+    double dir_violation;       /* Farkas */
+    double residual, c_r;       /* ray */
+    double bound_dir_violation; /* ray */
+    double norm;                /* max |entry| of the vector */
+    int64_t worst_dir_var, worst_row, worst_bound_var; /* where the three maxima sit; -1: the maximum is 0 */
+    int32_t refine_steps;       /* refinement steps of the vector's own solve */
+    int32_t reserved;
+} ellp_cert_info;
+
+ellp_status ellp_engine_certificate(ellp_engine *e, int source, int64_t n_check, const uint8_t *chk_kind, const double *chk_lb,
+                                    const double *chk_ub, double *vec, ellp_cert_info *info, char *errbuf, size_t errbuf_len);
+/* The same for a point in host memory, with the argument list of ellp_postsolve: the checks before any HIP call, a minimal
+ * engine, the same kernels and the same bits. */
+ellp_status ellp_certificate(int64_t m, int64_t n, int64_t n_c, const double *A, const double *c, const double *b,
+                             const uint8_t *bound_kind, const double *lb, const double *ub, const double *x,
+                             const int64_t *B_index, int64_t n_B, const int64_t *N_index, const uint8_t *N_bound, int64_t n_N,
+                             const ellp_opts *opts, int source, int64_t n_check, const uint8_t *chk_kind, const double *chk_lb,
+                             const double *chk_ub, double *vec, ellp_cert_info *info, char *errbuf, size_t errbuf_len);
+/* The process's certificate calls: out4[0] calls of the two entry points so far (refused ones included), out4[1] kernels
+ * the last call enqueued — its own stages, every compensated pass and fold and the solves of x_B, each counted where it is
+ * launched; the LU, the triangular solves of y and B^-1 are not counted; independent of n, of m only through the refinement
+ * steps — out4[2] the refinement steps of its vector, out4[3] 0.  Not thread safe. */
+void ellp_certificate_info(uint64_t *out4);
+
+/*
  * SURVEY.md §8 f3 — the rank check of the standard form on the device: column-pivoted Householder
  * QR of A^T (src/standard_form.rs:142 `A.transpose().col_piv_qr()`), reduced to what :143-181
  * consume.  A: m x nv column-major (ld = m) in HOST memory, not modified.  pivot_out[i] = the

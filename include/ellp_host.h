@@ -122,6 +122,22 @@ typedef struct ellp_start { int64_t n_B; const int64_t *B_index; int64_t n_N; co
 typedef struct ellp_start_report { int used; int reason; ellp_start_info info; } ellp_start_report;
 int ellp_solve_start(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, unsigned flags,
                      const ellp_start *start, ellp_result_rng *out, ellp_start_report *report);
+/* Certificates: ellp_solve_flags / ellp_solve_start (start may be NULL: no warm start) with one more flag,
+ * ELLP_SOLVE_CERTIFICATE, which only this entry point accepts.  With the flag an Infeasible result of primal phase 1 (an
+ * optimum with a positive objective) or of dual phase 2 carries a Farkas vector — vec: one entry per constraint of the
+ * problem, with the sign convention of the duals (<= 0 on a `<=` row, >= 0 on a `>=` row, 0.0 on a row the rank check
+ * dropped) — and an Unbounded result of primal phase 2 a ray — vec: one entry per variable of the problem; info is the
+ * device's report (ellp_cert_info, include/ellp_hip.h) on the standard form the vector was made on.  Every other ending has
+ * kind ELLP_CERT_KIND_NONE and a reason: infeasibility decided by the set-up, no rows, a loop status of primal phase 1,
+ * MaxIter, Optimal, search found none, or a certificate call that met a NaN or a singular basis.  Without the flag the call
+ * is exactly ellp_solve_flags / ellp_solve_start (not one extra device call) and *cert is zeroed.  ELLP_ERR_ARG: p, out or
+ * cert NULL, an unknown solver or flag.  report may be NULL.  Free out with ellp_result_rng_free, cert with
+ * ellp_result_cert_free. */
+#define ELLP_SOLVE_CERTIFICATE 4u
+typedef struct ellp_result_cert { int kind; char reason[128]; int64_t n; double *vec; ellp_cert_info info; } ellp_result_cert;
+int ellp_solve_cert(const ellp_problem *p, int solver, uint64_t max_iter, const ellp_opts *opts, unsigned flags,
+                    const ellp_start *start, ellp_result_rng *out, ellp_start_report *report, ellp_result_cert *cert);
+void ellp_result_cert_free(ellp_result_cert *c);
 /* Test/diagnostic tap, host only: the start as ellp_solve_start maps it into the standard form.  *rows, *cols: the standard
  * form's; B_out (rows), N_out / Nb_out (cols - rows) when the return is 0; capacity: what the arrays hold, at least *cols.
  * Returns 0, a reason (1, 2, 5) or a negative ellp_status. */
