@@ -550,6 +550,27 @@ class BatchItem(C.Structure):
                 ("n_N", C.c_int64), ("y", C.c_void_p), ("d", C.c_void_p), ("err", C.c_char * 256)]
 
 
+def _fill_item(it, fp, *, x=None, Nb=None, y=None, d=None):
+    """A BatchItem from a FlatProblem; x, Nb, y, d: the caller's arrays where the call writes into its own (fp's x and Nb
+    otherwise; y and d stay NULL where none is given)."""
+    it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
+    it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
+    it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(fp.x if x is None else x)
+    it.B_index, it.n_B = _p(fp.B), fp.nB
+    it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(fp.Nb if Nb is None else Nb), fp.nN
+    it.y, it.d = _p(y), _p(d)
+
+
+def _info4(fn, names):
+    """The four counters a batched call keeps per thread, under the given names."""
+    out = (C.c_uint64 * 4)()
+    fn(out)
+    return {name: int(v) for name, v in zip(names, out)}
+
+
+_BATCH_INFO = ("launches", "batched", "single", "chunks")
+
+
 def batch_solve_with_initial(kind, flat_problems, opts=None):
     """solve_with_initial of every FlatProblem in one batched call (ENGINE_PRIMAL or ENGINE_DUAL).  Returns one
     (status, Stats, errmsg) per problem, as the single-call wrappers do, and mutates the problems in place.  Raises
@@ -558,12 +579,7 @@ def batch_solve_with_initial(kind, flat_problems, opts=None):
     n = len(fps)
     items = (BatchItem * max(n, 1))()
     for it, fp in zip(items, fps):
-        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
-        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
-        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
-        it.B_index, it.n_B = _p(fp.B), fp.nB
-        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(fp.Nb), fp.nN
-        it.y, it.d = _p(fp.y), _p(fp.d)
+        _fill_item(it, fp, y=fp.y, d=fp.d)
     status = (C.c_int * max(n, 1))()
     stats = (Stats * max(n, 1))()
     o = opts or default_opts()
@@ -577,9 +593,7 @@ def batch_solve_with_initial(kind, flat_problems, opts=None):
 def batch_solve_info():
     """ellp_batch_solve_info: the calling thread's calls of ellp_batch_solve_with_initial: how many so far, the items and the
     kind of the last one."""
-    out = (C.c_uint64 * 4)()
-    lib().ellp_batch_solve_info(out)
-    return {"calls": int(out[0]), "items": int(out[1]), "kind": int(out[2])}
+    return _info4(lib().ellp_batch_solve_info, ("calls", "items", "kind"))
 
 
 class BatchPostOut(C.Structure):
@@ -599,11 +613,7 @@ def batch_postsolve(flat_problems, opts=None, fill=0.0):
     kkts = (Kkt * max(n, 1))()
     arrays = []
     for k, (it, fp) in enumerate(zip(items, fps)):
-        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
-        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
-        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
-        it.B_index, it.n_B = _p(fp.B), fp.nB
-        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(fp.Nb), fp.nN
+        _fill_item(it, fp)
         y, d, r = np.full(max(fp.m, 0), fill), np.full(max(fp.n_c, 0), fill), np.full(max(fp.m, 0), fill)
         arrays.append((y, d, r))
         outs[k].y, outs[k].d, outs[k].r = y.ctypes.data, d.ctypes.data, r.ctypes.data
@@ -621,9 +631,7 @@ def batch_postsolve(flat_problems, opts=None, fill=0.0):
 def batch_postsolve_info():
     """ellp_batch_postsolve_info: the calling thread's last ellp_batch_postsolve: kernel launches of the batched path, items
     on the batched kernel, items on the single path (inside the call), chunks."""
-    out = (C.c_uint64 * 4)()
-    lib().ellp_batch_postsolve_info(out)
-    return {"launches": int(out[0]), "batched": int(out[1]), "single": int(out[2]), "chunks": int(out[3])}
+    return _info4(lib().ellp_batch_postsolve_info, _BATCH_INFO)
 
 
 class BatchRangeOut(C.Structure):
@@ -650,11 +658,7 @@ def _batch_ranging_raw(flat_problems, opts=None, want_W=False, fill=0.0, wanted=
     outs = (BatchRangeOut * max(n, 1))()
     keep = []
     for k, (it, fp) in enumerate(zip(items, fps)):
-        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
-        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
-        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
-        it.B_index, it.n_B = _p(fp.B), fp.nB
-        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(fp.Nb), fp.nN
+        _fill_item(it, fp)
         rg = Ranging(max(fp.m, 0), max(fp.n_c, 0))
         for name in Ranging.ARRAYS:
             a = getattr(rg, name)
@@ -685,9 +689,7 @@ def batch_ranging_info():
     """ellp_batch_ranging_info: the calling thread's last ellp_batch_ranging: kernel launches of the batched path (5 per
     chunk, whatever the item count and the items' shapes: k_brange_front, k_brange_solve, k_brange_tab, k_brange_fold,
     k_post_report_batch), items on the batched kernels, items on the single path (inside the call), chunks."""
-    out = (C.c_uint64 * 4)()
-    lib().ellp_batch_ranging_info(out)
-    return {"launches": int(out[0]), "batched": int(out[1]), "single": int(out[2]), "chunks": int(out[3])}
+    return _info4(lib().ellp_batch_ranging_info, _BATCH_INFO)
 
 
 def batch_basis_start(flat_problems, mode=START_KEEP_LABELS, opts=None, fill=0.0):
@@ -705,12 +707,7 @@ def batch_basis_start(flat_problems, mode=START_KEEP_LABELS, opts=None, fill=0.0
         x, y, d = np.full(max(fp.n, 0), fill), np.full(max(fp.m, 0), fill), np.full(max(fp.n, 0), fill)
         Nb = fp.Nb.copy()
         arrays.append((x, y, d, Nb))
-        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
-        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
-        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(x)
-        it.B_index, it.n_B = _p(fp.B), fp.nB
-        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(Nb), fp.nN
-        it.y, it.d = _p(y), _p(d)
+        _fill_item(it, fp, x=x, Nb=Nb, y=y, d=d)
     status = (C.c_int * max(n, 1))()
     o = opts or default_opts()
     err = C.create_string_buffer(512)
@@ -731,9 +728,7 @@ def batch_basis_start(flat_problems, mode=START_KEEP_LABELS, opts=None, fill=0.0
 def batch_basis_start_info():
     """ellp_batch_basis_start_info: the calling thread's last ellp_batch_basis_start: kernel launches of the batched path,
     items on the batched kernel, items on the single path (inside the call), chunks."""
-    out = (C.c_uint64 * 4)()
-    lib().ellp_batch_basis_start_info(out)
-    return {"launches": int(out[0]), "batched": int(out[1]), "single": int(out[2]), "chunks": int(out[3])}
+    return _info4(lib().ellp_batch_basis_start_info, _BATCH_INFO)
 
 
 class BatchPrimalItem(C.Structure):
@@ -760,12 +755,7 @@ def batch_primal_solve(items, opts=None):
         c2, lb2, ub2 = _f64(c2), _f64(lb2), _f64(ub2)
         kind2 = np.ascontiguousarray(kind2, dtype=np.uint8)
         keep.append((c2, kind2, lb2, ub2))
-        b = it.p1
-        b.m, b.n, b.n_c = fp.m, fp.n, fp.n_c
-        b.A, b.c, b.b, b.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
-        b.lb, b.ub, b.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
-        b.B_index, b.n_B = _p(fp.B), fp.nB
-        b.N_index, b.N_bound, b.n_N = _p(fp.N), _p(fp.Nb), fp.nN
+        _fill_item(it.p1, fp)
         it.c2, it.bound_kind2, it.lb2, it.ub2 = _p(c2), _p(kind2), _p(lb2), _p(ub2)
     res = (BatchPrimalResult * max(n, 1))()
     o = opts or default_opts()
@@ -780,9 +770,7 @@ def batch_primal_solve(items, opts=None):
 def batch_primal_info():
     """ellp_batch_primal_info: the calling thread's last ellp_batch_primal_solve (solve_batch of the primal solver makes one
     per batch): launch rounds, bytes uploaded by the last chunk and by all chunks, chunks."""
-    out = (C.c_uint64 * 4)()
-    lib().ellp_batch_primal_info(out)
-    return {"rounds": int(out[0]), "upload_bytes": int(out[1]), "upload_bytes_total": int(out[2]), "chunks": int(out[3])}
+    return _info4(lib().ellp_batch_primal_info, ("rounds", "upload_bytes", "upload_bytes_total", "chunks"))
 
 
 def batch_dual_phase1_start(problems, opts=None):
@@ -797,12 +785,7 @@ def batch_dual_phase1_start(problems, opts=None):
     k = len(fps)
     items = (BatchItem * max(k, 1))()
     for it, fp in zip(items, fps):
-        it.m, it.n, it.n_c = fp.m, fp.n, fp.n_c
-        it.A, it.c, it.b, it.bound_kind = _p(fp.A), _p(fp.c), _p(fp.b), _p(fp.kind)
-        it.lb, it.ub, it.x = _p(fp.lb), _p(fp.ub), _p(fp.x)
-        it.B_index, it.n_B = _p(fp.B), fp.nB
-        it.N_index, it.N_bound, it.n_N = _p(fp.N), _p(fp.Nb), fp.nN
-        it.y, it.d = _p(fp.y), _p(fp.d)
+        _fill_item(it, fp, y=fp.y, d=fp.d)
     status = (C.c_int * max(k, 1))()
     obj = (C.c_double * max(k, 1))()
     o = opts or default_opts()

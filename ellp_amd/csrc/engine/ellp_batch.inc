@@ -12,7 +12,8 @@
 // every round one k_mid_transpose_batch launch makes the row-major copy A_Nt of every mid item, as launch_mid does.
 //
 // Chunks: the items are taken in consecutive chunks whose slab stays within a budget (2 GiB; ELLP_BATCH_MAX_BYTES lowers it)
-// and at most 65,535 items; a chunk is a batch of its own, so chunking changes no item's bits.
+// and at most 65,535 items; a chunk is a batch of its own, so chunking changes no item's bits.  The driver below
+// (batch_budget, SlabCursor, batch_cuts, batch_open, batch_drive) states that once for every batched call; DESIGN.md §3.1f.
 //
 // Layout of the slab: [DevState x runnable items][outputs of each item: x, B_index, N_index, Nb (y, d)] | [inputs and
 // scratch of each item: A_B, A_N, c_B, c_N, lb, ub, kind, rbuf, kbuf (flist)][SmallArgs of all items][MidArgs of the mid
@@ -132,6 +133,128 @@ struct BatchCleanup {
 
 size_t batch_round16(size_t b) { return (b + 15) / 16 * 16; }
 
+// ---- the driver of every batched call (this file, ellp_bpost.inc, ellp_bstart.inc, ellp_brange.inc): the budget, the slab
+// cursor of a layout, the chunk cuts, the device and its buffers, the loop over the chunks.  DESIGN.md §3.1f.
+
+// slab bytes per chunk (the staging buffer is a part of it): 2 GiB; ELLP_BATCH_MAX_BYTES only lowers it
+size_t batch_budget() {
+    size_t budget = (size_t)2 << 30;
+    if (const char *v = getenv("ELLP_BATCH_MAX_BYTES"); v && v[0] && atoll(v) > 0 && (size_t)atoll(v) < budget) budget = (size_t)atoll(v);
+    return budget;
+}
+
+// the array at byte offset `off` of the staging buffer or the slab
+template <class T>
+T *slab_at(unsigned char *base, size_t off) {
+    return reinterpret_cast<T *>(base + off);
+}
+
+// The bump allocator of a layout function: arrays in steps of 16 bytes, in the order they are taken.  What is taken while
+// `bytes` points at a plan's share counts towards that share; nullptr: a shared array, counted in the shares up front
+struct SlabCursor {
+    size_t off = 0;
+    size_t *bytes = nullptr;
+    size_t take(size_t b) {
+        const size_t o = off;
+        off += batch_round16(b);
+        if (bytes) *bytes += batch_round16(b);
+        return o;
+    }
+};
+
+// chunks: consecutive items within the budget (an item alone over it is a chunk of its own) and at most 65,535 items;
+// plan[k].bytes is item k's share, slack what the rounding of a chunk's shared arrays may add
+template <class Plan>
+std::vector<size_t> batch_cuts(const std::vector<Plan> &plan, size_t budget, size_t slack) {
+    std::vector<size_t> cut{0};
+    size_t acc = slack;
+    for (size_t k = 0; k < plan.size(); ++k) {
+        if (k > cut.back() && (acc + plan[k].bytes > budget || k - cut.back() >= 65535)) {
+            cut.push_back(k);
+            acc = slack;
+        }
+        acc += plan[k].bytes;
+    }
+    cut.push_back(plan.size());
+    return cut;
+}
+
+// the device of the call, its host set, a pinned staging buffer and a slab of the sizes the largest chunk needs
+ellp_status batch_open(const ellp_opts *opts_in, size_t max_stage, size_t max_total, BatchCleanup &cl, char *errbuf, size_t errlen) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_err(errbuf, errlen, "no HIP device available (this library has no CPU path)");
+        return ELLP_ERR_DEVICE;
+    }
+    int dev = opts_in ? opts_in->device : -1;  // -1, the default: the current device
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+    HIPCHK(hipSetDevice(dev));
+    HIPCHK(host_set_acquire(dev, &cl.hs));
+    HIPCHK(batch_buf_acquire(dev, true, max_stage, &cl.stage));
+    HIPCHK(batch_buf_acquire(dev, false, max_total, &cl.slab));
+    return ELLP_OPTIMAL;
+}
+
+// The planned items of a call, chunk by chunk.  layout(plan, R) lays R consecutive plans out (offsets, each share in
+// Plan::bytes; its result has stage_bytes and total), run_chunk(plan, R, cl) runs them start to end; *chunks counts the
+// chunks that ran.  A chunk that does not return ELLP_OPTIMAL ends the call with that status, which every planned item from
+// that chunk on and every item of `single` (the caller's single-path items, not run yet) then carries; the call's other
+// results are unspecified (ellp_hip.h).  A failure before the first chunk (no device, no buffer) marks no item.  The host
+// set, the stage and the slab are held for the chunks only: they are back in their pools, and the stream has drained, when
+// the caller's single-path items run (a single call may take the same host set).
+template <class Plan, class Layout, class RunChunk>
+ellp_status batch_drive(std::vector<Plan> &plan, const std::vector<int64_t> &single, size_t slack, const ellp_opts *opts_in,
+                        ellp_status *status_out, uint64_t *chunks, Layout layout, RunChunk run_chunk, char *errbuf, size_t errlen) {
+    (void)layout(plan.data(), plan.size());  // every item's share of a slab
+    const std::vector<size_t> cut = batch_cuts(plan, batch_budget(), slack);
+    size_t max_stage = 0, max_total = 0;
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        const auto L = layout(plan.data() + cut[c], cut[c + 1] - cut[c]);
+        max_stage = L.stage_bytes > max_stage ? L.stage_bytes : max_stage;
+        max_total = L.total > max_total ? L.total : max_total;
+    }
+    BatchCleanup cl;
+    if (const ellp_status s = batch_open(opts_in, max_stage, max_total, cl, errbuf, errlen); s != ELLP_OPTIMAL) return s;
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        const ellp_status rc = run_chunk(plan.data() + cut[c], cut[c + 1] - cut[c], cl);
+        if (rc != ELLP_OPTIMAL) {
+            for (size_t k = cut[c]; k < plan.size(); ++k) status_out[plan[k].item] = rc;
+            for (int64_t i : single) status_out[i] = rc;
+            return rc;
+        }
+        if (chunks) *chunks += 1;
+    }
+    return ELLP_OPTIMAL;
+}
+
+// A_B, A_N, c_B and c_N of an item gathered into the staging buffer h (copies, so exact): columns of ld >= m doubles, zero
+// beyond row m; an item without a nonbasic column gets one zero column
+inline void batch_stage_basis(unsigned char *h, const ellp_batch_item &it, int64_t ld, size_t o_AB, size_t o_AN, size_t o_cB, size_t o_cN) {
+    const int64_t m = it.m, nN = it.n_N;
+    double *AB = slab_at<double>(h, o_AB), *AN = slab_at<double>(h, o_AN), *cB = slab_at<double>(h, o_cB), *cN = slab_at<double>(h, o_cN);
+    for (int64_t j = 0; j < m; ++j) {
+        memcpy(AB + j * ld, it.A + it.B_index[j] * m, sizeof(double) * (size_t)m);
+        memset(AB + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
+        cB[j] = it.c[it.B_index[j]];
+    }
+    if (nN == 0) memset(AN, 0, sizeof(double) * (size_t)ld);
+    for (int64_t j = 0; j < nN; ++j) {
+        memcpy(AN + j * ld, it.A + it.N_index[j] * m, sizeof(double) * (size_t)m);
+        memset(AN + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
+        cN[j] = it.c[it.N_index[j]];
+    }
+}
+
+// the fail flag an item's kernel raised on a zero on U's diagonal, read back: the single call's status and message
+inline bool batch_item_singular(const unsigned char *h, size_t o_fail, ellp_batch_item &it, ellp_status *status) {
+    int fail = 0;
+    memcpy(&fail, h + o_fail, sizeof(int));
+    if (!fail) return false;
+    set_err(it.err, sizeof(it.err), "invalid B, A_B is not invertible");
+    *status = ELLP_ERR_SINGULAR;
+    return true;
+}
+
 // Per-chunk rounding of the four argument arrays, at most (the chunk budget allows for it)
 constexpr size_t BATCH_CHUNK_SLACK = 4 * 16;
 // ... and of the records and the two BatchPhaseArgs arrays of a whole primal solve
@@ -152,71 +275,65 @@ struct BatchLayout {
 };
 BatchLayout batch_layout(int kind, const ellp_batch_item *items, BatchPlan *plan, size_t R, bool bflip, bool two = false) {
     BatchLayout L{};
-    size_t off = sizeof(DevState) * R;
-    BatchPlan *owner = nullptr;  // the item the next takes belong to
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += batch_round16(bytes);
-        if (owner) owner->bytes += batch_round16(bytes);
-        return o;
-    };
-    if (two) L.o_rec = take(sizeof(BatchPhaseRec) * R);
+    SlabCursor cur;
+    cur.off = sizeof(DevState) * R;
+    if (two) L.o_rec = cur.take(sizeof(BatchPhaseRec) * R);
     size_t nmid = 0;
     for (size_t k = 0; k < R; ++k) {
         BatchPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
-        owner = &p;
+        cur.bytes = &p.bytes;
         p.bytes = sizeof(DevState) + 2 * sizeof(SmallArgs) + (p.mid ? 2 * sizeof(MidArgs) : 0);
         if (two) p.bytes += sizeof(BatchPhaseRec) + 2 * sizeof(BatchPhaseArgs);
-        p.o_x = take(sizeof(double) * (size_t)it.n_c);
-        p.o_B = take(sizeof(int64_t) * (size_t)it.m);
-        p.o_N = take(sizeof(int64_t) * (size_t)p.nNa);
-        p.o_Nb = take((size_t)p.nNa);
-        p.o_y = kind == ELLP_ENGINE_DUAL ? take(sizeof(double) * (size_t)p.ld) : 0;
-        p.o_d = kind == ELLP_ENGINE_DUAL ? take(sizeof(double) * (size_t)it.n_c) : 0;
+        p.o_x = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_B = cur.take(sizeof(int64_t) * (size_t)it.m);
+        p.o_N = cur.take(sizeof(int64_t) * (size_t)p.nNa);
+        p.o_Nb = cur.take((size_t)p.nNa);
+        p.o_y = kind == ELLP_ENGINE_DUAL ? cur.take(sizeof(double) * (size_t)p.ld) : 0;
+        p.o_d = kind == ELLP_ENGINE_DUAL ? cur.take(sizeof(double) * (size_t)it.n_c) : 0;
         nmid += p.mid ? 1 : 0;
     }
-    L.out_bytes = off;
+    L.out_bytes = cur.off;
     for (size_t k = 0; k < R; ++k) {
         BatchPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
-        owner = &p;
-        p.o_AB = take(sizeof(double) * (size_t)(p.ld * it.m));
-        p.o_AN = take(sizeof(double) * (size_t)(p.ld * p.nNa));
-        p.o_cB = take(sizeof(double) * (size_t)it.m);
-        p.o_cN = take(sizeof(double) * (size_t)p.nNa);
-        p.o_lb = take(sizeof(double) * (size_t)it.n_c);
-        p.o_ub = take(sizeof(double) * (size_t)it.n_c);
-        p.o_kind = take((size_t)it.n_c);
+        cur.bytes = &p.bytes;
+        p.o_AB = cur.take(sizeof(double) * (size_t)(p.ld * it.m));
+        p.o_AN = cur.take(sizeof(double) * (size_t)(p.ld * p.nNa));
+        p.o_cB = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_cN = cur.take(sizeof(double) * (size_t)p.nNa);
+        p.o_lb = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_ub = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_kind = cur.take((size_t)it.n_c);
         // k_mid, like k_small, touches rbuf / kbuf at nonbasic positions j < |N| only, and flist up to |N| entries
-        p.o_rbuf = take(sizeof(double) * (size_t)p.nNa);
-        p.o_kbuf = take(sizeof(double) * (size_t)p.nNa);
-        p.o_fl = bflip ? take(sizeof(long long) * (size_t)(p.nNa + 1)) : 0;
+        p.o_rbuf = cur.take(sizeof(double) * (size_t)p.nNa);
+        p.o_kbuf = cur.take(sizeof(double) * (size_t)p.nNa);
+        p.o_fl = bflip ? cur.take(sizeof(long long) * (size_t)(p.nNa + 1)) : 0;
         if (two) {
-            p.o_c1 = take(sizeof(double) * (size_t)it.n_c);
-            p.o_c2 = take(sizeof(double) * (size_t)it.n_c);
-            p.o_lb2 = take(sizeof(double) * (size_t)it.n_c);
-            p.o_ub2 = take(sizeof(double) * (size_t)it.n_c);
-            p.o_kind2 = take((size_t)it.n_c);
+            p.o_c1 = cur.take(sizeof(double) * (size_t)it.n_c);
+            p.o_c2 = cur.take(sizeof(double) * (size_t)it.n_c);
+            p.o_lb2 = cur.take(sizeof(double) * (size_t)it.n_c);
+            p.o_ub2 = cur.take(sizeof(double) * (size_t)it.n_c);
+            p.o_kind2 = cur.take((size_t)it.n_c);
         }
     }
-    owner = nullptr;  // the argument arrays: shared, counted in the items' bytes above
-    L.o_sargs_all = take(sizeof(SmallArgs) * R);
-    L.o_margs_all = take(sizeof(MidArgs) * nmid);
-    if (two) L.o_pargs_all = take(sizeof(BatchPhaseArgs) * R);
-    L.o_sargs_run = take(sizeof(SmallArgs) * R);  // the round's argument lists are written per round
-    L.o_margs_run = take(sizeof(MidArgs) * nmid);
-    if (two) L.o_pargs_run = take(sizeof(BatchPhaseArgs) * R);
-    L.stage_bytes = off;
+    cur.bytes = nullptr;  // the argument arrays: shared, counted in the items' bytes above
+    L.o_sargs_all = cur.take(sizeof(SmallArgs) * R);
+    L.o_margs_all = cur.take(sizeof(MidArgs) * nmid);
+    if (two) L.o_pargs_all = cur.take(sizeof(BatchPhaseArgs) * R);
+    L.o_sargs_run = cur.take(sizeof(SmallArgs) * R);  // the round's argument lists are written per round
+    L.o_margs_run = cur.take(sizeof(MidArgs) * nmid);
+    if (two) L.o_pargs_run = cur.take(sizeof(BatchPhaseArgs) * R);
+    L.stage_bytes = cur.off;
     for (size_t k = 0; k < R; ++k) {
         BatchPlan &p = plan[k];
         if (!p.mid) continue;
-        owner = &p;
-        p.o_LUa = take(sizeof(double) * (size_t)(p.ld * p.ld));
-        p.o_Ut = take(sizeof(double) * (size_t)(p.ld * p.ld));
-        p.o_ANt = take(sizeof(double) * (size_t)(p.ld * p.ldn));
+        cur.bytes = &p.bytes;
+        p.o_LUa = cur.take(sizeof(double) * (size_t)(p.ld * p.ld));
+        p.o_Ut = cur.take(sizeof(double) * (size_t)(p.ld * p.ld));
+        p.o_ANt = cur.take(sizeof(double) * (size_t)(p.ld * p.ldn));
     }
-    L.total = off;
+    L.total = cur.off;
     return L;
 }
 
@@ -238,10 +355,10 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
 
     // ---- staging: the engine's starting arrays, gathered as ellp_engine_create gathers them on the device
     DevState *h_states = reinterpret_cast<DevState *>(h);
-    SmallArgs *h_all = reinterpret_cast<SmallArgs *>(h + L.o_sargs_all);
-    MidArgs *h_mall = reinterpret_cast<MidArgs *>(h + L.o_margs_all);
-    BatchPhaseRec *h_rec = two ? reinterpret_cast<BatchPhaseRec *>(h + L.o_rec) : nullptr;
-    BatchPhaseArgs *h_pall = two ? reinterpret_cast<BatchPhaseArgs *>(h + L.o_pargs_all) : nullptr;
+    SmallArgs *h_all = slab_at<SmallArgs>(h, L.o_sargs_all);
+    MidArgs *h_mall = slab_at<MidArgs>(h, L.o_margs_all);
+    BatchPhaseRec *h_rec = two ? slab_at<BatchPhaseRec>(h, L.o_rec) : nullptr;
+    BatchPhaseArgs *h_pall = two ? slab_at<BatchPhaseArgs>(h, L.o_pargs_all) : nullptr;
     std::vector<size_t> mid_at(R, 0);  // position of a mid item in the MidArgs lists
     size_t nmid = 0;
     for (size_t k = 0; k < R; ++k) {
@@ -260,38 +377,26 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
             memcpy(h + p.o_d, it.d, sizeof(double) * (size_t)it.n_c);
         }
         if (kind == ELLP_ENGINE_DUAL) memset(h + p.o_y + sizeof(double) * (size_t)m, 0, sizeof(double) * (size_t)(ld - m));
-        double *AB = reinterpret_cast<double *>(h + p.o_AB), *AN = reinterpret_cast<double *>(h + p.o_AN);
-        double *cB = reinterpret_cast<double *>(h + p.o_cB), *cN = reinterpret_cast<double *>(h + p.o_cN);
-        for (int64_t j = 0; j < m; ++j) {
-            memcpy(AB + j * ld, it.A + it.B_index[j] * m, sizeof(double) * (size_t)m);
-            memset(AB + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
-            cB[j] = it.c[it.B_index[j]];
-        }
-        if (nN == 0) memset(AN, 0, sizeof(double) * (size_t)ld);
-        for (int64_t j = 0; j < nN; ++j) {
-            memcpy(AN + j * ld, it.A + it.N_index[j] * m, sizeof(double) * (size_t)m);
-            memset(AN + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
-            cN[j] = it.c[it.N_index[j]];
-        }
+        batch_stage_basis(h, it, ld, p.o_AB, p.o_AN, p.o_cB, p.o_cN);
         memcpy(h + p.o_lb, it.lb, sizeof(double) * (size_t)it.n_c);
         memcpy(h + p.o_ub, it.ub, sizeof(double) * (size_t)it.n_c);
         memcpy(h + p.o_kind, it.bound_kind, (size_t)it.n_c);
         SmallArgs a{};
-        a.A_B = reinterpret_cast<double *>(dv + p.o_AB);
-        a.A_N = reinterpret_cast<double *>(dv + p.o_AN);
-        a.c_B = reinterpret_cast<double *>(dv + p.o_cB);
-        a.c_N = reinterpret_cast<double *>(dv + p.o_cN);
-        a.x = reinterpret_cast<double *>(dv + p.o_x);
-        a.y = kind == ELLP_ENGINE_DUAL ? reinterpret_cast<double *>(dv + p.o_y) : nullptr;
-        a.dd = kind == ELLP_ENGINE_DUAL ? reinterpret_cast<double *>(dv + p.o_d) : nullptr;
-        a.lb = reinterpret_cast<const double *>(dv + p.o_lb);
-        a.ub = reinterpret_cast<const double *>(dv + p.o_ub);
-        a.kind = reinterpret_cast<const uint8_t *>(dv + p.o_kind);
-        a.B_index = reinterpret_cast<int64_t *>(dv + p.o_B);
-        a.N_index = reinterpret_cast<int64_t *>(dv + p.o_N);
-        a.Nb = reinterpret_cast<uint8_t *>(dv + p.o_Nb);
-        a.rbuf = reinterpret_cast<double *>(dv + p.o_rbuf);
-        a.kbuf = reinterpret_cast<double *>(dv + p.o_kbuf);
+        a.A_B = slab_at<double>(dv, p.o_AB);
+        a.A_N = slab_at<double>(dv, p.o_AN);
+        a.c_B = slab_at<double>(dv, p.o_cB);
+        a.c_N = slab_at<double>(dv, p.o_cN);
+        a.x = slab_at<double>(dv, p.o_x);
+        a.y = kind == ELLP_ENGINE_DUAL ? slab_at<double>(dv, p.o_y) : nullptr;
+        a.dd = kind == ELLP_ENGINE_DUAL ? slab_at<double>(dv, p.o_d) : nullptr;
+        a.lb = slab_at<const double>(dv, p.o_lb);
+        a.ub = slab_at<const double>(dv, p.o_ub);
+        a.kind = slab_at<const uint8_t>(dv, p.o_kind);
+        a.B_index = slab_at<int64_t>(dv, p.o_B);
+        a.N_index = slab_at<int64_t>(dv, p.o_N);
+        a.Nb = slab_at<uint8_t>(dv, p.o_Nb);
+        a.rbuf = slab_at<double>(dv, p.o_rbuf);
+        a.kbuf = slab_at<double>(dv, p.o_kbuf);
         a.st = reinterpret_cast<DevState *>(dv) + k;
         a.m = m;
         a.ld = ld;
@@ -303,7 +408,7 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
         a.stamps = nullptr;
         a.maxviol = cfg.maxviol ? 1 : 0;
         a.bflip = cfg.bflip ? 1 : 0;
-        a.flist = cfg.bflip ? reinterpret_cast<long long *>(dv + p.o_fl) : nullptr;
+        a.flist = cfg.bflip ? slab_at<long long>(dv, p.o_fl) : nullptr;
         h_all[k] = a;  // k_primal_obj_batch reads every item's, mid items' included
         if (two) {
             const ellp_batch_primal_item &pi = two->pitems[p.item];
@@ -317,12 +422,12 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
             r.obj1 = std::numeric_limits<double>::quiet_NaN();
             h_rec[k] = r;
             BatchPhaseArgs pa{};
-            pa.c1 = reinterpret_cast<const double *>(dv + p.o_c1);
-            pa.c2 = reinterpret_cast<const double *>(dv + p.o_c2);
-            pa.lb2 = reinterpret_cast<const double *>(dv + p.o_lb2);
-            pa.ub2 = reinterpret_cast<const double *>(dv + p.o_ub2);
-            pa.kind2 = reinterpret_cast<const uint8_t *>(dv + p.o_kind2);
-            pa.rec = reinterpret_cast<BatchPhaseRec *>(dv + L.o_rec) + k;
+            pa.c1 = slab_at<const double>(dv, p.o_c1);
+            pa.c2 = slab_at<const double>(dv, p.o_c2);
+            pa.lb2 = slab_at<const double>(dv, p.o_lb2);
+            pa.ub2 = slab_at<const double>(dv, p.o_ub2);
+            pa.kind2 = slab_at<const uint8_t>(dv, p.o_kind2);
+            pa.rec = slab_at<BatchPhaseRec>(dv, L.o_rec) + k;
             pa.n_c = it.n_c;
             pa.max_iter = cfg.max_iter;
             h_pall[k] = pa;
@@ -334,9 +439,9 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
             ma.lb = a.lb; ma.ub = a.ub; ma.kind = a.kind; ma.B_index = a.B_index; ma.N_index = a.N_index; ma.Nb = a.Nb;
             ma.rbuf = a.rbuf;
             ma.kbuf = a.kbuf;
-            ma.A_Nt = reinterpret_cast<double *>(dv + p.o_ANt);
-            ma.LUa = reinterpret_cast<double *>(dv + p.o_LUa);
-            ma.Ut = reinterpret_cast<double *>(dv + p.o_Ut);
+            ma.A_Nt = slab_at<double>(dv, p.o_ANt);
+            ma.LUa = slab_at<double>(dv, p.o_LUa);
+            ma.Ut = slab_at<double>(dv, p.o_Ut);
             ma.st = a.st; ma.m = m; ma.ld = ld; ma.nN = nN; ma.ldn = p.ldn;
             ma.max_iters = 0;
             ma.nch = a.nch;
@@ -356,12 +461,12 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
     uint64_t uploaded = L.o_sargs_run;
 
     // ---- launch rounds: every item still running, at most a cap of loop bodies each, grouped by kernel and workgroup size
-    SmallArgs *h_run = reinterpret_cast<SmallArgs *>(h + L.o_sargs_run);
-    SmallArgs *d_run = reinterpret_cast<SmallArgs *>(dv + L.o_sargs_run);
-    MidArgs *h_mrun = reinterpret_cast<MidArgs *>(h + L.o_margs_run);
-    MidArgs *d_mrun = reinterpret_cast<MidArgs *>(dv + L.o_margs_run);
-    BatchPhaseArgs *h_prun = two ? reinterpret_cast<BatchPhaseArgs *>(h + L.o_pargs_run) : nullptr;
-    BatchPhaseArgs *d_prun = two ? reinterpret_cast<BatchPhaseArgs *>(dv + L.o_pargs_run) : nullptr;
+    SmallArgs *h_run = slab_at<SmallArgs>(h, L.o_sargs_run);
+    SmallArgs *d_run = slab_at<SmallArgs>(dv, L.o_sargs_run);
+    MidArgs *h_mrun = slab_at<MidArgs>(h, L.o_margs_run);
+    MidArgs *d_mrun = slab_at<MidArgs>(dv, L.o_margs_run);
+    BatchPhaseArgs *h_prun = two ? slab_at<BatchPhaseArgs>(h, L.o_pargs_run) : nullptr;
+    BatchPhaseArgs *d_prun = two ? slab_at<BatchPhaseArgs>(dv, L.o_pargs_run) : nullptr;
     const uint64_t max_iter = cfg.max_iter;
     std::vector<size_t> live;  // plan positions that a launch may still advance
     // (a whole solve also takes the items without nonbasic columns: their checks and hand-off are the workgroup's too)
@@ -450,7 +555,7 @@ ellp_status batch_run_chunk(const BatchRun &cfg, ellp_batch_item *items, BatchPl
         live.swap(next);
     }
     if (kind == ELLP_ENGINE_PRIMAL)
-        hipLaunchKernelGGL(k_primal_obj_batch, dim3((unsigned)R), dim3(1024), 0, stream, reinterpret_cast<const SmallArgs *>(dv + L.o_sargs_all));
+        hipLaunchKernelGGL(k_primal_obj_batch, dim3((unsigned)R), dim3(1024), 0, stream, slab_at<const SmallArgs>(dv, L.o_sargs_all));
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h, dv, L.out_bytes, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -551,9 +656,6 @@ static ellp_status batch_solve_impl(int kind, int64_t count, ellp_batch_item *it
         if (c < cfg.cap_small) cfg.cap_small = c;
         if (c < cfg.cap_mid) cfg.cap_mid = c;
     }
-    size_t budget = (size_t)2 << 30;  // slab bytes per chunk (the staging buffer is a part of it)
-    if (const char *v = getenv("ELLP_BATCH_MAX_BYTES"); v && v[0] && atoll(v) > 0 && (size_t)atoll(v) < budget) budget = (size_t)atoll(v);
-
     // ---- per item: the single call's checks, then what the batch cannot take (all before any HIP call)
     std::vector<BatchPlan> plan;
     const int64_t mid_auto = plan_env().mid_auto_max;
@@ -612,50 +714,12 @@ static ellp_status batch_solve_impl(int kind, int64_t count, ellp_batch_item *it
     }
     if (plan.empty()) return ELLP_OPTIMAL;
 
-    // ---- chunks: consecutive items within the budget (an item alone over it is a chunk of its own)
-    std::vector<size_t> cut{0};
-    size_t max_stage = 0, max_total = 0;
-    {
-        const size_t slack = two ? BATCH_CHUNK_SLACK_PRIMAL : BATCH_CHUNK_SLACK;
-        (void)batch_layout(kind, items, plan.data(), plan.size(), bflip, two != nullptr);  // every item's share of a slab
-        size_t acc = slack;
-        for (size_t k = 0; k < plan.size(); ++k) {
-            if (k > cut.back() && (acc + plan[k].bytes > budget || k - cut.back() >= 65535)) {
-                cut.push_back(k);
-                acc = slack;
-            }
-            acc += plan[k].bytes;
-        }
-        cut.push_back(plan.size());
-        for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const BatchLayout L = batch_layout(kind, items, plan.data() + cut[c], cut[c + 1] - cut[c], bflip, two != nullptr);
-            max_stage = L.stage_bytes > max_stage ? L.stage_bytes : max_stage;
-            max_total = L.total > max_total ? L.total : max_total;
-        }
-    }
-
-    // ---- device
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_err(errbuf, errlen, "no HIP device available (this library has no CPU path)");
-        return ELLP_ERR_DEVICE;
-    }
-    int dev = opts.device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    HIPCHK(hipSetDevice(dev));
-    BatchCleanup cl;
-    HIPCHK(host_set_acquire(dev, &cl.hs));
-    HIPCHK(batch_buf_acquire(dev, true, max_stage, &cl.stage));
-    HIPCHK(batch_buf_acquire(dev, false, max_total, &cl.slab));
-    for (size_t c = 0; c + 1 < cut.size(); ++c) {
-        const ellp_status rc = batch_run_chunk(cfg, items, plan.data() + cut[c], cut[c + 1] - cut[c], cl, status_out, stats_out,
-                                               two, errbuf, errlen);
-        if (rc != ELLP_OPTIMAL) {  // the items that did not run say so; the call's result is unspecified (ellp_hip.h)
-            for (size_t k = cut[c]; k < plan.size(); ++k) status_out[plan[k].item] = rc;
-            return rc;
-        }
-    }
-    return ELLP_OPTIMAL;
+    // ---- the chunks, through the driver (every planned item runs on the batched kernels: no single-path items)
+    return batch_drive(
+        plan, {}, two ? BATCH_CHUNK_SLACK_PRIMAL : BATCH_CHUNK_SLACK, &opts, status_out, nullptr,
+        [&](BatchPlan *pl, size_t R) { return batch_layout(kind, items, pl, R, bflip, two != nullptr); },
+        [&](BatchPlan *pl, size_t R, BatchCleanup &cl) { return batch_run_chunk(cfg, items, pl, R, cl, status_out, stats_out, two, errbuf, errlen); },
+        errbuf, errlen);
 }
 
 // the calling thread's calls of ellp_batch_solve_with_initial (ellp_batch_solve_info): how many so far, the last one's items and kind

@@ -21,9 +21,9 @@
 // The workgroup always has four waves, so the four-wave order of r needs no emulation.
 //
 // The columns are read from the gathered, padded copies A_B / A_N in the chunk's slab (ld a multiple of 16: the double2
-// loads are aligned), which the host stages as ellp_batch.inc stages them.  Chunks, the pinned staging buffer, the slab and
-// the buffer pool are ellp_batch.inc's.  An item the kernel does not take (m > 128, |N| > 65,536) goes through
-// ellp_postsolve inside the call.
+// loads are aligned), which the host stages as ellp_batch.inc stages them (batch_stage_basis).  The driver (budget, chunks,
+// device, the pinned staging buffer, the slab) and the buffer pool are ellp_batch.inc's.  An item the kernel does not take
+// (m > 128, |N| > 65,536) goes through ellp_postsolve inside the call.
 //
 // Included at the end of ellp_engine.hip, after ellp_batch.inc and ellp_post.inc.
 
@@ -333,95 +333,83 @@ constexpr size_t BPOST_CHUNK_SLACK = 16;  // the rounding of the argument array
 
 BpostLayout bpost_layout(const ellp_batch_item *items, BpostPlan *plan, size_t R) {
     BpostLayout L{};
-    size_t off = 0;
-    BpostPlan *owner = nullptr;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += batch_round16(bytes);
-        if (owner) owner->bytes += batch_round16(bytes);
-        return o;
-    };
+    SlabCursor cur;
     for (size_t k = 0; k < R; ++k) {
         BpostPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
-        owner = &p;
+        cur.bytes = &p.bytes;
         p.bytes = sizeof(PostBatchArgs);
-        p.o_y = take(sizeof(double) * (size_t)it.m);
-        p.o_d = take(sizeof(double) * (size_t)it.n_c);
-        p.o_r = take(sizeof(double) * (size_t)it.m);
-        p.o_kkt = take(sizeof(ellp_kkt));
-        p.o_fail = take(sizeof(int));
+        p.o_y = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_d = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_r = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_kkt = cur.take(sizeof(ellp_kkt));
+        p.o_fail = cur.take(sizeof(int));
     }
-    L.out_bytes = off;
+    L.out_bytes = cur.off;
     for (size_t k = 0; k < R; ++k) {
         BpostPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
-        owner = &p;
-        p.o_AB = take(sizeof(double) * (size_t)(p.ld * it.m));
-        p.o_AN = take(sizeof(double) * (size_t)(p.ld * p.nNa));
-        p.o_cB = take(sizeof(double) * (size_t)it.m);
-        p.o_cN = take(sizeof(double) * (size_t)p.nNa);
-        p.o_ct = take(sizeof(double) * (size_t)p.ntail);
-        p.o_x = take(sizeof(double) * (size_t)it.n_c);
-        p.o_b = take(sizeof(double) * (size_t)it.m);
-        p.o_lb = take(sizeof(double) * (size_t)it.n_c);
-        p.o_ub = take(sizeof(double) * (size_t)it.n_c);
-        p.o_kind = take((size_t)it.n_c);
-        p.o_B = take(sizeof(int64_t) * (size_t)it.m);
-        p.o_N = take(sizeof(int64_t) * (size_t)p.nNa);
-        p.o_Nb = take((size_t)p.nNa);
+        cur.bytes = &p.bytes;
+        p.o_AB = cur.take(sizeof(double) * (size_t)(p.ld * it.m));
+        p.o_AN = cur.take(sizeof(double) * (size_t)(p.ld * p.nNa));
+        p.o_cB = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_cN = cur.take(sizeof(double) * (size_t)p.nNa);
+        p.o_ct = cur.take(sizeof(double) * (size_t)p.ntail);
+        p.o_x = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_b = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_lb = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_ub = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_kind = cur.take((size_t)it.n_c);
+        p.o_B = cur.take(sizeof(int64_t) * (size_t)it.m);
+        p.o_N = cur.take(sizeof(int64_t) * (size_t)p.nNa);
+        p.o_Nb = cur.take((size_t)p.nNa);
     }
-    owner = nullptr;
-    L.o_args = take(sizeof(PostBatchArgs) * R);
-    L.stage_bytes = off;
+    cur.bytes = nullptr;
+    L.o_args = cur.take(sizeof(PostBatchArgs) * R);
+    L.stage_bytes = cur.off;
     for (size_t k = 0; k < R; ++k) {
         BpostPlan &p = plan[k];
-        owner = &p;
-        p.o_rho = take(sizeof(double) * (size_t)items[p.item].m);
-        p.o_omega = take(sizeof(double));
-        p.o_steps = take(sizeof(int32_t));
+        cur.bytes = &p.bytes;
+        p.o_rho = cur.take(sizeof(double) * (size_t)items[p.item].m);
+        p.o_omega = cur.take(sizeof(double));
+        p.o_steps = cur.take(sizeof(int32_t));
     }
-    L.total = off;
+    L.total = cur.off;
     return L;
-}
-
-// chunks: consecutive items within the budget (an item alone over it is a chunk of its own); plan[k].bytes is item k's share
-template <typename Plan>
-std::vector<size_t> bpost_cuts(const std::vector<Plan> &plan, size_t budget) {
-    std::vector<size_t> cut{0};
-    size_t acc = BPOST_CHUNK_SLACK;
-    for (size_t k = 0; k < plan.size(); ++k) {
-        if (k > cut.back() && (acc + plan[k].bytes > budget || k - cut.back() >= 65535)) {
-            cut.push_back(k);
-            acc = BPOST_CHUNK_SLACK;
-        }
-        acc += plan[k].bytes;
-    }
-    cut.push_back(plan.size());
-    return cut;
 }
 
 // the calling thread's last ellp_batch_postsolve that passed the checks of the call (ellp_batch_postsolve_info)
 thread_local uint64_t g_batch_post_info[4] = {0, 0, 0, 0};
 
+// The item as the report sees it, from its plan's offsets in the slab dv (BpostPlan and BstartPlan name them alike); c_tail
+// is the caller's.  ra.steps stays 0: the batch reads the item's steps on the device
+template <class Plan>
+void bpost_report_args(PostReportArgs &ra, unsigned char *dv, const Plan &p, const ellp_batch_item &it) {
+    ra.r = slab_at<double>(dv, p.o_r);
+    ra.d = slab_at<double>(dv, p.o_d);
+    ra.rho = slab_at<double>(dv, p.o_rho);
+    ra.y = slab_at<double>(dv, p.o_y);
+    ra.omega = slab_at<double>(dv, p.o_omega);
+    ra.b = slab_at<double>(dv, p.o_b);
+    ra.x = slab_at<double>(dv, p.o_x);
+    ra.lb = slab_at<double>(dv, p.o_lb);
+    ra.ub = slab_at<double>(dv, p.o_ub);
+    ra.c_B = slab_at<double>(dv, p.o_cB);
+    ra.c_N = slab_at<double>(dv, p.o_cN);
+    ra.kind = slab_at<uint8_t>(dv, p.o_kind);
+    ra.Nb = slab_at<uint8_t>(dv, p.o_Nb);
+    ra.B_index = slab_at<int64_t>(dv, p.o_B);
+    ra.N_index = slab_at<int64_t>(dv, p.o_N);
+    ra.m = it.m; ra.n = it.n; ra.n_c = it.n_c; ra.nN = it.n_N;
+    ra.out = slab_at<ellp_kkt>(dv, p.o_kkt);
+}
+
 // One item into the staging buffer h, as its plan lays it out, and its arguments in the slab dv.  Shared by
 // ellp_batch_postsolve and ellp_batch_ranging (ellp_brange.inc), whose plan extends this one
 PostBatchArgs bpost_stage_item(unsigned char *h, unsigned char *dv, const BpostPlan &p, const ellp_batch_item &it) {
-    const int64_t m = it.m, nN = it.n_N, ld = p.ld;
+    const int64_t m = it.m, nN = it.n_N;
     memset(h + p.o_fail, 0, sizeof(int));
-    double *AB = reinterpret_cast<double *>(h + p.o_AB), *AN = reinterpret_cast<double *>(h + p.o_AN);
-    double *cB = reinterpret_cast<double *>(h + p.o_cB), *cN = reinterpret_cast<double *>(h + p.o_cN);
-    for (int64_t j = 0; j < m; ++j) {
-        memcpy(AB + j * ld, it.A + it.B_index[j] * m, sizeof(double) * (size_t)m);
-        memset(AB + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
-        cB[j] = it.c[it.B_index[j]];
-    }
-    if (nN == 0) memset(AN, 0, sizeof(double) * (size_t)ld);
-    for (int64_t j = 0; j < nN; ++j) {
-        memcpy(AN + j * ld, it.A + it.N_index[j] * m, sizeof(double) * (size_t)m);
-        memset(AN + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
-        cN[j] = it.c[it.N_index[j]];
-    }
+    batch_stage_basis(h, it, p.ld, p.o_AB, p.o_AN, p.o_cB, p.o_cN);
     if (p.ntail > 0) memcpy(h + p.o_ct, it.c + it.n, sizeof(double) * (size_t)p.ntail);
     memcpy(h + p.o_x, it.x, sizeof(double) * (size_t)it.n_c);
     memcpy(h + p.o_b, it.b, sizeof(double) * (size_t)m);
@@ -434,33 +422,19 @@ PostBatchArgs bpost_stage_item(unsigned char *h, unsigned char *dv, const BpostP
         memcpy(h + p.o_Nb, it.N_bound, (size_t)nN);
     }
     PostBatchArgs a{};
-    a.A_B = reinterpret_cast<const double *>(dv + p.o_AB);
-    a.A_N = reinterpret_cast<const double *>(dv + p.o_AN);
-    a.c_N = reinterpret_cast<const double *>(dv + p.o_cN);
-    a.y = reinterpret_cast<double *>(dv + p.o_y);
-    a.d = reinterpret_cast<double *>(dv + p.o_d);
-    a.r = reinterpret_cast<double *>(dv + p.o_r);
-    a.rho = reinterpret_cast<double *>(dv + p.o_rho);
-    a.omega = reinterpret_cast<double *>(dv + p.o_omega);
-    a.steps = reinterpret_cast<int32_t *>(dv + p.o_steps);
-    a.fail = reinterpret_cast<int *>(dv + p.o_fail);
-    a.ld = ld;
-    PostReportArgs &ra = a.rep;
-    ra.r = a.r; ra.d = a.d; ra.rho = a.rho; ra.y = a.y; ra.omega = a.omega;
-    ra.b = reinterpret_cast<const double *>(dv + p.o_b);
-    ra.x = reinterpret_cast<const double *>(dv + p.o_x);
-    ra.lb = reinterpret_cast<const double *>(dv + p.o_lb);
-    ra.ub = reinterpret_cast<const double *>(dv + p.o_ub);
-    ra.c_B = reinterpret_cast<const double *>(dv + p.o_cB);
-    ra.c_N = a.c_N;
-    ra.c_tail = reinterpret_cast<const double *>(dv + p.o_ct);
-    ra.kind = reinterpret_cast<const uint8_t *>(dv + p.o_kind);
-    ra.Nb = reinterpret_cast<const uint8_t *>(dv + p.o_Nb);
-    ra.B_index = reinterpret_cast<const int64_t *>(dv + p.o_B);
-    ra.N_index = reinterpret_cast<const int64_t *>(dv + p.o_N);
-    ra.m = m; ra.n = it.n; ra.n_c = it.n_c; ra.nN = nN;
-    ra.steps = 0;  // the batch reads a.steps on the device
-    ra.out = reinterpret_cast<ellp_kkt *>(dv + p.o_kkt);
+    a.A_B = slab_at<double>(dv, p.o_AB);
+    a.A_N = slab_at<double>(dv, p.o_AN);
+    a.c_N = slab_at<double>(dv, p.o_cN);
+    a.y = slab_at<double>(dv, p.o_y);
+    a.d = slab_at<double>(dv, p.o_d);
+    a.r = slab_at<double>(dv, p.o_r);
+    a.rho = slab_at<double>(dv, p.o_rho);
+    a.omega = slab_at<double>(dv, p.o_omega);
+    a.steps = slab_at<int32_t>(dv, p.o_steps);
+    a.fail = slab_at<int>(dv, p.o_fail);
+    a.ld = p.ld;
+    bpost_report_args(a.rep, dv, p, it);
+    a.rep.c_tail = slab_at<double>(dv, p.o_ct);
     return a;
 }
 
@@ -471,7 +445,7 @@ ellp_status bpost_run_chunk(ellp_batch_item *items, const ellp_batch_post_out *o
     hipStream_t stream = cl.hs.stream;
     unsigned char *h = static_cast<unsigned char *>(cl.stage.p);
     unsigned char *dv = static_cast<unsigned char *>(cl.slab.p);
-    PostBatchArgs *h_args = reinterpret_cast<PostBatchArgs *>(h + L.o_args);
+    PostBatchArgs *h_args = slab_at<PostBatchArgs>(h, L.o_args);
     size_t lds = 0;
     for (size_t k = 0; k < R; ++k) {
         const BpostPlan &p = plan[k];
@@ -480,7 +454,7 @@ ellp_status bpost_run_chunk(ellp_batch_item *items, const ellp_batch_post_out *o
     }
     // the outputs' region goes up too (the fail flags are its only part that is read before it is written)
     HIPCHK(hipMemcpyAsync(dv, h, L.stage_bytes, hipMemcpyHostToDevice, stream));
-    const PostBatchArgs *d_args = reinterpret_cast<const PostBatchArgs *>(dv + L.o_args);
+    const PostBatchArgs *d_args = slab_at<const PostBatchArgs>(dv, L.o_args);
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_post_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // ELLP_POST_PROFILE=1 (tools/batch_postsolve_time.py): one line per chunk in the single call's format, with m = the
     // chunk's items, lu_ms = k_post_batch (everything up to r) and rest_ms = the reports
@@ -501,13 +475,7 @@ ellp_status bpost_run_chunk(ellp_batch_item *items, const ellp_batch_post_out *o
         const BpostPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
         const ellp_batch_post_out &o = outs[p.item];
-        int fail = 0;
-        memcpy(&fail, h + p.o_fail, sizeof(int));
-        if (fail) {
-            set_err(items[p.item].err, sizeof(items[p.item].err), "invalid B, A_B is not invertible");
-            status_out[p.item] = ELLP_ERR_SINGULAR;
-            continue;
-        }
+        if (batch_item_singular(h, p.o_fail, items[p.item], &status_out[p.item])) continue;
         if (o.y) memcpy(o.y, h + p.o_y, sizeof(double) * (size_t)it.m);
         if (o.d) memcpy(o.d, h + p.o_d, sizeof(double) * (size_t)it.n_c);
         if (o.r) memcpy(o.r, h + p.o_r, sizeof(double) * (size_t)it.m);
@@ -526,9 +494,6 @@ extern "C" ellp_status ellp_batch_postsolve(int64_t count, ellp_batch_item *item
         set_err(errbuf, errlen, "count < 0, or items / outs / status_out NULL");
         return ELLP_ERR_ARG;
     }
-    size_t budget = (size_t)2 << 30;  // slab bytes per chunk, as ellp_batch_solve_with_initial
-    if (const char *v = getenv("ELLP_BATCH_MAX_BYTES"); v && v[0] && atoll(v) > 0 && (size_t)atoll(v) < budget) budget = (size_t)atoll(v);
-
     // ---- per item: the single call's checks, then who runs it (all before any HIP call)
     std::vector<BpostPlan> plan;
     std::vector<int64_t> single;
@@ -565,39 +530,12 @@ extern "C" ellp_status ellp_batch_postsolve(int64_t count, ellp_batch_item *item
     if (plan.empty() && single.empty()) return ELLP_OPTIMAL;
 
     if (!plan.empty()) {
-        // ---- chunks: consecutive items within the budget (an item alone over it is a chunk of its own)
-        size_t max_stage = 0, max_total = 0;
-        (void)bpost_layout(items, plan.data(), plan.size());  // every item's share of a slab
-        const std::vector<size_t> cut = bpost_cuts(plan, budget);
-        for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const BpostLayout L = bpost_layout(items, plan.data() + cut[c], cut[c + 1] - cut[c]);
-            max_stage = L.stage_bytes > max_stage ? L.stage_bytes : max_stage;
-            max_total = L.total > max_total ? L.total : max_total;
-        }
-        ellp_opts opts;
-        ellp_default_opts(&opts);
-        if (opts_in) opts = *opts_in;
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-            set_err(errbuf, errlen, "no HIP device available (this library has no CPU path)");
-            return ELLP_ERR_DEVICE;
-        }
-        int dev = opts.device;
-        if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-        HIPCHK(hipSetDevice(dev));
-        BatchCleanup cl;
-        HIPCHK(host_set_acquire(dev, &cl.hs));
-        HIPCHK(batch_buf_acquire(dev, true, max_stage, &cl.stage));
-        HIPCHK(batch_buf_acquire(dev, false, max_total, &cl.slab));
-        for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const ellp_status rc = bpost_run_chunk(items, outs, plan.data() + cut[c], cut[c + 1] - cut[c], cl, status_out, errbuf, errlen);
-            if (rc != ELLP_OPTIMAL) {  // the items that did not run say so
-                for (size_t k = cut[c]; k < plan.size(); ++k) status_out[plan[k].item] = rc;
-                for (int64_t i : single) status_out[i] = rc;
-                return rc;
-            }
-            g_batch_post_info[3] += 1;
-        }
+        const ellp_status rc = batch_drive(
+            plan, single, BPOST_CHUNK_SLACK, opts_in, status_out, &g_batch_post_info[3],
+            [&](BpostPlan *pl, size_t R) { return bpost_layout(items, pl, R); },
+            [&](BpostPlan *pl, size_t R, BatchCleanup &cl) { return bpost_run_chunk(items, outs, pl, R, cl, status_out, errbuf, errlen); },
+            errbuf, errlen);
+        if (rc != ELLP_OPTIMAL) return rc;
     }
     // ---- the items the kernel does not take: the single call, inside this one
     for (int64_t i : single) {

@@ -21,10 +21,10 @@
 // postsolve's (ellp_bpost.inc), everything else runs the single call's own device functions on the single call's numbers.
 // An item whose LU meets a zero on U's diagonal sets its flag in A; B to E leave it alone.
 //
-// Chunks, the pinned staging buffer, the slab and the buffer pool are ellp_batch.inc's; the staging of an item is
-// ellp_bpost.inc's.  The outputs an item asks for lie at the front of the slab and come back in one read-back; those it
-// does not ask for (W above all) lie behind the inputs and stay on the device.  The fail flags end the outputs' region so
-// that one upload from there on zeroes them.
+// The driver (budget, chunks, device, the pinned staging buffer, the slab) and the buffer pool are ellp_batch.inc's; the
+// staging of an item is ellp_bpost.inc's.  The outputs an item asks for lie at the front of the slab and come back in one
+// read-back; those it does not ask for (W above all) lie behind the inputs and stay on the device.  The fail flags end the
+// outputs' region so that one upload from there on zeroes them.
 //
 // Included at the end of ellp_engine.hip, after ellp_range.inc and ellp_bpost.inc.
 
@@ -164,87 +164,80 @@ struct BrangeLayout {
 
 BrangeLayout brange_layout(const ellp_batch_item *items, BrangePlan *plan, size_t R) {
     BrangeLayout L{};
-    size_t off = 0;
-    BrangePlan *owner = nullptr;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += batch_round16(bytes);
-        if (owner) owner->bytes += batch_round16(bytes);
-        return o;
-    };
+    SlabCursor cur;
     // an array that comes back where it is wanted (pass 0) and stays on the device where it is not (pass 1)
     auto split = [&](int pass, BrangePlan &q) {
         const BrangePlan &p = q;
         const ellp_batch_item &it = items[p.item];
         const size_t m = (size_t)it.m, nc = (size_t)it.n_c;
-        if ((pass == 0) == p.w_y) q.o_y = take(sizeof(double) * m);
-        if ((pass == 0) == p.w_d) q.o_d = take(sizeof(double) * nc);
-        if ((pass == 0) == p.w_cost) q.o_cost = take(sizeof(double) * 2 * nc);
-        if ((pass == 0) == p.w_cblk) q.o_cblk = take(sizeof(int64_t) * 2 * nc);
-        if ((pass == 0) == p.w_rhs) q.o_rhs = take(sizeof(double) * 2 * m);
-        if ((pass == 0) == p.w_rblk) q.o_rblk = take(sizeof(int64_t) * 2 * m);
-        if ((pass == 0) == p.w_W) q.o_W = take(sizeof(double) * m * (size_t)p.ld);
+        if ((pass == 0) == p.w_y) q.o_y = cur.take(sizeof(double) * m);
+        if ((pass == 0) == p.w_d) q.o_d = cur.take(sizeof(double) * nc);
+        if ((pass == 0) == p.w_cost) q.o_cost = cur.take(sizeof(double) * 2 * nc);
+        if ((pass == 0) == p.w_cblk) q.o_cblk = cur.take(sizeof(int64_t) * 2 * nc);
+        if ((pass == 0) == p.w_rhs) q.o_rhs = cur.take(sizeof(double) * 2 * m);
+        if ((pass == 0) == p.w_rblk) q.o_rblk = cur.take(sizeof(int64_t) * 2 * m);
+        if ((pass == 0) == p.w_W) q.o_W = cur.take(sizeof(double) * m * (size_t)p.ld);
     };
     for (size_t k = 0; k < R; ++k) {
         BrangePlan &p = plan[k];
-        owner = &p;
+        cur.bytes = &p.bytes;
         p.bytes = sizeof(PostBatchArgs) + sizeof(BrangeArgs) + sizeof(int2) * (size_t)(p.nsolve + p.nblk);
         split(0, p);
-        p.o_kkt = take(sizeof(ellp_kkt));
-        p.o_res = take(sizeof(double));
+        p.o_kkt = cur.take(sizeof(ellp_kkt));
+        p.o_res = cur.take(sizeof(double));
     }
-    L.up_from = off;
+    L.up_from = cur.off;
     for (size_t k = 0; k < R; ++k) {
-        owner = &plan[k];
-        plan[k].o_fail = take(sizeof(int));
+        cur.bytes = &plan[k].bytes;
+        plan[k].o_fail = cur.take(sizeof(int));
     }
-    L.out_bytes = off;
+    L.out_bytes = cur.off;
     L.nsolve = L.ntab = 0;
     for (size_t k = 0; k < R; ++k) {
         BrangePlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
-        owner = &p;
-        p.o_AB = take(sizeof(double) * (size_t)(p.ld * it.m));
-        p.o_AN = take(sizeof(double) * (size_t)(p.ld * p.nNa));
-        p.o_cB = take(sizeof(double) * (size_t)it.m);
-        p.o_cN = take(sizeof(double) * (size_t)p.nNa);
-        p.o_ct = take(sizeof(double) * (size_t)p.ntail);
-        p.o_x = take(sizeof(double) * (size_t)it.n_c);
-        p.o_b = take(sizeof(double) * (size_t)it.m);
-        p.o_lb = take(sizeof(double) * (size_t)it.n_c);
-        p.o_ub = take(sizeof(double) * (size_t)it.n_c);
-        p.o_kind = take((size_t)it.n_c);
-        p.o_B = take(sizeof(int64_t) * (size_t)it.m);
-        p.o_N = take(sizeof(int64_t) * (size_t)p.nNa);
-        p.o_Nb = take((size_t)p.nNa);
+        cur.bytes = &p.bytes;
+        p.o_AB = cur.take(sizeof(double) * (size_t)(p.ld * it.m));
+        p.o_AN = cur.take(sizeof(double) * (size_t)(p.ld * p.nNa));
+        p.o_cB = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_cN = cur.take(sizeof(double) * (size_t)p.nNa);
+        p.o_ct = cur.take(sizeof(double) * (size_t)p.ntail);
+        p.o_x = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_b = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_lb = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_ub = cur.take(sizeof(double) * (size_t)it.n_c);
+        p.o_kind = cur.take((size_t)it.n_c);
+        p.o_B = cur.take(sizeof(int64_t) * (size_t)it.m);
+        p.o_N = cur.take(sizeof(int64_t) * (size_t)p.nNa);
+        p.o_Nb = cur.take((size_t)p.nNa);
         L.nsolve += (size_t)p.nsolve;
         L.ntab += (size_t)p.nblk;
     }
-    owner = nullptr;
-    L.o_pargs = take(sizeof(PostBatchArgs) * R);
-    L.o_rargs = take(sizeof(BrangeArgs) * R);
-    L.o_tsolve = take(sizeof(int2) * L.nsolve);
-    L.o_ttab = take(sizeof(int2) * L.ntab);
-    L.stage_bytes = off;
+    cur.bytes = nullptr;
+    L.o_pargs = cur.take(sizeof(PostBatchArgs) * R);
+    L.o_rargs = cur.take(sizeof(BrangeArgs) * R);
+    L.o_tsolve = cur.take(sizeof(int2) * L.nsolve);
+    L.o_ttab = cur.take(sizeof(int2) * L.ntab);
+    L.stage_bytes = cur.off;
     for (size_t k = 0; k < R; ++k) {
         BrangePlan &p = plan[k];
         const size_t m = (size_t)items[p.item].m, rec = (size_t)p.nblk * m;
-        owner = &p;
+        cur.bytes = &p.bytes;
         split(1, p);
-        p.o_r = take(sizeof(double) * m);
-        p.o_rho = take(sizeof(double) * m);
-        p.o_omega = take(sizeof(double));
-        p.o_steps = take(sizeof(int32_t));
-        p.o_M = take(sizeof(double) * m * m);
-        p.o_piv = take(sizeof(int64_t) * m);
-        p.o_srow = take(sizeof(int32_t) * m);
-        p.o_sval = take(sizeof(double) * m);
-        p.o_pu = take(sizeof(double) * rec);
-        p.o_pd = take(sizeof(double) * rec);
-        p.o_ppu = take(sizeof(int32_t) * rec);
-        p.o_ppd = take(sizeof(int32_t) * rec);
+        p.o_r = cur.take(sizeof(double) * m);
+        p.o_rho = cur.take(sizeof(double) * m);
+        p.o_omega = cur.take(sizeof(double));
+        p.o_steps = cur.take(sizeof(int32_t));
+        p.o_M = cur.take(sizeof(double) * m * m);
+        p.o_piv = cur.take(sizeof(int64_t) * m);
+        p.o_srow = cur.take(sizeof(int32_t) * m);
+        p.o_sval = cur.take(sizeof(double) * m);
+        p.o_pu = cur.take(sizeof(double) * rec);
+        p.o_pd = cur.take(sizeof(double) * rec);
+        p.o_ppu = cur.take(sizeof(int32_t) * rec);
+        p.o_ppd = cur.take(sizeof(int32_t) * rec);
     }
-    L.total = off;
+    L.total = cur.off;
     return L;
 }
 
@@ -290,9 +283,9 @@ ellp_status brange_run_chunk(ellp_batch_item *items, const ellp_batch_range_out 
     hipStream_t stream = cl.hs.stream;
     unsigned char *h = static_cast<unsigned char *>(cl.stage.p);
     unsigned char *dv = static_cast<unsigned char *>(cl.slab.p);
-    PostBatchArgs *h_pargs = reinterpret_cast<PostBatchArgs *>(h + L.o_pargs);
-    BrangeArgs *h_rargs = reinterpret_cast<BrangeArgs *>(h + L.o_rargs);
-    int2 *h_tsolve = reinterpret_cast<int2 *>(h + L.o_tsolve), *h_ttab = reinterpret_cast<int2 *>(h + L.o_ttab);
+    PostBatchArgs *h_pargs = slab_at<PostBatchArgs>(h, L.o_pargs);
+    BrangeArgs *h_rargs = slab_at<BrangeArgs>(h, L.o_rargs);
+    int2 *h_tsolve = slab_at<int2>(h, L.o_tsolve), *h_ttab = slab_at<int2>(h, L.o_ttab);
     size_t lds = 0, lds_solve = 0, ns = 0, nt = 0;
     for (size_t k = 0; k < R; ++k) {
         const BrangePlan &p = plan[k];
@@ -302,20 +295,20 @@ ellp_status brange_run_chunk(ellp_batch_item *items, const ellp_batch_range_out 
         const int64_t m = it.m, n_c = it.n_c;
         BrangeArgs a{};
         a.A_B = pa.A_B;
-        a.M = reinterpret_cast<double *>(dv + p.o_M);
-        a.sval = reinterpret_cast<double *>(dv + p.o_sval);
-        a.W = reinterpret_cast<double *>(dv + p.o_W);
-        a.res = reinterpret_cast<double *>(dv + p.o_res);
-        a.piv = reinterpret_cast<int64_t *>(dv + p.o_piv);
-        a.srow = reinterpret_cast<int32_t *>(dv + p.o_srow);
+        a.M = slab_at<double>(dv, p.o_M);
+        a.sval = slab_at<double>(dv, p.o_sval);
+        a.W = slab_at<double>(dv, p.o_W);
+        a.res = slab_at<double>(dv, p.o_res);
+        a.piv = slab_at<int64_t>(dv, p.o_piv);
+        a.srow = slab_at<int32_t>(dv, p.o_srow);
         a.fail = pa.fail;
         a.m = m; a.ld = p.ld; a.ldw = p.ld;
-        double *cost = reinterpret_cast<double *>(dv + p.o_cost);
-        int64_t *cblk = reinterpret_cast<int64_t *>(dv + p.o_cblk);
+        double *cost = slab_at<double>(dv, p.o_cost);
+        int64_t *cblk = slab_at<int64_t>(dv, p.o_cblk);
         RngTabArgs &t = a.tab;
         t.W = a.W; t.rowmap = nullptr; t.A_N = pa.A_N; t.d = pa.d; t.N_index = pa.rep.N_index; t.Nb = pa.rep.Nb; t.kind = pa.rep.kind;
-        t.pu = reinterpret_cast<double *>(dv + p.o_pu); t.pd = reinterpret_cast<double *>(dv + p.o_pd);
-        t.ppu = reinterpret_cast<int32_t *>(dv + p.o_ppu); t.ppd = reinterpret_cast<int32_t *>(dv + p.o_ppd);
+        t.pu = slab_at<double>(dv, p.o_pu); t.pd = slab_at<double>(dv, p.o_pd);
+        t.ppu = slab_at<int32_t>(dv, p.o_ppu); t.ppd = slab_at<int32_t>(dv, p.o_ppd);
         t.out = nullptr; t.m = m; t.ld = p.ld; t.ldw = p.ld; t.nrows = m; t.nN = it.n_N; t.eps = eps;
         RngCfoldArgs &f = a.fold;
         f.pu = t.pu; f.pd = t.pd; f.ppu = t.ppu; f.ppd = t.ppd; f.B_index = pa.rep.B_index; f.N_index = pa.rep.N_index;
@@ -325,7 +318,7 @@ ellp_status brange_run_chunk(ellp_batch_item *items, const ellp_batch_range_out 
         c.nN = it.n_N; c.n = it.n; c.n_c = n_c;
         RngRhsArgs &r = a.rhs;
         r.W = a.W; r.x = pa.rep.x; r.lb = pa.rep.lb; r.ub = pa.rep.ub; r.kind = pa.rep.kind; r.B_index = pa.rep.B_index;
-        r.rhs = reinterpret_cast<double *>(dv + p.o_rhs); r.rblk = reinterpret_cast<int64_t *>(dv + p.o_rblk);
+        r.rhs = slab_at<double>(dv, p.o_rhs); r.rblk = slab_at<int64_t>(dv, p.o_rblk);
         r.m = m; r.ldw = p.ld; r.eps = eps;
         h_rargs[k] = a;
         for (int64_t q = 0; q < p.nsolve; ++q) h_tsolve[ns++] = make_int2((int)k, (int)q);
@@ -336,9 +329,9 @@ ellp_status brange_run_chunk(ellp_batch_item *items, const ellp_batch_range_out 
     }
     // from the fail flags on: the flags are zeroed, the outputs in front of them are written before they are read
     HIPCHK(hipMemcpyAsync(dv + L.up_from, h + L.up_from, L.stage_bytes - L.up_from, hipMemcpyHostToDevice, stream));
-    const PostBatchArgs *d_pargs = reinterpret_cast<const PostBatchArgs *>(dv + L.o_pargs);
-    const BrangeArgs *d_rargs = reinterpret_cast<const BrangeArgs *>(dv + L.o_rargs);
-    const int2 *d_tsolve = reinterpret_cast<const int2 *>(dv + L.o_tsolve), *d_ttab = reinterpret_cast<const int2 *>(dv + L.o_ttab);
+    const PostBatchArgs *d_pargs = slab_at<const PostBatchArgs>(dv, L.o_pargs);
+    const BrangeArgs *d_rargs = slab_at<const BrangeArgs>(dv, L.o_rargs);
+    const int2 *d_tsolve = slab_at<const int2>(dv, L.o_tsolve), *d_ttab = slab_at<const int2>(dv, L.o_ttab);
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_brange_front), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     BrangeProf prof(stream);
     prof.mark();
@@ -363,13 +356,7 @@ ellp_status brange_run_chunk(ellp_batch_item *items, const ellp_batch_range_out 
         const ellp_batch_item &it = items[p.item];
         const ellp_batch_range_out &bo = outs[p.item];
         const ellp_ranging_out &o = bo.out;
-        int fail = 0;
-        memcpy(&fail, h + p.o_fail, sizeof(int));
-        if (fail) {
-            set_err(items[p.item].err, sizeof(items[p.item].err), "invalid B, A_B is not invertible");
-            status_out[p.item] = ELLP_ERR_SINGULAR;
-            continue;
-        }
+        if (batch_item_singular(h, p.o_fail, items[p.item], &status_out[p.item])) continue;
         const size_t cb = sizeof(double) * (size_t)it.n_c, rb = sizeof(double) * (size_t)it.m;
         if (o.cost_down) memcpy(o.cost_down, h + p.o_cost, cb);
         if (o.cost_up) memcpy(o.cost_up, h + p.o_cost + cb, cb);
@@ -422,9 +409,6 @@ extern "C" ellp_status ellp_batch_ranging(int64_t count, ellp_batch_item *items,
         set_err(errbuf, errlen, "count < 0, or items / outs / status_out NULL");
         return ELLP_ERR_ARG;
     }
-    size_t budget = (size_t)2 << 30;  // slab bytes per chunk, as ellp_batch_solve_with_initial
-    if (const char *v = getenv("ELLP_BATCH_MAX_BYTES"); v && v[0] && atoll(v) > 0 && (size_t)atoll(v) < budget) budget = (size_t)atoll(v);
-
     // ---- per item: the single call's checks, then who runs it (all before any HIP call)
     std::vector<BrangePlan> plan;
     std::vector<int64_t> single;
@@ -471,39 +455,13 @@ extern "C" ellp_status ellp_batch_ranging(int64_t count, ellp_batch_item *items,
     if (plan.empty() && single.empty()) return ELLP_OPTIMAL;
 
     if (!plan.empty()) {
-        size_t max_stage = 0, max_total = 0;
-        (void)brange_layout(items, plan.data(), plan.size());  // every item's share of a slab
-        const std::vector<size_t> cut = bpost_cuts(plan, budget);
-        for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const BrangeLayout L = brange_layout(items, plan.data() + cut[c], cut[c + 1] - cut[c]);
-            max_stage = L.stage_bytes > max_stage ? L.stage_bytes : max_stage;
-            max_total = L.total > max_total ? L.total : max_total;
-        }
-        ellp_opts opts;
-        ellp_default_opts(&opts);
-        if (opts_in) opts = *opts_in;
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-            set_err(errbuf, errlen, "no HIP device available (this library has no CPU path)");
-            return ELLP_ERR_DEVICE;
-        }
-        int dev = opts.device;
-        if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-        HIPCHK(hipSetDevice(dev));
-        BatchCleanup cl;
-        HIPCHK(host_set_acquire(dev, &cl.hs));
-        HIPCHK(batch_buf_acquire(dev, true, max_stage, &cl.stage));
-        HIPCHK(batch_buf_acquire(dev, false, max_total, &cl.slab));
-        const double eps = opts.eps > 0.0 ? opts.eps : 1e-10;  // post_host_engine's
-        for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const ellp_status rc = brange_run_chunk(items, outs, eps, plan.data() + cut[c], cut[c + 1] - cut[c], cl, status_out, errbuf, errlen);
-            if (rc != ELLP_OPTIMAL) {  // the items that did not run say so
-                for (size_t k = cut[c]; k < plan.size(); ++k) status_out[plan[k].item] = rc;
-                for (int64_t i : single) status_out[i] = rc;
-                return rc;
-            }
-            g_batch_range_info[3] += 1;
-        }
+        const double eps = opts_in && opts_in->eps > 0.0 ? opts_in->eps : 1e-10;  // post_host_engine's
+        const ellp_status rc = batch_drive(
+            plan, single, BPOST_CHUNK_SLACK, opts_in, status_out, &g_batch_range_info[3],
+            [&](BrangePlan *pl, size_t R) { return brange_layout(items, pl, R); },
+            [&](BrangePlan *pl, size_t R, BatchCleanup &cl) { return brange_run_chunk(items, outs, eps, pl, R, cl, status_out, errbuf, errlen); },
+            errbuf, errlen);
+        if (rc != ELLP_OPTIMAL) return rc;
     }
     // ---- the items the kernels do not take: the single call's steps, inside this one
     for (int64_t i : single) status_out[i] = brange_single(items[i], opts_in, outs[i], items[i].err, sizeof(items[i].err));

@@ -6,7 +6,8 @@
 // refined y (bpost_solve_y, k_post_batch's), d_N, the labels and the nonbasic values, t = b - A_N x_N, x_B = B^-1 t with the
 // singleton rows snapped, the refinement loop of x_B with the host's stop rule, and r.  k_start_report_batch then runs
 // post_report and start_verdict once per item, with the single call's 1,024 threads.  Two launches per chunk, whatever the
-// item count; one upload and one read-back per chunk.
+// item count; one upload and one read-back per chunk.  The driver (budget, chunks, device, the pinned staging buffer, the
+// slab) and the buffer pool are ellp_batch.inc's.
 //
 // Every output is, bit for bit, what ellp_basis_start returns for the item alone.  The orders of y, d, r and omega are
 // those ellp_bpost.inc lists; on top of them
@@ -223,59 +224,52 @@ struct BstartPlan {
 
 BpostLayout bstart_layout(const ellp_batch_item *items, BstartPlan *plan, size_t R) {
     BpostLayout L{};
-    size_t off = 0;
-    BstartPlan *owner = nullptr;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += batch_round16(bytes);
-        if (owner) owner->bytes += batch_round16(bytes);
-        return o;
-    };
+    SlabCursor cur;
     for (size_t k = 0; k < R; ++k) {
         BstartPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
-        owner = &p;
+        cur.bytes = &p.bytes;
         p.bytes = sizeof(StartBatchArgs);
-        p.o_x = take(sizeof(double) * (size_t)it.n);
-        p.o_y = take(sizeof(double) * (size_t)it.m);
-        p.o_d = take(sizeof(double) * (size_t)it.n);
-        p.o_Nb = take((size_t)p.nNa);
-        p.o_kkt = take(sizeof(ellp_kkt));
-        p.o_verdict = take(sizeof(StartVerdict));
-        p.o_xomega = take(sizeof(double));
-        p.o_xsteps = take(sizeof(int32_t));
-        p.o_changed = take(sizeof(long long));
-        p.o_fail = take(sizeof(int));
+        p.o_x = cur.take(sizeof(double) * (size_t)it.n);
+        p.o_y = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_d = cur.take(sizeof(double) * (size_t)it.n);
+        p.o_Nb = cur.take((size_t)p.nNa);
+        p.o_kkt = cur.take(sizeof(ellp_kkt));
+        p.o_verdict = cur.take(sizeof(StartVerdict));
+        p.o_xomega = cur.take(sizeof(double));
+        p.o_xsteps = cur.take(sizeof(int32_t));
+        p.o_changed = cur.take(sizeof(long long));
+        p.o_fail = cur.take(sizeof(int));
     }
-    L.out_bytes = off;
+    L.out_bytes = cur.off;
     for (size_t k = 0; k < R; ++k) {
         BstartPlan &p = plan[k];
         const ellp_batch_item &it = items[p.item];
-        owner = &p;
-        p.o_AB = take(sizeof(double) * (size_t)(p.ld * it.m));
-        p.o_AN = take(sizeof(double) * (size_t)(p.ld * p.nNa));
-        p.o_cB = take(sizeof(double) * (size_t)it.m);
-        p.o_cN = take(sizeof(double) * (size_t)p.nNa);
-        p.o_b = take(sizeof(double) * (size_t)it.m);
-        p.o_lb = take(sizeof(double) * (size_t)it.n);
-        p.o_ub = take(sizeof(double) * (size_t)it.n);
-        p.o_kind = take((size_t)it.n);
-        p.o_B = take(sizeof(int64_t) * (size_t)it.m);
-        p.o_N = take(sizeof(int64_t) * (size_t)p.nNa);
+        cur.bytes = &p.bytes;
+        p.o_AB = cur.take(sizeof(double) * (size_t)(p.ld * it.m));
+        p.o_AN = cur.take(sizeof(double) * (size_t)(p.ld * p.nNa));
+        p.o_cB = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_cN = cur.take(sizeof(double) * (size_t)p.nNa);
+        p.o_b = cur.take(sizeof(double) * (size_t)it.m);
+        p.o_lb = cur.take(sizeof(double) * (size_t)it.n);
+        p.o_ub = cur.take(sizeof(double) * (size_t)it.n);
+        p.o_kind = cur.take((size_t)it.n);
+        p.o_B = cur.take(sizeof(int64_t) * (size_t)it.m);
+        p.o_N = cur.take(sizeof(int64_t) * (size_t)p.nNa);
     }
-    owner = nullptr;
-    L.o_args = take(sizeof(StartBatchArgs) * R);
-    L.stage_bytes = off;
+    cur.bytes = nullptr;
+    L.o_args = cur.take(sizeof(StartBatchArgs) * R);
+    L.stage_bytes = cur.off;
     for (size_t k = 0; k < R; ++k) {
         BstartPlan &p = plan[k];
-        owner = &p;
-        p.o_r = take(sizeof(double) * (size_t)items[p.item].m);
-        p.o_rho = take(sizeof(double) * (size_t)items[p.item].m);
-        p.o_omega = take(sizeof(double));
-        p.o_steps = take(sizeof(int32_t));
-        p.o_rkeep = take(sizeof(double) * 2 * BPOST_ROWS * (size_t)(p.nbn > 0 ? p.nbn : 1));
+        cur.bytes = &p.bytes;
+        p.o_r = cur.take(sizeof(double) * (size_t)items[p.item].m);
+        p.o_rho = cur.take(sizeof(double) * (size_t)items[p.item].m);
+        p.o_omega = cur.take(sizeof(double));
+        p.o_steps = cur.take(sizeof(int32_t));
+        p.o_rkeep = cur.take(sizeof(double) * 2 * BPOST_ROWS * (size_t)(p.nbn > 0 ? p.nbn : 1));
     }
-    L.total = off;
+    L.total = cur.off;
     return L;
 }
 
@@ -289,7 +283,7 @@ ellp_status bstart_run_chunk(ellp_batch_item *items, int mode, double eps, ellp_
     hipStream_t stream = cl.hs.stream;
     unsigned char *h = static_cast<unsigned char *>(cl.stage.p);
     unsigned char *dv = static_cast<unsigned char *>(cl.slab.p);
-    StartBatchArgs *h_args = reinterpret_cast<StartBatchArgs *>(h + L.o_args);
+    StartBatchArgs *h_args = slab_at<StartBatchArgs>(h, L.o_args);
     size_t lds = 0;
     for (size_t k = 0; k < R; ++k) {
         const BstartPlan &p = plan[k];
@@ -297,19 +291,7 @@ ellp_status bstart_run_chunk(ellp_batch_item *items, int mode, double eps, ellp_
         const int64_t m = it.m, n = it.n, nN = it.n_N, ld = p.ld;
         memset(h + p.o_x, 0, sizeof(double) * (size_t)n);  // the pass for d_N reads x before the labels are made
         memset(h + p.o_fail, 0, sizeof(int));
-        double *AB = reinterpret_cast<double *>(h + p.o_AB), *AN = reinterpret_cast<double *>(h + p.o_AN);
-        double *cB = reinterpret_cast<double *>(h + p.o_cB), *cN = reinterpret_cast<double *>(h + p.o_cN);
-        for (int64_t j = 0; j < m; ++j) {
-            memcpy(AB + j * ld, it.A + it.B_index[j] * m, sizeof(double) * (size_t)m);
-            memset(AB + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
-            cB[j] = it.c[it.B_index[j]];
-        }
-        if (nN == 0) memset(AN, 0, sizeof(double) * (size_t)ld);
-        for (int64_t j = 0; j < nN; ++j) {
-            memcpy(AN + j * ld, it.A + it.N_index[j] * m, sizeof(double) * (size_t)m);
-            memset(AN + j * ld + m, 0, sizeof(double) * (size_t)(ld - m));
-            cN[j] = it.c[it.N_index[j]];
-        }
+        batch_stage_basis(h, it, ld, p.o_AB, p.o_AN, p.o_cB, p.o_cN);
         memcpy(h + p.o_b, it.b, sizeof(double) * (size_t)m);
         memcpy(h + p.o_lb, it.lb, sizeof(double) * (size_t)n);
         memcpy(h + p.o_ub, it.ub, sizeof(double) * (size_t)n);
@@ -320,48 +302,33 @@ ellp_status bstart_run_chunk(ellp_batch_item *items, int mode, double eps, ellp_
             memcpy(h + p.o_Nb, it.N_bound, (size_t)nN);
         }
         StartBatchArgs a{};
-        a.A_B = reinterpret_cast<const double *>(dv + p.o_AB);
-        a.A_N = reinterpret_cast<const double *>(dv + p.o_AN);
-        a.c_N = reinterpret_cast<const double *>(dv + p.o_cN);
-        a.x = reinterpret_cast<double *>(dv + p.o_x);
-        a.y = reinterpret_cast<double *>(dv + p.o_y);
-        a.d = reinterpret_cast<double *>(dv + p.o_d);
-        a.r = reinterpret_cast<double *>(dv + p.o_r);
-        a.rho = reinterpret_cast<double *>(dv + p.o_rho);
-        a.omega = reinterpret_cast<double *>(dv + p.o_omega);
-        a.xomega = reinterpret_cast<double *>(dv + p.o_xomega);
-        a.rkeep = reinterpret_cast<double *>(dv + p.o_rkeep);
+        a.A_B = slab_at<const double>(dv, p.o_AB);
+        a.A_N = slab_at<const double>(dv, p.o_AN);
+        a.c_N = slab_at<const double>(dv, p.o_cN);
+        a.x = slab_at<double>(dv, p.o_x);
+        a.y = slab_at<double>(dv, p.o_y);
+        a.d = slab_at<double>(dv, p.o_d);
+        a.r = slab_at<double>(dv, p.o_r);
+        a.rho = slab_at<double>(dv, p.o_rho);
+        a.omega = slab_at<double>(dv, p.o_omega);
+        a.xomega = slab_at<double>(dv, p.o_xomega);
+        a.rkeep = slab_at<double>(dv, p.o_rkeep);
         a.Nb = dv + p.o_Nb;
-        a.steps = reinterpret_cast<int32_t *>(dv + p.o_steps);
-        a.xsteps = reinterpret_cast<int32_t *>(dv + p.o_xsteps);
-        a.changed = reinterpret_cast<long long *>(dv + p.o_changed);
-        a.fail = reinterpret_cast<int *>(dv + p.o_fail);
-        a.verdict = reinterpret_cast<StartVerdict *>(dv + p.o_verdict);
+        a.steps = slab_at<int32_t>(dv, p.o_steps);
+        a.xsteps = slab_at<int32_t>(dv, p.o_xsteps);
+        a.changed = slab_at<long long>(dv, p.o_changed);
+        a.fail = slab_at<int>(dv, p.o_fail);
+        a.verdict = slab_at<StartVerdict>(dv, p.o_verdict);
         a.ld = ld;
         a.by_d = mode == ELLP_START_LABELS_BY_D;
         a.eps = eps;
-        PostReportArgs &ra = a.rep;
-        ra.r = a.r; ra.d = a.d; ra.rho = a.rho; ra.y = a.y; ra.omega = a.omega;
-        ra.b = reinterpret_cast<const double *>(dv + p.o_b);
-        ra.x = a.x;
-        ra.lb = reinterpret_cast<const double *>(dv + p.o_lb);
-        ra.ub = reinterpret_cast<const double *>(dv + p.o_ub);
-        ra.c_B = reinterpret_cast<const double *>(dv + p.o_cB);
-        ra.c_N = a.c_N;
-        ra.c_tail = nullptr;  // n_c == n
-        ra.kind = dv + p.o_kind;
-        ra.Nb = a.Nb;
-        ra.B_index = reinterpret_cast<const int64_t *>(dv + p.o_B);
-        ra.N_index = reinterpret_cast<const int64_t *>(dv + p.o_N);
-        ra.m = m; ra.n = n; ra.n_c = n; ra.nN = nN;
-        ra.steps = 0;  // the batch reads a.steps on the device
-        ra.out = reinterpret_cast<ellp_kkt *>(dv + p.o_kkt);
+        bpost_report_args(a.rep, dv, p, it);  // rep.x = x, rep.Nb = Nb; c_tail stays NULL: n_c == n
         h_args[k] = a;
         if (p.lds > lds) lds = p.lds;
     }
     // the outputs' region goes up too: x as zeros, the given labels and the fail flags are read before they are written
     HIPCHK(hipMemcpyAsync(dv, h, L.stage_bytes, hipMemcpyHostToDevice, stream));
-    const StartBatchArgs *d_args = reinterpret_cast<const StartBatchArgs *>(dv + L.o_args);
+    const StartBatchArgs *d_args = slab_at<const StartBatchArgs>(dv, L.o_args);
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_start_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // ELLP_POST_PROFILE=1 (tools/batch_start_time.py): one line per chunk, m = the chunk's items, lu_ms = k_start_batch,
     // rest_ms = the reports
@@ -381,13 +348,8 @@ ellp_status bstart_run_chunk(ellp_batch_item *items, int mode, double eps, ellp_
     for (size_t k = 0; k < R; ++k) {
         const BstartPlan &p = plan[k];
         ellp_batch_item &it = items[p.item];
-        int fail = 0;
-        memcpy(&fail, h + p.o_fail, sizeof(int));
-        if (fail) {  // every output of the item, N_bound too, stays as it was
-            set_err(it.err, sizeof(it.err), "invalid B, A_B is not invertible");
-            status_out[p.item] = ELLP_ERR_SINGULAR;
-            continue;
-        }
+        // a singular basis: every output of the item, N_bound too, stays as it was
+        if (batch_item_singular(h, p.o_fail, it, &status_out[p.item])) continue;
         memcpy(it.x, h + p.o_x, sizeof(double) * (size_t)it.n);
         if (it.n_N > 0) memcpy(it.N_bound, h + p.o_Nb, (size_t)it.n_N);
         if (it.y) memcpy(it.y, h + p.o_y, sizeof(double) * (size_t)it.m);
@@ -433,9 +395,6 @@ extern "C" ellp_status ellp_batch_basis_start(int64_t count, ellp_batch_item *it
         set_err(errbuf, errlen, "basis_start: unknown mode %d", mode);
         return ELLP_ERR_ARG;
     }
-    size_t budget = (size_t)2 << 30;  // slab bytes per chunk, as ellp_batch_solve_with_initial
-    if (const char *v = getenv("ELLP_BATCH_MAX_BYTES"); v && v[0] && atoll(v) > 0 && (size_t)atoll(v) < budget) budget = (size_t)atoll(v);
-
     // ---- per item: the single call's checks, then who runs it (all before any HIP call)
     std::vector<BstartPlan> plan;
     std::vector<int64_t> single;
@@ -473,40 +432,13 @@ extern "C" ellp_status ellp_batch_basis_start(int64_t count, ellp_batch_item *it
     if (plan.empty() && single.empty()) return ELLP_OPTIMAL;
 
     if (!plan.empty()) {
-        size_t max_stage = 0, max_total = 0;
-        (void)bstart_layout(items, plan.data(), plan.size());  // every item's share of a slab
-        const std::vector<size_t> cut = bpost_cuts(plan, budget);
-        for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const BpostLayout L = bstart_layout(items, plan.data() + cut[c], cut[c + 1] - cut[c]);
-            max_stage = L.stage_bytes > max_stage ? L.stage_bytes : max_stage;
-            max_total = L.total > max_total ? L.total : max_total;
-        }
-        ellp_opts opts;
-        ellp_default_opts(&opts);
-        if (opts_in) opts = *opts_in;
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-            set_err(errbuf, errlen, "no HIP device available (this library has no CPU path)");
-            return ELLP_ERR_DEVICE;
-        }
-        int dev = opts.device;
-        if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-        HIPCHK(hipSetDevice(dev));
-        BatchCleanup cl;
-        HIPCHK(host_set_acquire(dev, &cl.hs));
-        HIPCHK(batch_buf_acquire(dev, true, max_stage, &cl.stage));
-        HIPCHK(batch_buf_acquire(dev, false, max_total, &cl.slab));
-        const double eps = opts.eps > 0.0 ? opts.eps : 1e-10;  // post_host_engine's
-        for (size_t c = 0; c + 1 < cut.size(); ++c) {
-            const ellp_status rc =
-                bstart_run_chunk(items, mode, eps, infos, plan.data() + cut[c], cut[c + 1] - cut[c], cl, status_out, errbuf, errlen);
-            if (rc != ELLP_OPTIMAL) {  // the items that did not run say so
-                for (size_t k = cut[c]; k < plan.size(); ++k) status_out[plan[k].item] = rc;
-                for (int64_t i : single) status_out[i] = rc;
-                return rc;
-            }
-            g_batch_start_info[3] += 1;
-        }
+        const double eps = opts_in && opts_in->eps > 0.0 ? opts_in->eps : 1e-10;  // post_host_engine's
+        const ellp_status rc = batch_drive(
+            plan, single, BPOST_CHUNK_SLACK, opts_in, status_out, &g_batch_start_info[3],
+            [&](BstartPlan *pl, size_t R) { return bstart_layout(items, pl, R); },
+            [&](BstartPlan *pl, size_t R, BatchCleanup &cl) { return bstart_run_chunk(items, mode, eps, infos, pl, R, cl, status_out, errbuf, errlen); },
+            errbuf, errlen);
+        if (rc != ELLP_OPTIMAL) return rc;
     }
     // ---- the items the kernel does not take: the single call, inside this one
     for (int64_t i : single) {

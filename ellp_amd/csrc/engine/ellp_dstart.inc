@@ -506,8 +506,7 @@ extern "C" ellp_status ellp_batch_dual_phase1_start(int64_t count, ellp_batch_it
     if (plan.empty()) return ELLP_OPTIMAL;
     // the sub-panel width and k_bl_factor variant launch_refactor picks (every item has m <= 1,024, so the same for all)
     const auto [bl_nt, nbw_max] = bl_factor_variant(MID_MAX_M);
-    size_t budget = (size_t)2 << 30;
-    if (const char *v = getenv("ELLP_BATCH_MAX_BYTES"); v && v[0] && atoll(v) > 0 && (size_t)atoll(v) < budget) budget = (size_t)atoll(v);
+    const size_t budget = batch_budget();
     int dev = opts.device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
     int ndev = 0;

@@ -54,6 +54,32 @@ void unflatten(const Flat &f, Point &pt) {
     }
 }
 
+// the item of a batched call: the standard form, its flattened bounds and index sets, the point x (and y, d where the call
+// reads or writes them)
+ellp_batch_item batch_item_of(const StandardForm &sf, Flat &f, std::vector<double> &x, std::vector<double> *y = nullptr,
+                              std::vector<double> *d = nullptr) {
+    ellp_batch_item it;
+    std::memset(&it, 0, sizeof(it));
+    it.m = static_cast<std::int64_t>(sf.rows());
+    it.n = static_cast<std::int64_t>(sf.cols());
+    it.n_c = static_cast<std::int64_t>(sf.bounds.size());
+    it.A = sf.A.a.data();
+    it.c = sf.c.data();
+    it.b = sf.b.data();
+    it.bound_kind = f.kind.data();
+    it.lb = f.lb.data();
+    it.ub = f.ub.data();
+    it.x = x.data();
+    it.B_index = f.B.data();
+    it.n_B = static_cast<std::int64_t>(f.B.size());
+    it.N_index = f.N.data();
+    it.N_bound = f.Nb.data();
+    it.n_N = static_cast<std::int64_t>(f.N.size());
+    if (y) it.y = y->data();
+    if (d) it.d = d->data();
+    return it;
+}
+
 ellp_opts make_opts(std::uint64_t max_iter, const EngineOptions &e) {
     ellp_opts o;
     ellp_default_opts(&o);
@@ -841,27 +867,7 @@ bool run_seams(int kind, std::vector<Seam *> &seams, std::uint64_t max_iter, con
     for (size_t k = 0; k < seams.size(); ++k) {
         Seam &s = *seams[k];
         s.f = flatten(*s.sf, *s.pt);
-        ellp_batch_item &it = items[k];
-        std::memset(&it, 0, sizeof(it));
-        it.m = static_cast<std::int64_t>(s.sf->rows());
-        it.n = static_cast<std::int64_t>(s.sf->cols());
-        it.n_c = static_cast<std::int64_t>(s.sf->bounds.size());
-        it.A = s.sf->A.a.data();
-        it.c = s.sf->c.data();
-        it.b = s.sf->b.data();
-        it.bound_kind = s.f.kind.data();
-        it.lb = s.f.lb.data();
-        it.ub = s.f.ub.data();
-        it.x = s.pt->x.data();
-        it.B_index = s.f.B.data();
-        it.n_B = static_cast<std::int64_t>(s.f.B.size());
-        it.N_index = s.f.N.data();
-        it.N_bound = s.f.Nb.data();
-        it.n_N = static_cast<std::int64_t>(s.f.N.size());
-        if (s.dp) {
-            it.y = s.dp->y.data();
-            it.d = s.dp->d.data();
-        }
+        items[k] = batch_item_of(*s.sf, s.f, s.pt->x, s.dp ? &s.dp->y : nullptr, s.dp ? &s.dp->d : nullptr);
     }
     const ellp_opts o = make_opts(max_iter, eng);
     std::vector<ellp_status> st(seams.size());
@@ -999,21 +1005,7 @@ void primal_batch(std::vector<Problem> &probs, const std::vector<size_t> &which,
         it.in2 = phase2_inputs(*it.p1);
         ellp_batch_primal_item &b = bi[k];
         std::memset(&b, 0, sizeof(b));
-        b.p1.m = static_cast<std::int64_t>(sf.rows());
-        b.p1.n = static_cast<std::int64_t>(sf.cols());
-        b.p1.n_c = static_cast<std::int64_t>(sf.bounds.size());
-        b.p1.A = sf.A.a.data();
-        b.p1.c = sf.c.data();
-        b.p1.b = sf.b.data();
-        b.p1.bound_kind = it.f.kind.data();
-        b.p1.lb = it.f.lb.data();
-        b.p1.ub = it.f.ub.data();
-        b.p1.x = it.p1->point.x.data();
-        b.p1.B_index = it.f.B.data();
-        b.p1.n_B = static_cast<std::int64_t>(it.f.B.size());
-        b.p1.N_index = it.f.N.data();
-        b.p1.N_bound = it.f.Nb.data();
-        b.p1.n_N = static_cast<std::int64_t>(it.f.N.size());
+        b.p1 = batch_item_of(sf, it.f, it.p1->point.x);
         b.c2 = it.in2.c.data();
         b.bound_kind2 = it.in2.kind.data();
         b.lb2 = it.in2.lb.data();
@@ -1127,25 +1119,7 @@ void dual_batch(std::vector<Problem> &probs, const std::vector<size_t> &which, s
             const StandardForm &sf = deferred[k]->p1->std_form;
             DualFeasiblePoint &dp = deferred[k]->p1->point;
             fl[k] = flatten(sf, dp.point);
-            ellp_batch_item &b = bi[k];
-            std::memset(&b, 0, sizeof(b));
-            b.m = static_cast<std::int64_t>(sf.rows());
-            b.n = static_cast<std::int64_t>(sf.cols());
-            b.n_c = static_cast<std::int64_t>(sf.bounds.size());
-            b.A = sf.A.a.data();
-            b.c = sf.c.data();
-            b.b = sf.b.data();
-            b.bound_kind = fl[k].kind.data();
-            b.lb = fl[k].lb.data();
-            b.ub = fl[k].ub.data();
-            b.x = dp.point.x.data();
-            b.B_index = fl[k].B.data();
-            b.n_B = static_cast<std::int64_t>(fl[k].B.size());
-            b.N_index = fl[k].N.data();
-            b.N_bound = fl[k].Nb.data();
-            b.n_N = static_cast<std::int64_t>(fl[k].N.size());
-            b.y = dp.y.data();
-            b.d = dp.d.data();
+            bi[k] = batch_item_of(sf, fl[k], dp.point.x, &dp.y, &dp.d);
         }
         const ellp_opts o = make_opts(max_iter, eng);
         std::vector<ellp_status> st(deferred.size(), ELLP_ERR_ARG);
@@ -1257,16 +1231,17 @@ void dual_batch(std::vector<Problem> &probs, const std::vector<size_t> &which, s
     }
 }
 
-// solve_batch(..., postsolve): duals, reduced costs and the report of every Optimal outcome, ONE ellp_batch_postsolve call
-// for all of them (the items over 128 rows take the single call's path inside it); without rows it is answered on the
-// host, as attach_postsolve answers it.  An item's refusal or singular basis becomes that outcome's exception, the one
-// solve() with_postsolve(true) throws.  No Optimal outcome with rows: not one device call.
-void batch_postsolve(std::vector<BatchOutcome> &out, const EngineOptions &eng) {
+// What batch_postsolve and batch_ranging share.  Every Optimal outcome gets its results from ONE batched call for all of them
+// (the items over 128 rows take the single call's path inside it); without rows it is answered on the host (`host`, what the
+// attach_ function of solve() does there).  An item's refusal or singular basis becomes that outcome's exception, the one
+// solve() with the same request throws.  No Optimal outcome with rows: not one device call.  Payload: the output arrays of
+// one job, the struct that hands them to the call (out) and their way into the Solution (map)
+template <class Payload, class Host, class Call>
+void batch_attach(std::vector<BatchOutcome> &out, const EngineOptions &eng, Host host, Call call) {
     struct Job {
         size_t k;
         Flat f;
-        std::vector<double> y, d;
-        ellp_kkt kkt;
+        Payload p;
     };
     auto fail = [&](size_t k) {
         out[k].error = std::current_exception();
@@ -1278,130 +1253,60 @@ void batch_postsolve(std::vector<BatchOutcome> &out, const EngineOptions &eng) {
         Solution &sol = *out[k].result.solution;
         if (sol.std_form.rows() == 0) {
             try {
-                attach_postsolve(sol, nullptr, eng);
+                host(sol, nullptr, eng);
             } catch (...) {
                 fail(k);
             }
             continue;
         }
-        Job j;
-        j.k = k;
-        j.f = flatten(sol.std_form, sol.point);
-        j.y.assign(sol.std_form.rows(), 0.0);
-        j.d.assign(sol.std_form.bounds.size(), 0.0);
-        std::memset(&j.kkt, 0, sizeof(j.kkt));
-        jobs.push_back(std::move(j));
+        jobs.push_back(Job{k, flatten(sol.std_form, sol.point), Payload(sol.std_form)});
     }
     if (jobs.empty()) return;
     std::vector<ellp_batch_item> items(jobs.size());
-    std::vector<ellp_batch_post_out> outs(jobs.size());
+    std::vector<decltype(jobs[0].p.out())> outs(jobs.size());
     for (size_t q = 0; q < jobs.size(); ++q) {
-        Job &j = jobs[q];
-        Solution &sol = *out[j.k].result.solution;
-        const StandardForm &sf = sol.std_form;
-        ellp_batch_item &it = items[q];
-        std::memset(&it, 0, sizeof(it));
-        it.m = static_cast<std::int64_t>(sf.rows());
-        it.n = static_cast<std::int64_t>(sf.cols());
-        it.n_c = static_cast<std::int64_t>(sf.bounds.size());
-        it.A = sf.A.a.data();
-        it.c = sf.c.data();
-        it.b = sf.b.data();
-        it.bound_kind = j.f.kind.data();
-        it.lb = j.f.lb.data();
-        it.ub = j.f.ub.data();
-        it.x = sol.point.x.data();
-        it.B_index = j.f.B.data();
-        it.n_B = static_cast<std::int64_t>(j.f.B.size());
-        it.N_index = j.f.N.data();
-        it.N_bound = j.f.Nb.data();
-        it.n_N = static_cast<std::int64_t>(j.f.N.size());
-        outs[q] = ellp_batch_post_out{j.y.data(), j.d.data(), nullptr, &j.kkt};
+        Solution &sol = *out[jobs[q].k].result.solution;
+        items[q] = batch_item_of(sol.std_form, jobs[q].f, sol.point.x);
+        outs[q] = jobs[q].p.out();
     }
     const ellp_opts o = make_opts(0, eng);
     std::vector<ellp_status> st(jobs.size(), ELLP_ERR_DEVICE);
     char err[512] = {0};
-    const ellp_status rc = ellp_batch_postsolve(static_cast<std::int64_t>(items.size()), items.data(), &o, outs.data(), st.data(), err, sizeof(err));
+    const ellp_status rc = call(static_cast<std::int64_t>(items.size()), items.data(), &o, outs.data(), st.data(), err, sizeof(err));
     for (size_t q = 0; q < jobs.size(); ++q) {
         Job &j = jobs[q];
         try {
-            if (rc != ELLP_OPTIMAL) to_status(rc, err);                 // throws, as attach_postsolve
+            if (rc != ELLP_OPTIMAL) to_status(rc, err);  // throws, as the attach_ function
             else if (st[q] != ELLP_OPTIMAL) to_status(st[q], items[q].err);
-            map_postsolve(*out[j.k].result.solution, j.y, j.d, j.kkt);
+            j.p.map(*out[j.k].result.solution);
         } catch (...) {
             fail(j.k);
         }
     }
 }
 
-// solve_batch(..., ranging): the ranges, and with them the duals, reduced costs and report, of every Optimal outcome from ONE
-// ellp_batch_ranging call for all of them and no ellp_batch_postsolve call (the items over 128 rows take the single call's
-// steps inside it); without rows attach_ranging answers on the host.  An item's refusal or singular basis becomes that
-// outcome's exception, the one solve() with_ranging(true) throws.  No Optimal outcome with rows: not one device call.
+// solve_batch(..., postsolve): duals, reduced costs and the report, from ellp_batch_postsolve
+void batch_postsolve(std::vector<BatchOutcome> &out, const EngineOptions &eng) {
+    struct Payload {
+        std::vector<double> y, d;
+        ellp_kkt kkt;
+        explicit Payload(const StandardForm &sf) : y(sf.rows(), 0.0), d(sf.bounds.size(), 0.0) { std::memset(&kkt, 0, sizeof(kkt)); }
+        ellp_batch_post_out out() { return ellp_batch_post_out{y.data(), d.data(), nullptr, &kkt}; }
+        void map(Solution &sol) const { map_postsolve(sol, y, d, kkt); }
+    };
+    batch_attach<Payload>(out, eng, attach_postsolve, ellp_batch_postsolve);
+}
+
+// solve_batch(..., ranging): the ranges, and with them the duals, reduced costs and report, from ellp_batch_ranging (and no
+// ellp_batch_postsolve call)
 void batch_ranging(std::vector<BatchOutcome> &out, const EngineOptions &eng) {
-    struct Job {
-        size_t k;
-        Flat f;
+    struct Payload {
         RangeArrays ra;
+        explicit Payload(const StandardForm &sf) : ra(sf.rows(), sf.bounds.size()) {}
+        ellp_batch_range_out out() { return ellp_batch_range_out{ra.out(), nullptr}; }
+        void map(Solution &sol) const { map_ranging(sol, ra); }
     };
-    auto fail = [&](size_t k) {
-        out[k].error = std::current_exception();
-        out[k].result = SolverResult{};
-    };
-    std::vector<Job> jobs;
-    for (size_t k = 0; k < out.size(); ++k) {
-        if (out[k].error || out[k].result.kind != SolverResult::Optimal || !out[k].result.solution) continue;
-        Solution &sol = *out[k].result.solution;
-        if (sol.std_form.rows() == 0) {
-            try {
-                attach_ranging(sol, nullptr, eng);
-            } catch (...) {
-                fail(k);
-            }
-            continue;
-        }
-        jobs.push_back(Job{k, flatten(sol.std_form, sol.point), RangeArrays(sol.std_form.rows(), sol.std_form.bounds.size())});
-    }
-    if (jobs.empty()) return;
-    std::vector<ellp_batch_item> items(jobs.size());
-    std::vector<ellp_batch_range_out> outs(jobs.size());
-    for (size_t q = 0; q < jobs.size(); ++q) {
-        Job &j = jobs[q];
-        Solution &sol = *out[j.k].result.solution;
-        const StandardForm &sf = sol.std_form;
-        ellp_batch_item &it = items[q];
-        std::memset(&it, 0, sizeof(it));
-        it.m = static_cast<std::int64_t>(sf.rows());
-        it.n = static_cast<std::int64_t>(sf.cols());
-        it.n_c = static_cast<std::int64_t>(sf.bounds.size());
-        it.A = sf.A.a.data();
-        it.c = sf.c.data();
-        it.b = sf.b.data();
-        it.bound_kind = j.f.kind.data();
-        it.lb = j.f.lb.data();
-        it.ub = j.f.ub.data();
-        it.x = sol.point.x.data();
-        it.B_index = j.f.B.data();
-        it.n_B = static_cast<std::int64_t>(j.f.B.size());
-        it.N_index = j.f.N.data();
-        it.N_bound = j.f.Nb.data();
-        it.n_N = static_cast<std::int64_t>(j.f.N.size());
-        outs[q] = ellp_batch_range_out{j.ra.out(), nullptr};
-    }
-    const ellp_opts o = make_opts(0, eng);
-    std::vector<ellp_status> st(jobs.size(), ELLP_ERR_DEVICE);
-    char err[512] = {0};
-    const ellp_status rc = ellp_batch_ranging(static_cast<std::int64_t>(items.size()), items.data(), &o, outs.data(), st.data(), err, sizeof(err));
-    for (size_t q = 0; q < jobs.size(); ++q) {
-        Job &j = jobs[q];
-        try {
-            if (rc != ELLP_OPTIMAL) to_status(rc, err);                 // throws, as attach_ranging
-            else if (st[q] != ELLP_OPTIMAL) to_status(st[q], items[q].err);
-            map_ranging(*out[j.k].result.solution, j.ra);
-        } catch (...) {
-            fail(j.k);
-        }
-    }
+    batch_attach<Payload>(out, eng, attach_ranging, ellp_batch_ranging);
 }
 
 // solve_batch(..., starts): the problems that come with a start.  Per problem the steps of solve_from:
@@ -1473,23 +1378,10 @@ void start_batch(int solver, std::vector<Problem> &probs, const std::vector<cons
         j.dp.d.assign(sf.cols(), 0.0);
         std::memset(&infos[q], 0, sizeof(infos[q]));
         ellp_batch_item &it = items[q];
-        std::memset(&it, 0, sizeof(it));
-        it.m = static_cast<std::int64_t>(sf.rows());
-        it.n = it.n_c = static_cast<std::int64_t>(sf.cols());
-        it.A = sf.A.a.data();
-        it.c = sf.c.data();
-        it.b = sf.b.data();
-        it.bound_kind = j.f.kind.data();
-        it.lb = j.f.lb.data();
-        it.ub = j.f.ub.data();
-        it.x = j.dp.point.x.data();
-        it.B_index = j.B.data();
-        it.n_B = static_cast<std::int64_t>(j.B.size());
+        it = batch_item_of(sf, j.f, j.dp.point.x, &j.dp.y, &j.dp.d);  // n_c == n here (START_BAD_SIZE)
+        it.B_index = j.B.data();  // the mapped start, not the shape's placeholders, which the resizes above gave its counts
         it.N_index = j.N.data();
         it.N_bound = j.Nb.data();
-        it.n_N = static_cast<std::int64_t>(j.N.size());
-        it.y = j.dp.y.data();
-        it.d = j.dp.d.data();
     }
     const ellp_opts o0 = make_opts(0, eng);
     std::vector<ellp_status> st(jobs.size(), ELLP_ERR_DEVICE);

@@ -343,3 +343,27 @@ def test_large_items_take_the_single_path():
     _same_bits("big", res[1][1:5], alone)
     _same_bits("before", res[0][1:5], ref[0])
     _same_bits("after", res[2][1:5], ref[1])
+
+
+def test_refusal_chunks_and_single_path_in_one_call(monkeypatch):
+    """a refused item, two batched items, one on the single path and one more batched item, cut into chunks by the budget"""
+    from batch_driver_case import DRIVER_BUDGET, driver_items
+    E = _E()
+    f3, f17, f129, f128 = driver_items()
+    refused = _copy(f17)
+    refused.N[0] = refused.n + 3
+    run = [f3, f17, f129, f128]
+    alone = [_single(fp) for fp in [refused] + run]
+    assert alone[0][0] == E.ERR_ARG and alone[0][1] and [a[0] for a in alone[1:]] == [E.OPTIMAL] * 4
+    _, one = _batch([f3])
+    assert one["chunks"] == 1
+    per_chunk = one["launches"]
+    monkeypatch.setenv("ELLP_BATCH_MAX_BYTES", str(DRIVER_BUDGET))
+    res, info = _batch([refused] + run, fill=-7.5)
+    assert info["chunks"] >= 2
+    assert info == {"launches": per_chunk * info["chunks"], "batched": 3, "single": 1, "chunks": info["chunks"]}
+    st, y, d, r, k, msg = res[0]
+    assert (st, msg) == alone[0][:2] and k is None and all((v == -7.5).all() for v in (y, d, r))  # untouched
+    for pos, ((st, y, d, r, k, msg), a) in enumerate(zip(res[1:], alone[1:]), 1):
+        assert st == E.OPTIMAL and msg == "", (pos, st, msg)
+        _same_bits(("driver", pos), (y, d, r, k), a[2:])

@@ -275,3 +275,28 @@ def test_same_bits_twice():
             assert getattr(ra, name).tobytes() == getattr(rb, name).tobytes(), name
         assert Wa.tobytes() == Wb.tobytes()
         assert np.float64(ra.inverse_residual).tobytes() == np.float64(rb.inverse_residual).tobytes()
+
+
+def test_refusal_chunks_and_single_path_in_one_call(monkeypatch):
+    """a refused item, two batched items (3 and 17 rows), one of 129 rows on the single path and one more batched item of
+    128 rows, cut into chunks by the budget: every branch of the batched calls' shared chunk driver in one call"""
+    from batch_driver_case import DRIVER_BUDGET, driver_items
+    E = _E()
+    f3, f17, f129, f128 = driver_items()
+    refused = _copy(f17)
+    refused.N[0] = refused.n + 3
+    run = [f3, f17, f129, f128]
+    alone = [_single(fp) for fp in [refused] + run]
+    assert alone[0][0] == E.ERR_ARG and alone[0][1] and [a[0] for a in alone[1:]] == [E.OPTIMAL] * 4
+    _, one = _batch([f3])
+    assert one["chunks"] == 1
+    per_chunk = one["launches"]
+    monkeypatch.setenv("ELLP_BATCH_MAX_BYTES", str(DRIVER_BUDGET))
+    res, info = _batch([refused] + run, fill=-7.5)
+    assert info["chunks"] >= 2
+    assert info == {"launches": per_chunk * info["chunks"], "batched": 3, "single": 1, "chunks": info["chunks"]}
+    st, rg, W, msg = res[0]
+    assert (st, msg) == alone[0][:2] and _untouched(rg, W, -7.5)
+    for pos, ((st, rg, W, msg), a) in enumerate(zip(res[1:], alone[1:]), 1):
+        assert st == E.OPTIMAL and msg == "", (pos, st, msg)
+        _same_rg(("driver", pos), rg, a[2])

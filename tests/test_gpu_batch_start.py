@@ -300,3 +300,27 @@ def test_against_exact_model():
         tol_d = float((np.abs(A).T @ tol_y).max()) + float(big_d)
         assert abs(info["dual_infeasibility"] - float(mod.dual_infeasibility)) <= tol_d + U * float(mod.dual_infeasibility), name
         assert (info["primal_feasible"], info["dual_feasible"]) == mod.flags(EPS), (name, info, mod.flags(EPS))
+
+
+def test_refusal_chunks_and_single_path_in_one_call(monkeypatch):
+    """a refused item, two batched items (3 and 17 rows), one of 129 rows on the single path and one more batched item of
+    128 rows, cut into chunks by the budget: every branch of the batched calls' shared chunk driver in one call (LABELS_BY_D)"""
+    from batch_driver_case import DRIVER_BUDGET, driver_items
+    E = _E()
+    mode = 1
+    f3, f17, f129, f128 = driver_items()
+    refused = _copy(f17)
+    refused.N[0] = refused.n + 3
+    run = [f3, f17, f129, f128]
+    alone = [E.basis_start(_copy(fp), mode) for fp in [refused] + run]
+    assert alone[0][0] == E.ERR_ARG and alone[0][5]["message"] and [a[0] for a in alone[1:]] == [E.OPTIMAL] * 4
+    monkeypatch.setenv("ELLP_BATCH_MAX_BYTES", str(DRIVER_BUDGET))
+    res, info = _batch([refused] + run, mode, fill=-7.5)
+    assert info["chunks"] >= 2
+    assert info == {"launches": 2 * info["chunks"], "batched": 3, "single": 1, "chunks": info["chunks"]}
+    st, x, y, d, Nb, inf = res[0]
+    assert st == E.ERR_ARG and inf == {"message": alone[0][5]["message"]}
+    assert all((v == -7.5).all() for v in (x, y, d)) and (Nb == refused.Nb).all()  # untouched
+    for pos, (got, a) in enumerate(zip(res[1:], alone[1:]), 1):
+        assert got[5]["message"] == "", (pos, got[5])
+        _same_bits(("driver", pos), got, a)
